@@ -79,8 +79,14 @@ def parse(argv=None):
     ap.add_argument("--c4-frames", type=int, default=32768, help="config 4: padded frames per micro-batch (n x M_pad)")
     ap.add_argument("--gather-dtype", choices=["f32", "bf16"], default="f32",
                     help="dtype of the mel message of the per-step RCCL gather (bf16 halves the xGMI bytes; the lengths stay int64)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (every tensor of the "
+                         "forward's output) as DIR/<name>.npy, float32 / float64, at most 64 MiB in all (rank 0)")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ parent: start N ranks
@@ -245,6 +251,52 @@ def other_from_profiles():
     return _profile_json("other_kernels.json")
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 23
+
+
+def _flatten_outputs(obj, prefix: str, found: dict) -> None:
+    """Tensors of a (nested) NamedTuple / dict output, keyed by dotted field name; None fields are skipped."""
+    if obj is None:
+        return
+    if hasattr(obj, "_fields"):
+        for k in obj._fields:
+            _flatten_outputs(getattr(obj, k), f"{prefix}{k}.", found)
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            _flatten_outputs(obj[k], f"{prefix}{k}.", found)
+    elif hasattr(obj, "detach"):
+        found[prefix[:-1]] = obj
+
+
+def dump_outputs(out, dirname: str, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Writes every tensor of `out` as DIR/<name>.npy: floating point as float32 (float64 stays float64), integers and
+    booleans as float64 (exact).  Each array may take budget / n_arrays bytes; a larger one is replaced by a fixed sample
+    of its flattened elements (indices drawn with DUMP_SEED from its element count, sorted), so two builds that compute
+    the same shapes write the same sample.  -> {name: {"shape", "dtype", "sampled"}}."""
+    import numpy as np
+    import torch
+    found: dict = {}
+    _flatten_outputs(out, "", found)
+    os.makedirs(dirname, exist_ok=True)
+    share = budget // max(1, len(found))
+    meta = {}
+    for name, t in found.items():
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.is_complex())
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy().reshape(-1)
+        cap = share // a.itemsize
+        sampled = a.size > cap
+        if sampled:
+            idx = np.random.default_rng(DUMP_SEED).choice(a.size, size=cap, replace=False)
+            a = a[np.sort(idx)]
+        else:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        meta[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": sampled}
+    return meta
+
+
 # ------------------------------------------------------------------------------------------------ worker
 def worker(args) -> int:
     import torch
@@ -373,10 +425,16 @@ def worker(args) -> int:
 
     # ---------------------------------------------------------------------------------------------- headline (config 3)
     step, pipes, lanes, d = fixed_batch_runner(B, max(1, args.in_flight))
-    elapsed = measure(step, args.steps, args.warmup, pipes)
-    out = step()
-    fence(pipes)
+    last = [None]
+
+    def timed_step():
+        last[0] = step()
+    elapsed = measure(timed_step, args.steps, args.warmup, pipes)
+    out = last[0]                  # the last TIMED step's outputs (measure() ends with a fence)
     assert torch.isfinite(out.mel).all()
+    if args.dump_outputs and rank == 0:
+        meta = dump_outputs(out, args.dump_outputs)
+        print(f"bench.py: wrote {len(meta)} arrays of the last timed step to {args.dump_outputs}", file=sys.stderr)
     frames = world * B * M * args.steps
     value = frames / elapsed
     line = None

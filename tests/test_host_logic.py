@@ -461,3 +461,53 @@ def test_bench_launcher_takes_siblings_down_when_a_rank_fails(tmp_path):
     t0 = time.time()
     r = subprocess.run([sys.executable, str(fake), "--gpus", "2"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 7 and time.time() - t0 < 60
+
+
+def test_bench_dump_outputs_writes_every_output_within_budget(tmp_path):
+    """`bench.py --dump-outputs DIR`: every tensor of the forward's (nested) output tuple becomes DIR/<name>.npy in float32
+    (float64 for integers and booleans, exact), None fields are skipped, arrays over their share of the budget are a fixed
+    seeded sample - the same one on every run - and the files stay within the budget."""
+    from typing import NamedTuple, Optional
+
+    import numpy as np
+
+    import bench
+
+    class Inner(NamedTuple):
+        lengths: torch.Tensor
+        hard: torch.Tensor
+        unused: Optional[torch.Tensor]
+
+    class Out(NamedTuple):
+        mel: torch.Tensor
+        inner: Inner
+        losses: Optional[dict]
+
+    g = torch.Generator().manual_seed(0)
+    out = Out(mel=torch.randn(4, 80, 300, generator=g).to(torch.bfloat16), inner=Inner(
+        lengths=torch.tensor([300, 7, 2 ** 40, -1], dtype=torch.int64), hard=torch.rand(4, 30, 20, generator=g) > 0.5,
+        unused=None), losses={"flow": torch.tensor(0.25, dtype=torch.float64)})
+    budget = 4 * 80 * 300 * 4 // 2               # the mel alone would take twice its share
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        meta = bench.dump_outputs(out, str(d), budget=budget)
+        assert sorted(meta) == ["inner.hard", "inner.lengths", "losses.flow", "mel"]
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in meta)
+        assert sum(os.path.getsize(d / f) - 128 for f in os.listdir(d)) <= budget      # .npy header: 128 bytes
+        runs.append({n: np.load(d / (n + ".npy")) for n in meta})
+    a = runs[0]
+    assert a["mel"].dtype == np.float32 and a["mel"].ndim == 1 and meta["mel"]["sampled"]
+    assert np.array_equal(a["mel"], runs[1]["mel"])
+    assert np.isin(a["mel"], out.mel.float().numpy().reshape(-1)).all()
+    assert a["inner.lengths"].dtype == np.float64 and a["inner.lengths"].tolist() == [300, 7, 2 ** 40, -1]
+    assert a["inner.hard"].shape == (4, 30, 20) and np.array_equal(a["inner.hard"], out.inner.hard.double().numpy())
+    assert a["losses.flow"].dtype == np.float64 and float(a["losses.flow"]) == 0.25
+
+
+def test_bench_rejects_a_step_count_below_one():
+    import bench
+    assert bench.parse(["--steps", "3", "--warmup", "0"]).steps == 3
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
