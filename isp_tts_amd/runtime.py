@@ -295,6 +295,17 @@ def layernorm(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], ada_sc
 
 
 # ------------------------------------------------------------------------------------------------- GEMM
+def _splitk_layout_ok(c2: Tensor, bias: Optional[Tensor], r2: Optional[Tensor], flags: int) -> bool:
+    """The pointer / leading-dimension half of vec_epilogue_ok (csrc/gemm.hip:541), which ispk_gemm_bf16_splitk requires on
+    top of its plan (the plan sees only M, N, K and flags).  Views that fail it (an offset `out=`, a bias slice off 16 bytes,
+    an odd row stride) go to ispk_gemm_bf16, whose other kernels take any layout."""
+    c_align = 8 if flags & EP_OUT_BF16 else 16
+    r_align = 8 if flags & EP_RESID_BF16 else 16
+    return (c2.stride(0) % 4 == 0 and c2.data_ptr() % c_align == 0 and
+            (r2 is None or (r2.stride(0) % 4 == 0 and r2.data_ptr() % r_align == 0)) and
+            (bias is None or bias.data_ptr() % 16 == 0))
+
+
 def gemm(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, resid: Optional[Tensor] = None,
          mask: Optional[Tensor] = None, flags: int = 0, out: Optional[Tensor] = None,
          out_dtype: Optional[torch.dtype] = None) -> Tensor:
@@ -317,6 +328,8 @@ def gemm(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, resid: Optional[Te
     if mask is not None:
         mask = mask.reshape(-1).contiguous()
         assert mask.dtype == torch.bool
+    if M == 0:      # nothing to compute; the C entries would refuse the NULL data_ptr() torch gives an empty tensor
+        return out
     if bf16:
         if out.dtype == torch.bfloat16:
             flags |= EP_OUT_BF16
@@ -324,7 +337,8 @@ def gemm(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, resid: Optional[Te
             flags |= EP_RESID_BF16
         fn = lib().ispk_gemm_bf16
         ks = lib().ispk_gemm_bf16_splitk_plan(M, N, K, flags) if M < 2048 and K >= 512 else 1
-        if ks > 1:      # few rows, long K: K slices on separate workgroups + one combine pass (ispk_gemm_bf16_splitk)
+        if ks > 1 and _splitk_layout_ok(c2, bias, r2, flags):
+            # few rows, long K: K slices on separate workgroups + one combine pass (ispk_gemm_bf16_splitk)
             ws = torch.empty((ks * M * N,), dtype=torch.float32, device=a.device)
             _launch(f"gemm_bf16_splitk<{ks}>", 2.0 * M * N * K, _gemm_bytes(a2, w, out, r2) + 8.0 * ks * M * N, lib().ispk_gemm_bf16_splitk,
                     a2.data_ptr(), a2.stride(0), w.data_ptr(), w.stride(0), c2.data_ptr(), c2.stride(0), _ptr(bias), _ptr(r2),
