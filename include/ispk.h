@@ -546,6 +546,11 @@ int32_t ispk_gemm_tn_bf16(const float* A, int64_t lda, const float* B, int64_t l
 int32_t ispk_gemm_tn_b16(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc, int32_t M,
                          int32_t N1, int32_t N2, const uint8_t* row_mask, int32_t accumulate, float* workspace,
                          int64_t workspace_floats, ispk_stream_t stream);
+/* Plan of this thread's last weight-gradient launch (ispk_gemm_tn_f32 / _bf16 / _b16 / _batched_f32; tests and profiler labels):
+ * returns the kernel that ran - 1 fp32, 2 bf16 in flight, 3 bf16 operands staged through registers, 4 bf16 operands by LDS-DMA
+ * (no row mask, batch 1, N1 and N2 multiples of 8); 0 = none yet - and writes the number of row ranges and the rows per range
+ * (a multiple of 32; the last range may be shorter) through the pointers that are not NULL. */
+int32_t ispk_gemm_tn_last_plan(int32_t* splits, int32_t* rows_per_split);
 /* The same product for `batch` independent pairs (A_b, B_b) at element strides stride_a / stride_b, C_b at stride_c - e.g. the
  * backward of the length regulator (temporal_adaptor.py:419-421: out_b = A_b x_b): d x_b = A_b^T d out_b per utterance.
  * row_mask (or NULL) is [batch][M]; workspace >= batch * N1 * N2 floats. */

@@ -1085,6 +1085,15 @@ extern "C" int32_t ispk_transpose_f32(const float* x, int64_t ldx, float* y, int
     return ispk_launch_status();
 }
 
+// What the last gemm_tn_launch of THIS thread dispatched (ispk_gemm_tn_last_plan): 1 gemm_tn_kernel (fp32), 2
+// gemm_tn_bf16_kernel<., false> (bf16 in flight), 3 gemm_tn_bf16_kernel<., true> (bf16 operands), 4 gemm_tn_dma_kernel; 0 = none yet.
+static thread_local int32_t g_tn_kernel = 0, g_tn_splits = 0, g_tn_rows_per = 0;
+extern "C" int32_t ispk_gemm_tn_last_plan(int32_t* splits, int32_t* rows_per_split) {
+    if (splits) *splits = g_tn_splits;
+    if (rows_per_split) *rows_per_split = g_tn_rows_per;
+    return g_tn_kernel;
+}
+
 static int32_t gemm_tn_launch(const void* A, int64_t lda, int64_t stride_a, const void* B, int64_t ldb, int64_t stride_b, float* C,
                               int64_t ldc, int64_t stride_c, int batch, int M, int N1, int N2, const uint8_t* row_mask,
                               int accumulate, float* workspace, int64_t workspace_floats, hipStream_t s, const char* who,
@@ -1115,6 +1124,9 @@ static int32_t gemm_tn_launch(const void* A, int64_t lda, int64_t stride_a, cons
     splits = (M + rows_per - 1) / rows_per;
     ISPK_REQUIRE(splits * batch <= 65535, -4, "%s: batch %d x %lld row ranges exceed the grid limit", who, batch, (long long)splits);
     const dim3 grid3((N1 + 127) / 128, (N2 + 127) / 128, (unsigned)(splits * batch));
+    g_tn_kernel = dma ? 4 : (in16 ? 3 : (bf16_operands ? 2 : 1));
+    g_tn_splits = (int32_t)splits;
+    g_tn_rows_per = rows_per;
     if (bf16_operands) {
         constexpr size_t lds16 = 2 * 2 * kTnImg;                  // 32 KB
         const int nz = (int)(splits * batch);

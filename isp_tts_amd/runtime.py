@@ -99,6 +99,7 @@ SIGNATURES = {
     "ispk_gelu_bf16": [_P, _P, _I64, _F32, _U64, _P],
     "ispk_gelu_bwd_b16": [_P, _P, _P, _I64, _F32, _U64, _P],
     "ispk_gelu_bwd_bf16": [_P, _P, _P, _I64, _F32, _U64, _P],
+    "ispk_gemm_tn_last_plan": [_P, _P],
     "ispk_gemm_tn_batched_f32": [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32, _P, _I32, _P, _I64, _P],
     "ispk_layernorm_bwd_f32": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _I64, _I32, _F32, _P],
     "ispk_layernorm_bwd_dual_f32": [_P, _I64, _P, _I64, _P, _P, _P, _I64, _I32, _P, _P, _P, _I64, _I64, _I32, _F32, _P, _I64, _P],
@@ -205,6 +206,8 @@ def _launch(label: str, flops: float, nbytes: float, fn, *args) -> None:
         else:
             label = {2: f"gemm_bf16_wide_kernel<{(v % 1000) // 10},{v % 10}>",
                      3: f"gemm_bf16_kernel<{(v % 1000) // 10},{v % 10}>"}.get(v // 1000, label)
+    elif label.startswith("gemm_tn_b16_kernel") and lib().ispk_gemm_tn_last_plan(None, None) == 4:
+        label = "gemm_tn_dma_kernel" + label[len("gemm_tn_b16_kernel"):]      # the LDS-DMA kernel, not the register-staged one
     _profiler.records.append((label, flops, nbytes, e0, e1))
 
 
@@ -1191,6 +1194,16 @@ def zero_(t: Tensor) -> Tensor:
     return t
 
 
+def _zero_rows(out: Tensor) -> Tensor:
+    """The result of a weight-gradient product over zero rows: `out` zeroed (a strided view: copied from a zeroed scratch)."""
+    if out.numel() == 0 or out.is_contiguous():
+        return zero_(out) if out.numel() else out
+    z = zeros(tuple(out.shape[-2:]), device=out.device)
+    for o in (out,) if out.ndim == 2 else out:
+        copy2d(z, o)
+    return out
+
+
 def zeros(shape, dtype: torch.dtype = torch.float32, device=None) -> Tensor:
     return zero_(torch.empty(shape, dtype=dtype, device=device))
 
@@ -1322,10 +1335,15 @@ def gemm_tn(a: Tensor, b: Tensor, row_mask: Optional[Tensor] = None, out: Option
     if row_mask is not None:
         row_mask = row_mask.reshape(-1).contiguous()
         assert row_mask.dtype == torch.bool and row_mask.numel() == M
+    if M == 0:      # a sum over no rows (the C entry refuses M = 0 and the NULL data_ptr() of an empty tensor)
+        return out if accumulate else _zero_rows(out)
     ws = workspace(a.device, N1 * N2)
+    # one row: the leading dimensions are never stepped, and torch reports a single row's stride as its width whatever the
+    # view's real stride was (reshape), which the bf16 entry refuses for N % 8 == 4 - pass a width the ABI accepts
+    lda, ldb = (a2.stride(0), b2.stride(0)) if M > 1 else (-(-N1 // 8) * 8, -(-N2 // 8) * 8)
     fn = lib().ispk_gemm_tn_b16 if in16 else (lib().ispk_gemm_tn_bf16 if bf16 else lib().ispk_gemm_tn_f32)
     _launch(f"gemm_tn_{'b16_' if in16 else ('bf16_' if bf16 else '')}kernel<{N1}x{N2}>", 2.0 * M * N1 * N2,
-            float(a2.element_size()) * (a2.numel() + b2.numel()) + 4.0 * out.numel(), fn, a2.data_ptr(), a2.stride(0), b2.data_ptr(), b2.stride(0), out.data_ptr(), out.stride(0), M,
+            float(a2.element_size()) * (a2.numel() + b2.numel()) + 4.0 * out.numel(), fn, a2.data_ptr(), lda, b2.data_ptr(), ldb, out.data_ptr(), out.stride(0), M,
             N1, N2, _ptr(row_mask), int(accumulate), ws.data_ptr(), ws.numel(), _stream())
     return out
 
@@ -1401,6 +1419,8 @@ def gemm_tn_batched(a: Tensor, b: Tensor, out: Optional[Tensor] = None) -> Tenso
     if out is None:
         out = torch.empty((batch, N1, N2), dtype=torch.float32, device=a.device)
     assert out.shape == (batch, N1, N2) and out.stride(2) == 1 and out.dtype == torch.float32
+    if batch == 0 or M == 0:
+        return out if batch == 0 else _zero_rows(out)
     ws = workspace(a.device, batch * N1 * N2)
     _launch("gemm_tn_kernel<batched>", 2.0 * batch * M * N1 * N2, 4.0 * (a.numel() + b.numel() + out.numel()),
             lib().ispk_gemm_tn_batched_f32, a.data_ptr(), a.stride(1), a.stride(0), b.data_ptr(), b.stride(1), b.stride(0),
@@ -1698,6 +1718,8 @@ def colsum(x: Tensor, row_mask: Optional[Tensor] = None) -> Tensor:
         row_mask = row_mask.reshape(-1).contiguous()
         assert row_mask.dtype == torch.bool and row_mask.numel() == rows
     out = torch.empty((cols,), dtype=torch.float32, device=x.device)
+    if rows == 0:
+        return zero_(out)
     ws = workspace(x.device, 256 * cols)
     _launch("colsum_kernels", 0.0, 4.0 * x2.numel(), lib().ispk_colsum_f32, x2.data_ptr(), x2.stride(0), rows, cols,
             _ptr(row_mask), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream())
@@ -1712,6 +1734,8 @@ def smallk_wgrad(g: Tensor, x: Tensor) -> Tensor:
     rows, N = g2.shape
     K = x2.shape[1]
     out = torch.empty((N, K), dtype=torch.float32, device=g.device)
+    if rows == 0:
+        return zero_(out)
     ws = workspace(g.device, 256 * N * K)
     _launch("smallk_wgrad_kernels", 2.0 * rows * N * K, 4.0 * (g2.numel() + x2.numel()), lib().ispk_smallk_wgrad_f32, g2.data_ptr(),
             g2.stride(0), x2.data_ptr(), x2.stride(0), rows, N, K, ws.data_ptr(), ws.numel(), out.data_ptr(), _stream())

@@ -1155,7 +1155,10 @@ def test_training_step_against_the_reference_fixture(state_dict):
 @pytest.mark.parametrize("M,N1,N2,masked", [(1000, 80, 384, False), (4099, 384, 1536, True), (64, 512, 384, True)])
 def test_gemm_tn_with_operands_stored_in_bf16(M, N1, N2, masked):
     """`ispk_gemm_tn_b16` (the AMP step's weight gradient over activations kept in bf16): bit-equal to `ispk_gemm_tn_bf16` on
-    the fp32 images of the same bf16 values - same products, same summation order - and within bf16 grade of float64."""
+    the fp32 images of the same bf16 values - same products, same summation order - and within bf16 grade of float64.  The
+    bit-equality holds at these three shapes because both planners choose the same range count there (16 ranges at
+    1000 x 80 x 384, where the unmasked bf16 operands go to the LDS-DMA kernel; the masked shapes run the register kernel on
+    both entries); elsewhere the DMA planner's target of 512 workgroups and the register kernels' 1024 give different ranges."""
     a = _rand((M, N1), 301).to(torch.bfloat16)
     b = _rand((M, N2), 302).to(torch.bfloat16)
     mask = (torch.arange(M) % 5 != 2) if masked else None
