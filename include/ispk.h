@@ -299,6 +299,8 @@ int32_t ispk_linear_small_f32(const float* a, int64_t lda, const float* w, int64
  *   slopes [H] fp32 = exp(learned_logslopes) (embeddings.py:81-82);  key_len [B] int64 or NULL (= N)
  *   1 <= H <= 8.  Rows i >= key_len[b] are computed like the reference (finite values; zeroed later by the
  *   caller's row mask, attention.py:172).
+ *   Every attention entry (these, the split and both training pairs) clamps key_len[b] to [1, N]: 0 (an empty utterance)
+ *   attends to key 0 alone, values above N mean N.  key_len values must fit in int32.
  */
 int32_t ispk_alibi_mqa_attn_f32(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                                 const float* slopes, const int64_t* key_len, float* out, int64_t ldo, int32_t B,
@@ -482,7 +484,10 @@ int32_t ispk_length_regulate_split_f16(const float* alignment, const float* dur_
  *                              [B][N][H*64] at ld_o, slopes [H] = exp(learned_logslopes), key_len int64 [B] or NULL.
  *                              dQ per head; dK, dV summed over the H heads that share them; dlogslopes[h] = slope_h *
  *                              sum_ij dS_ij (-|i - j|) (or NULL).  The softmax statistics are recomputed (no state is
- *                              kept from the forward).  workspace >= 2*B*H*N + H*B*ceil(N/32) floats.
+ *                              kept from the forward).  workspace >= 2*B*H*N + H*B*ceil(N/32) floats.  Every query row is
+ *                              differentiated, rows i >= key_len[b] included: d_o there flows into dQ, dK, dV and d log-slope
+ *                              like any other row's (training zeroes it first, as the forward's row mask does).  Both
+ *                              backwards (this and _bwd_bf16) take o as given for delta_i = sum_d o_id dO_id.
  * ispk_mel_loss_f32            models/acoustic/loss.py:22-35 (MelLoss, weight folded into grad_out by the caller):
  *                              ratio[b] = sum over (c, t < mel_len[b]) of (out - target)^2 / max(C * len_b, 1e-5)
  *                              (utils/functions.py:44-58), loss[0] = mean_b ratio[b]; grad (or NULL) = d loss / d mel_out *

@@ -28,7 +28,9 @@ constexpr int kTileKeys = 64;
 __device__ __forceinline__ float xhalf_max(float v) { return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
 
-template <int MAXT>  // 768 (H <= 6: 3 waves per SIMD, 168 VGPRs) or 1024 (H = 7, 8)
+// MAXT 768 (H = 4..6: 3 waves per SIMD, 168 VGPRs) or 1024 (H = 7, 8); STAGE float4 staging registers per thread: a 64-key
+// K/V tile is 2048 float4, so STAGE * 2 H 64 >= 2048 - 4 covers H >= 4, and H <= 3 (128 .. 384 threads) takes <384, 16>.
+template <int MAXT, int STAGE = 4>
 __global__ __launch_bounds__(MAXT) void attn_f32_kernel(const float* __restrict__ q, int64_t ldq,
                                                         const float* __restrict__ k, const float* __restrict__ v,
                                                         int64_t ldkv, const float* __restrict__ slopes,
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(MAXT) void attn_f32_kernel(const float* __restrict_
     // K/V tile staging is split (guide T14): the global loads of tile t+1 are ISSUED before tile t is computed and their
     // LDS writes happen after it, so a tile's HBM/L2 latency hides under the previous tile's MFMAs instead of stalling
     // every wave at the top of each tile.  2048 float4 per tile over <= 1024 threads: 3 (at 768 threads) per thread.
-    constexpr int kStageMax = 4;  // ceil(2048 / 512): enough down to 8 waves (H = 4)
+    constexpr int kStageMax = STAGE;
     f32x4 sreg[kStageMax];
     auto stage_load = [&](int t) {
 #pragma unroll
@@ -196,7 +198,11 @@ extern "C" int32_t ispk_alibi_mqa_attn_f32(const float* q, int64_t ldq, const fl
     constexpr size_t lds = (size_t)4 * kTileKeys * kLdk * sizeof(float);  // 69,632 B
     static_assert(lds <= 160 * 1024, "LDS budget");
     dim3 grid((N + 63) / 64, B), block(2 * H * 64);
-    if (H <= 6) {
+    if (H <= 3) {   // (with 4 staging registers per thread, 2 H waves would leave part of every K/V tile unwritten)
+        ISPK_RESERVE_LDS((&attn_f32_kernel<384, 16>), lds, "attn");
+        hipLaunchKernelGGL((attn_f32_kernel<384, 16>), grid, block, lds, reinterpret_cast<hipStream_t>(stream), q, ldq, k, v,
+                           ldkv, slopes, key_len, out, ldo, N, H);
+    } else if (H <= 6) {
         ISPK_RESERVE_LDS(&attn_f32_kernel<768>, lds, "attn");
         hipLaunchKernelGGL(attn_f32_kernel<768>, grid, block, lds, reinterpret_cast<hipStream_t>(stream), q, ldq, k, v,
                            ldkv, slopes, key_len, out, ldo, N, H);

@@ -824,7 +824,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dq_kernel(const float* __restrict
     seed = run_seed(seed, seed_src);
     const int tile = blockIdx.x, h = blockIdx.y, b = blockIdx.z, l = threadIdx.x, c = l & 31, hf = l >> 5;
     const int ntiles = gridDim.x;
-    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)0, key_len[b])) : N;
+    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)1, key_len[b])) : N;   // [1, N], as every attention entry
     const int i = tile * 32 + c;
     const float* qb = qkv + (int64_t)b * N * ld;
     const float* kb = qb + H * 64;
@@ -922,7 +922,7 @@ __global__ __launch_bounds__(64) void attn_train_fwd_kernel(const float* __restr
         const uint64_t* __restrict__ seed_src) {
     seed = run_seed(seed, seed_src);
     const int tile = blockIdx.x, h = blockIdx.y, b = blockIdx.z, l = threadIdx.x, c = l & 31, hf = l >> 5;
-    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)0, key_len[b])) : N;
+    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)1, key_len[b])) : N;   // [1, N], as every attention entry
     const int i = tile * 32 + c;
     const float* qb = qkv + (int64_t)b * N * ld;
     const float* kb = qb + H * 64;
@@ -996,7 +996,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const float* __restri
     seed = run_seed(seed, seed_src);
     __shared__ float red[2][2][16][64];     // [dk | dv][M tile][register][lane]
     const int kt = blockIdx.x, b = blockIdx.y, h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63, c = l & 31, hf = l >> 5;
-    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)0, key_len[b])) : N;
+    const int klen = key_len ? (int)min((int64_t)N, max((int64_t)1, key_len[b])) : N;   // [1, N], as every attention entry
     const int j = kt * 32 + c;
     const float* qb = qkv + (int64_t)b * N * ld;
     const float* kb = qb + H * 64;
@@ -1376,7 +1376,7 @@ extern "C" int32_t ispk_alibi_mqa_attn_bwd_f32(const float* qkv, int64_t ld_qkv,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     ISPK_REQUIRE(qkv && o && d_o && slopes && dqkv && workspace, -1, "%s: null pointer", who);
     ISPK_REQUIRE(B >= 1 && N >= 1 && H >= 1 && H <= 8 && ld_qkv >= H * 64 + 128 && ld_o >= H * 64 && ld_qkv % 4 == 0 &&
-                     ld_o % 4 == 0, -2, "%s: bad shape B=%d N=%d H=%d", who, B, N, H);
+                     ld_o % 4 == 0 && B <= 65535, -2, "%s: bad shape B=%d N=%d H=%d", who, B, N, H);
     ISPK_REQUIRE(ispk_aligned(qkv, 16) && ispk_aligned(o, 16) && ispk_aligned(d_o, 16) && ispk_aligned(dqkv, 16), -3,
                  "%s: arrays must be 16-byte aligned", who);
     const int tiles = (N + 31) / 32;

@@ -662,11 +662,16 @@ def alibi_mqa_attention_raw(q: Tensor, ldq: int, k: Tensor, v: Tensor, ldkv: int
     q.data_ptr(); k / v likewise [B][N][64] at stride ldkv.  Returns the merged heads [B, N, H*64]."""
     _dev(q, k, v, slopes, key_len)
     out = torch.empty((B, N, heads * 64), dtype=q.dtype, device=q.device)
+    if B == 0:      # nothing to compute; the C entries would refuse the NULL data_ptr() torch gives an empty tensor
+        return out
     if key_len is not None:
         key_len = key_len.to(torch.int64).contiguous()
     slopes = slopes.to(torch.float32).contiguous()
     es = q.element_size()
-    label = ("attn_f32_kernel" if es == 4 else "attn_bf16_kernel") + ("<768>" if heads <= 6 else "<1024>")
+    if es == 4:
+        label = "attn_f32_kernel" + ("<384,16>" if heads <= 3 else "<768>" if heads <= 6 else "<1024>")
+    else:
+        label = "attn_bf16_kernel" + ("<768>" if heads <= 6 else "<1024>")
     flops, nbytes = 256.0 * B * N * N * heads, float(B) * N * (2 * heads * 64 + 128) * es
     if q_tiles:   # explicit query tiles per workgroup (bf16 kernel only; 0 = the launcher's own choice)
         assert es == 2
@@ -813,6 +818,8 @@ def alibi_mqa_attention_split(qkv: Tensor, heads: int, slopes: Tensor, key_len: 
     else:
         out = torch.empty((B, N, heads * 64), dtype=torch.float32, device=qkv.device)
         plane = 0
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see alibi_mqa_attention_raw)
+        return out
     es = qkv.element_size()
     _launch("attn_split_f16_kernel", 256.0 * B * N * N * heads, float(B) * N * (2 * heads * 64 + 128) * 4,
             lib().ispk_alibi_mqa_attn_split_f16, qkv.data_ptr(), W, qkv.data_ptr() + heads * 64 * es,
@@ -1545,6 +1552,8 @@ def alibi_mqa_attention_train(qkv: Tensor, heads: int, slopes: Tensor, key_len: 
         key_len = key_len.to(torch.int64).contiguous()
     o = torch.empty((B, N, heads * 64), dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see alibi_mqa_attention_raw)
+        return o, lse
     _launch("attn_train_fwd_bf16_kernel" if b16 else "attn_train_fwd_kernel", 4.0 * B * heads * N * N * 64,
             float(qkv.element_size()) * (qkv.numel() + o.numel()),
             lib().ispk_alibi_mqa_attn_train_bf16 if b16 else lib().ispk_alibi_mqa_attn_train_f32, qkv.data_ptr(), W, slopes.data_ptr(),
@@ -1583,6 +1592,8 @@ def alibi_mqa_attention_bwd(qkv: Tensor, o: Tensor, d_o: Tensor, heads: int, slo
         key_len = key_len.to(torch.int64).contiguous()
     dqkv = torch.empty_like(qkv)
     dls = torch.empty((heads,), dtype=torch.float32, device=qkv.device)
+    if B == 0:      # no rows, no gradient (NULL data_ptr() of an empty tensor: see alibi_mqa_attention_raw)
+        return dqkv, dls.zero_()
     if b16:
         assert lse is not None and lse.dtype == torch.float32 and lse.shape == (B, heads, N) and lse.is_contiguous()
         ws = workspace(qkv.device, B * heads * N + 2 * heads * B * ((N + 63) // 64))
