@@ -606,6 +606,33 @@ int32_t ispk_alibi_mqa_attn_bwd_bf16(const uint16_t* qkv, int64_t ld_qkv, const 
                                      int32_t H, float dropout_p, uint64_t seed, ispk_stream_t stream);
 int32_t ispk_mel_loss_f32(const float* mel_out, const float* mel_target, const int64_t* mel_len, float* ratio, float* loss,
                           float* grad, float grad_out, int32_t B, int32_t C, int32_t T, ispk_stream_t stream);
+/* ispk_acoustic_metrics_f32    models/acoustic/evaluator.py:14-67 (MCD, AlignmentMetric; AcousticModelEvaluator.__call__ makes
+ *                              all three in one call): out[0] = mcd_{n_mfcc}, out[1] = alignment_length, out[2] =
+ *                              alignment_strength, each what the reference's 0-dim result holds.
+ *   mel_out, mel_target        fp32 element (b, c, t) at b*sb + c*sc + t*st, c < C channels, t < T frames: [B][C][T] and
+ *                              [B][T][C] are a swap of the two strides (the reference's `_mfcc` picks the layout by size(-1)
+ *                              == n_mel_channels; the caller resolves it).  Vector loads when the unit-stride axis is the
+ *                              frame or (C % 4 == 0) the channel axis, the other strides are multiples of 4 and both bases
+ *                              are 16-byte aligned; element loads otherwise.  Both NULL: out[0] is not computed or written.
+ *   dct                        [C][n_mfcc] fp32, the DCT-II basis of torchaudio's create_dct(n_mfcc, C, "ortho").
+ *                              out[0] = 10 sqrt(2) / ln 10 * mean_b (sum over ALL t < T of |((x - y)[:, t] . D)[1:n_mfcc]|)
+ *                              / mel_len[b]  (padded frames included, coefficient 0 dropped, as evaluator.py:25-38).
+ *   attn_soft                  fp32 [B][T][L] at (attn_sb, attn_st, 1), or NULL (out[1], out[2] not computed or written).
+ *                              a[b][t] = argmax_l (first index on ties, NaN largest: torch's argmax);
+ *                              out[1] = mean_b (sum_{t=1}^{mel_len-1} sqrt(1 + (a[t] - a[t-1])^2)) / sqrt(text_len^2 + mel_len^2)
+ *                              out[2] = (sum over all B*T frames of max_l attn_soft) / sum_b mel_len[b].
+ *   mel_len, text_len          int64 [B] (text_len may be NULL without attn_soft).  1 <= mel_len[b] <= T is required; the
+ *                              lengths are device data, so a violation cannot be refused by the return code: it makes every
+ *                              written output NaN.
+ *   workspace                  >= 3 * B * ceil(T / 32) floats (per-(item, 32-frame chunk) partial sums).
+ * Refused (out untouched): a NULL required pointer, B < 1 or B > 65535, T < 1, L < 1 with attn_soft, and with the mels
+ * C < 1, C > 128, n_mfcc < 1 or n_mfcc > C; a short workspace (-3).  Two launches, every sum in a fixed order and no
+ * floating-point atomics: repeated calls and graph replays are bit-identical. */
+int32_t ispk_acoustic_metrics_f32(const float* mel_out, int64_t out_sb, int64_t out_sc, int64_t out_st, const float* mel_target,
+                                  int64_t tgt_sb, int64_t tgt_sc, int64_t tgt_st, const int64_t* mel_len, const int64_t* text_len,
+                                  const float* attn_soft, int64_t attn_sb, int64_t attn_st, const float* dct, float* workspace,
+                                  int64_t workspace_floats, float* out, int32_t B, int32_t C, int32_t T, int32_t L,
+                                  int32_t n_mfcc, ispk_stream_t stream);
 int32_t ispk_aligner_scores_bwd_f32(const float* attn_logits, const float* attn_soft, const float* d_soft, const float* d_logits,
                                     const int64_t* text_len, const int64_t* mel_len, float* dS, int64_t ld_s, float* dSt,
                                     int64_t ld_t, int32_t B, int32_t M, int32_t L, float scale, ispk_stream_t stream);

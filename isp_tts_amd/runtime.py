@@ -111,6 +111,8 @@ SIGNATURES = {
     "ispk_alibi_mqa_attn_train_bf16": [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _F32, _U64, _P],
     "ispk_alibi_mqa_attn_bwd_bf16": [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _U64, _P],
     "ispk_mel_loss_f32": [_P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _P],
+    "ispk_acoustic_metrics_f32": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I32,
+                                  _I32, _I32, _I32, _I32, _P],
     "ispk_aligner_scores_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_masked_instnorm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_soft_average_bwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P],
@@ -1625,6 +1627,65 @@ def mel_loss(mel_out: Tensor, mel_target: Tensor, mel_len: Tensor, want_grad: bo
             mel_target.data_ptr(), mel_len.data_ptr(), ratio.data_ptr(), loss.data_ptr(), _ptr(grad), grad_out, B, C, T,
             _stream())
     return loss, grad
+
+
+METRICS_CHUNK = 32     # frames per workgroup of ispk_acoustic_metrics_f32 (its workspace: 3 partials per item and chunk)
+
+
+def metrics_workspace_floats(B: int, T: int) -> int:
+    return 3 * B * ((T + METRICS_CHUNK - 1) // METRICS_CHUNK)
+
+
+def _mel_strides(x: Tensor, C: int):
+    """(C', T, sb, sc, st) of a mel as MCD._mfcc (evaluator.py:28-31) reads it: [B, T, C] when size(-1) == C, else
+    [B, C, T] (so a [B, C, C] mel is read frames-first: the axes are swapped)."""
+    if x.shape[-1] == C:
+        return x.shape[2], x.shape[1], x.stride(0), x.stride(2), x.stride(1)
+    return x.shape[1], x.shape[2], x.stride(0), x.stride(1), x.stride(2)
+
+
+def acoustic_metrics(mel_out: Optional[Tensor], mel_target: Optional[Tensor], mel_len: Tensor, text_len: Optional[Tensor],
+                     attn_soft: Optional[Tensor], dct: Optional[Tensor], out: Optional[Tensor] = None) -> Tensor:
+    """ispk_acoustic_metrics_f32 -> fp32 [3] on the device = (mcd, alignment_length, alignment_strength), no host read.
+    mel_out / mel_target fp32 [B, C, T] or [B, T, C] (any strides; C = dct.shape[0], the layout rule of MCD._mfcc), dct fp32
+    [C, n_mfcc] on the device, attn_soft fp32 [B, T, L] (unit stride on L), lengths int64 [B].  Either the mels (with dct)
+    or attn_soft (with text_len) may be None: that part of `out` is then not written.  B = 0 gives NaN for all three
+    without a launch, as the reference's means over an empty batch (0 / 0)."""
+    _dev(mel_out, mel_target, mel_len, text_len, attn_soft, dct, out)
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float32, device=mel_len.device)
+    assert out.dtype == torch.float32 and out.numel() == 3 and out.is_contiguous()
+    B = mel_len.shape[0]
+    if B == 0:
+        return out.fill_(float("nan"))
+    mel_len = mel_len.to(torch.int64).contiguous()
+    C = n_mfcc = T = L = 0
+    m = mt = (0,) * 5                   # (strides of an absent mel pair: not read)
+    if mel_out is not None or mel_target is not None:
+        assert mel_out is not None and mel_target is not None and dct is not None
+        assert mel_out.dtype == torch.float32 and mel_target.dtype == torch.float32 and dct.dtype == torch.float32
+        assert mel_out.ndim == 3 and mel_target.ndim == 3 and dct.ndim == 2 and dct.is_contiguous()
+        C, n_mfcc = dct.shape
+        m, mt = _mel_strides(mel_out, C), _mel_strides(mel_target, C)
+        if m[0] != C or mt[0] != C or m[1] != mt[1] or mel_out.shape[0] != B or mel_target.shape[0] != B:
+            raise ValueError(f"mels {tuple(mel_out.shape)} / {tuple(mel_target.shape)} do not match {C} channels and {B} lengths")
+        T = m[1]
+    if attn_soft is not None:
+        assert attn_soft.dtype == torch.float32 and attn_soft.ndim == 3 and text_len is not None
+        if attn_soft.stride(2) != 1:
+            attn_soft = attn_soft.contiguous()
+        if attn_soft.shape[0] != B or (T and attn_soft.shape[1] != T):
+            raise ValueError(f"attention {tuple(attn_soft.shape)} does not match {B} items of {T} frames")
+        T, L = attn_soft.shape[1], attn_soft.shape[2]
+        text_len = text_len.to(torch.int64).contiguous()
+    ws = torch.empty((metrics_workspace_floats(B, T),), dtype=torch.float32, device=mel_len.device)
+    nbytes = 4.0 * (2 * B * C * T + (attn_soft.numel() if attn_soft is not None else 0))
+    _launch("acoustic_metrics_kernels", 2.0 * B * T * C * n_mfcc, nbytes, lib().ispk_acoustic_metrics_f32,
+            _ptr(mel_out), m[2], m[3], m[4], _ptr(mel_target), mt[2], mt[3], mt[4], mel_len.data_ptr(),
+            _ptr(text_len) if attn_soft is not None else None, _ptr(attn_soft),
+            attn_soft.stride(0) if attn_soft is not None else 0, attn_soft.stride(1) if attn_soft is not None else 0,
+            _ptr(dct), ws.data_ptr(), ws.numel(), out.data_ptr(), B, C, T, L, n_mfcc, _stream())
+    return out
 
 
 def flow_loss_bwd(pred_raw: Tensor, flow: Tensor, mask: Tensor, grad_out: float = 1.0) -> Tensor:

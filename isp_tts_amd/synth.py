@@ -204,3 +204,36 @@ def make_mas_logits(batch: int, mel_max: int, text_max: int, variable: bool = Fa
         d = ti - mi
         x = z + torch.clamp(-(d * d) * 50.0, min=-13.815511)
     return x.contiguous(), text_len, mel_len
+
+
+# (B, T, L, mel layout, mel_len, text_len, attention kind) of the evaluator fixture's synthetic cases (tests/golden/metrics.npz)
+METRIC_CASES = {
+    "ragged": (5, 77, 23, "bct", [77, 1, 40, 76, 33], [23, 1, 9, 1, 12], "soft"),
+    "ties": (3, 70, 9, "bct", [70, 64, 33], [9, 5, 7], "ties"),
+    "t80": (2, 80, 17, "btc", [80, 41], [17, 6], "soft"),        # [B, 80, 80]: the reference reads it frames-first
+    "btc": (3, 100, 31, "btc", [100, 57, 2], [31, 20, 2], "soft"),
+}
+
+
+def make_metric_inputs(case: str, seed: int = SEED) -> dict[str, torch.Tensor]:
+    """Inputs of one evaluator case (models/acoustic/evaluator.py), from IEEE-exact operations on a keyed stream:
+    mel_out / mel_target fp32 [B, 80, T] ("bct") or [B, T, 80] ("btc"); the target is zero past mel_len (the collator's
+    padding), the prediction is not (MCD counts every frame).  attn_soft fp32 [B, T, L]: normalised squares of uniform draws
+    ("soft") or small multiples of 1/4 with many exact row ties ("ties"), non-zero on padded frames too (the strength sums
+    every frame).  max(mel_len) == T, as the reference's boolean mask requires."""
+    B, T, L, layout, mel_len, text_len, kind = METRIC_CASES[case]
+    g = _rng(f"metrics/{case}", seed)
+    target = g.standard_normal((B, 80, T)) * 2.0 - 5.0
+    out = target + g.standard_normal((B, 80, T)) * 0.5
+    target = target * (np.arange(T)[None, None, :] < np.asarray(mel_len)[:, None, None])
+    if kind == "ties":
+        attn = g.integers(0, 4, size=(B, T, L)) * 0.25
+    else:
+        r = g.random((B, T, L))
+        attn = r * r
+        attn = attn / attn.sum(axis=-1, keepdims=True)
+    if layout == "btc":
+        out, target = out.transpose(0, 2, 1), target.transpose(0, 2, 1)
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.float32))   # noqa: E731
+    return {"mel_out": f32(out), "mel_target": f32(target), "attn_soft": f32(attn),
+            "mel_len": torch.tensor(mel_len, dtype=torch.int64), "text_len": torch.tensor(text_len, dtype=torch.int64)}

@@ -17,21 +17,29 @@ import torch
 from torch import Tensor
 
 from .. import runtime
-from .model import acoustic_train_forward
+from .model import acoustic_train_forward, acoustic_train_losses, acoustic_train_outputs
 from .optim import FlatAdamW
 
 
 class GraphedTrainStep:
     """step = GraphedTrainStep(model, opt, batch); total, losses, norm = step(**next_batch).
     `batch`: text, text_len, mel, mel_len, pitch, energy (+ flow_x0, flow_t) on the device, at the shapes every later batch has.
-    The `warmup` steps before the capture are REAL steps on `batch`.  Single rank, no gradient accumulation."""
+    The `warmup` steps before the capture are REAL steps on `batch`.  Single rank, no gradient accumulation.
+    `evaluator` (e.g. acoustic.AcousticModelEvaluator, the reference's `metrics = self.evaluator(inputs, outputs)` of
+    experiments/trainer.py:557-559): the captured step also runs it on the step's forward outputs, before the backward;
+    after each replay `step.metrics` holds its dict and `step.outputs` the (detached) AcousticModelOutput it saw.  It must
+    issue device work only (the acoustic evaluator is one libispk launch pair)."""
 
     KEYS = ("text", "text_len", "mel", "mel_len", "pitch", "energy")
 
-    def __init__(self, model, opt: FlatAdamW, batch: dict, amp: bool = True, train_aligner: bool = True, warmup: int = 2):
+    def __init__(self, model, opt: FlatAdamW, batch: dict, amp: bool = True, train_aligner: bool = True, warmup: int = 2,
+                 evaluator=None):
         assert opt.world == 1 and opt.grad_accum_steps == 1, "one rank, no accumulation"
         self.model, self.opt, self.amp, self.train_aligner = model, opt, amp, train_aligner
+        self.evaluator, self.metrics, self.outputs = evaluator, None, None
         dev = batch["text"].device
+        if evaluator is not None and hasattr(evaluator, "mcd_evaluator"):
+            evaluator.mcd_evaluator.dct(dev)                # (its DCT basis reaches the device before, not inside, the capture)
         self.static = {k: batch[k].clone() for k in self.KEYS}
         b, l = batch["text"].shape
         self.static["flow_x0"] = batch["flow_x0"].clone() if "flow_x0" in batch else torch.randn(b, l, 3, device=dev)
@@ -76,7 +84,7 @@ class GraphedTrainStep:
     def close(self) -> None:
         """Forget the graph and what the module-global caches still hold of its private pool (weight images staged during the
         capture, the capture stream's workspace), so that the pool's memory can be returned."""
-        self.graph, self.out = None, None
+        self.graph, self.out, self.metrics, self.outputs = None, None, None, None
         for m in self.model.modules():
             m.__dict__.pop("_train_images", None)
         if getattr(self, "_capture_stream_key", None) is not None:
@@ -93,9 +101,18 @@ class GraphedTrainStep:
 
     def _body(self):
         s = self.static
-        _, total, losses = acoustic_train_forward(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"], s["energy"],
-                                                  flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
-                                                  train_aligner=self.train_aligner)
+        if self.evaluator is None:
+            _, total, losses = acoustic_train_forward(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"],
+                                                      s["energy"], flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
+                                                      train_aligner=self.train_aligner)
+        else:
+            out = acoustic_train_outputs(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"], s["energy"],
+                                         flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
+                                         train_aligner=self.train_aligner)
+            total, losses = acoustic_train_losses(out, s["text_len"], s["mel"], s["mel_len"], self.train_aligner)
+            self.outputs = _detached(out)
+            with torch.no_grad():
+                self.metrics = self.evaluator({k: s[k] for k in self.KEYS}, self.outputs)
         # (the finiteness check of an eager step is a host read of the norm; the AdamW factors come from the device record)
         norm = self.opt.step(total, args_dev=self.args_dev, check_finite=False)
         return total, losses, norm
@@ -121,3 +138,14 @@ class GraphedTrainStep:
         self.opt.step_count += 1
         self.opt.flat.mark_updated()        # eager users of the modules re-stage their weight images from the updated arena
         return self.out
+
+
+def _detached(x):
+    """The same nest of NamedTuples / dicts / tensors with every tensor detached (views: no copy)."""
+    if isinstance(x, Tensor):
+        return x.detach()
+    if isinstance(x, dict):
+        return {k: _detached(v) for k, v in x.items()}
+    if isinstance(x, tuple) and hasattr(x, "_fields"):
+        return type(x)(*(_detached(v) for v in x))
+    return x

@@ -84,6 +84,12 @@ def acoustic_train_forward(model, text: Tensor, text_len: Tensor, mel: Tensor, m
     reference's total (loss.py:140-182); otherwise the aligner is frozen, loss = mel + flow and the two attention terms are
     values."""
     out = acoustic_train_outputs(model, text, text_len, mel, mel_len, pitch, energy, flow_noise, flow_time, amp, train_aligner)
+    total, losses = acoustic_train_losses(out, text_len, mel, mel_len, train_aligner)
+    return out.mel, total, losses
+
+
+def acoustic_train_losses(out, text_len: Tensor, mel: Tensor, mel_len: Tensor, train_aligner: bool = True):
+    """-> (loss, losses) of the outputs of `acoustic_train_outputs` (the second half of `acoustic_train_forward`)."""
     al = out.aligner_output
     mel_loss = MelLoss()(out.mel, mel, mel_len)
     flow_loss = out.adaptor_output.losses["flow_loss"]
@@ -92,4 +98,4 @@ def acoustic_train_forward(model, text: Tensor, text_len: Tensor, mel: Tensor, m
         kl = AttentionBinarizationLoss()(al.attn_soft, al.attn_hard)
     losses = {"model/mel_loss": mel_loss, "adaptor/flow_loss": flow_loss, "aligner/attention_loss": ctc, "aligner/kl_loss": kl}
     total = sum_losses([mel_loss, flow_loss, ctc, kl] if train_aligner else [mel_loss, flow_loss])
-    return out.mel, total, losses
+    return total, losses
