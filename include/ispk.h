@@ -633,6 +633,40 @@ int32_t ispk_acoustic_metrics_f32(const float* mel_out, int64_t out_sb, int64_t 
                                   const float* attn_soft, int64_t attn_sb, int64_t attn_st, const float* dct, float* workspace,
                                   int64_t workspace_floats, float* out, int32_t B, int32_t C, int32_t T, int32_t L,
                                   int32_t n_mfcc, ispk_stream_t stream);
+/* ispk_audio_features_f32      data/providers.py:35-64 (SpectrogramProvider), :70-111 (MelScaleProvider with
+ *                              functions.py:19-20), :178-188 (EnergyProvider), :280-348 (PitchProvider, torch-yin, with
+ *                              data/pitch.py:17-100), the pitch pad of data/dataset.py:152 and the collator's zero padding
+ *                              (data/collator.py:27-95), for n_fft = win_length = 1024, hop 256, pad 384, center=False, power 1.
+ *   audio, ld_audio            fp32 [B][S] at row stride ld_audio >= S; utterance b is audio[b][0, audio_len[b]): nothing at or
+ *                              past audio_len[b] is read (the reference pads with zeros).  float4 loads when ld_audio % 4 == 0
+ *                              and the base is 16-byte aligned.
+ *   audio_len                  int64 [B] on the device.  mel_len[b] = (audio_len + 768 - 1024) / 256 + 1.  A length below 256
+ *                              (where torch.stft raises) or above S gives mel_len 0 and all-zero rows: lengths are device data,
+ *                              so they cannot be refused by the return code.
+ *   tables                     fp32: [0, 4096) W_2048^m = exp(-2 pi i m / 2048) as (re, im), m < 2048, made in float64;
+ *                              [4096, 5120) the periodic Hann window; [5120, ...) the non-zero filterbank weights, filter by
+ *                              filter, each over its contiguous bin range.
+ *   table_floats               the length of `tables`, >= 5120: no weight at or past it is read, whatever fb_index says.
+ *   fb_index                   int32 [2 n_mels + 1]: first bin lo[m] of filter m, then offsets off[0..n_mels] of its weights
+ *                              in tables[5120 + ...]: mel[m] = log(max(sum_{k < off[m+1] - off[m]} |X_{lo+k}| w[off[m]+k], 1e-5)).
+ *                              off[n_mels] <= 1026.  May be NULL without mel.
+ *   mel                        fp32 [B][n_mels][M] (contiguous), 1 <= n_mels <= 128, or NULL.
+ *   mel_len                    int64 [B], or NULL.
+ *   pitch                      fp32 [B][M], or NULL: (hz - pitch_mean) / pitch_std for t < (max(len + 768, 2 tau_max) -
+ *                              2 tau_max) / 256 + 1 frames, then 0 (dataset.py:152 pads the normalised pitch with 0).  hz is
+ *                              torch-yin's: lags tau_min + 1 .. tau_max - 1 of its cumulative-mean-normalised difference
+ *                              function, its first-index search against `threshold`, and reciprocal(lag) * sample_rate.
+ *                              1 <= tau_min < tau_max - 1, 512 <= tau_max and 3 tau_max <= 2048 (the autocorrelation by a
+ *                              2048-point FFT does not wrap).
+ *   energy                     fp32 [B][M], or NULL: log1p(sqrt(sum_k |X_k|^2)).
+ *   M                          output frames, >= the frame count of S.  Every output is written in full: zero past mel_len.
+ * Refused: NULL audio, audio_len or tables (-1), fb_index with mel (-1); table_floats < 5120, B < 1, B > 65535, S < 0, ld_audio < S, M below the
+ * frame count of S, n_mels out of range, tau bounds out of range, pitch_std == 0 (-2).  No workspace: one launch, every sum
+ * in a fixed order and no atomics, so repeated calls and graph replays are bit-identical. */
+int32_t ispk_audio_features_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables,
+                                int64_t table_floats, const int32_t* fb_index, int32_t n_mels, float* mel, int64_t* mel_len, float* pitch, float* energy,
+                                int32_t B, int32_t S, int32_t M, int32_t tau_min, int32_t tau_max, float sample_rate,
+                                float threshold, float pitch_mean, float pitch_std, ispk_stream_t stream);
 int32_t ispk_aligner_scores_bwd_f32(const float* attn_logits, const float* attn_soft, const float* d_soft, const float* d_logits,
                                     const int64_t* text_len, const int64_t* mel_len, float* dS, int64_t ld_s, float* dSt,
                                     int64_t ld_t, int32_t B, int32_t M, int32_t L, float scale, ispk_stream_t stream);

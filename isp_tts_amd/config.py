@@ -62,3 +62,20 @@ class AcousticDims:
                         "normalization": "instance", "activation": "gelu"},
             "num_speakers": None,
         }
+
+
+# recipes/acoustic/core.yaml `dataset`: the keys data.AcousticFeatures.from_config reads, `${...}` references as the recipe
+# writes them (tests build the extractor from it)
+ACOUSTIC_DATASET = {
+    "stats": {"pitch": {"mean": 166.6177, "std": 62.5423}},
+    "pitch_from_disk": False,
+    "audio": {"sample_rate": 22050},
+    "spec": {"n_fft": 1024, "hop_length": 256, "win_length": 1024, "pad": None, "power": 1.0, "normalized": False,
+             "center": False},
+    "mel_scale": {"sample_rate": "${dataset.audio.sample_rate}", "n_fft": "${dataset.spec.n_fft}", "n_mels": 80, "f_min": 0.0,
+                  "f_max": 8000.0, "norm": "slaney", "mel_scale": "slaney"},
+    "pitch": {"_disable_": False, "sample_rate": "${dataset.audio.sample_rate}", "hop_length": "${dataset.spec.hop_length}",
+              "win_length": "${dataset.spec.win_length}", "f_min": 40, "f_max": 800, "method": "torch-yin", "threshold": 0.15,
+              "norm": "standard", "device": None},
+    "energy": {"_disable_": False},
+}

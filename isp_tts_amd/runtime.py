@@ -113,6 +113,8 @@ SIGNATURES = {
     "ispk_mel_loss_f32": [_P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _P],
     "ispk_acoustic_metrics_f32": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I32,
                                   _I32, _I32, _I32, _I32, _P],
+    "ispk_audio_features_f32": [_P, _I64, _P, _P, _I64, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F32, _F32, _F32,
+                                _F32, _P],
     "ispk_aligner_scores_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_masked_instnorm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_soft_average_bwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P],
@@ -1686,6 +1688,53 @@ def acoustic_metrics(mel_out: Optional[Tensor], mel_target: Optional[Tensor], me
             attn_soft.stride(0) if attn_soft is not None else 0, attn_soft.stride(1) if attn_soft is not None else 0,
             _ptr(dct), ws.data_ptr(), ws.numel(), out.data_ptr(), B, C, T, L, n_mfcc, _stream())
     return out
+
+
+FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
+FEATURE_TABLE_HEAD = 5120  # tables[0, 5120): W_2048^m as (re, im), then the Hann window; the filterbank weights follow
+
+
+def feature_frames(samples: int) -> int:
+    """Frames of an utterance of `samples` samples: (S + 768 - 1024) // 256 + 1, 0 below 256 samples (where torch.stft raises)."""
+    return (samples - FEATURE_HOP) // FEATURE_HOP + 1 if samples >= FEATURE_HOP else 0
+
+
+def audio_features(audio: Tensor, audio_len: Tensor, tables: Tensor, fb_index: Optional[Tensor], mel: Optional[Tensor],
+                   mel_len: Optional[Tensor], pitch: Optional[Tensor], energy: Optional[Tensor], tau_min: int = 1,
+                   tau_max: int = 512, sample_rate: float = 0.0, threshold: float = 0.0, pitch_mean: float = 0.0,
+                   pitch_std: float = 1.0) -> None:
+    """ispk_audio_features_f32, one launch, no host read: fills the given outputs (each may be None) of the fp32 waveforms
+    audio [B, S] (unit stride on S, any row stride) with int64 lengths audio_len [B].  mel fp32 [B, n_mels, M], pitch / energy
+    fp32 [B, M], mel_len int64 [B], all contiguous; tables fp32 and fb_index int32 as include/ispk.h lays them out
+    (data.AcousticFeatures builds them).  The kernel reads no filterbank weight past tables.numel(), whatever fb_index
+    (device data, not read here) says."""
+    _dev(audio, audio_len, tables, fb_index, mel, mel_len, pitch, energy)
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and audio.stride(1) == 1, "audio: fp32 [B, S], unit stride on S"
+    assert audio_len.dtype == torch.int64 and audio_len.ndim == 1 and audio_len.is_contiguous()
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= FEATURE_TABLE_HEAD
+    B, S = audio.shape
+    if audio_len.shape[0] != B:
+        raise ValueError(f"{audio_len.shape[0]} lengths for {B} waveforms")
+    M, n_mels = None, 0
+    for name, t, dt, nd in (("mel", mel, torch.float32, 3), ("pitch", pitch, torch.float32, 2),
+                            ("energy", energy, torch.float32, 2), ("mel_len", mel_len, torch.int64, 1)):
+        if t is None:
+            continue
+        if t.dtype != dt or t.ndim != nd or not t.is_contiguous() or t.shape[0] != B:
+            raise ValueError(f"{name}: need a contiguous {dt} tensor of {nd} dims and {B} rows, got {t.dtype} {tuple(t.shape)}")
+        if nd > 1:
+            if M is not None and t.shape[-1] != M:
+                raise ValueError(f"{name}: {t.shape[-1]} frames, another output has {M}")
+            M = t.shape[-1]
+    if mel is not None:
+        n_mels = mel.shape[1]
+        assert fb_index is not None and fb_index.dtype == torch.int32 and fb_index.numel() == 2 * n_mels + 1
+    if B == 0:
+        return
+    _launch("features_kernel", 0.0, 4.0 * audio.numel() + 4.0 * (n_mels + 2) * B * (M or 0), lib().ispk_audio_features_f32,
+            audio.data_ptr(), audio.stride(0), audio_len.data_ptr(), tables.data_ptr(), tables.numel(), _ptr(fb_index), n_mels, _ptr(mel),
+            _ptr(mel_len), _ptr(pitch), _ptr(energy), B, S, M if M is not None else feature_frames(S), tau_min, tau_max,
+            sample_rate, threshold, pitch_mean, pitch_std, _stream())
 
 
 def flow_loss_bwd(pred_raw: Tensor, flow: Tensor, mask: Tensor, grad_out: float = 1.0) -> Tensor:

@@ -237,3 +237,49 @@ def make_metric_inputs(case: str, seed: int = SEED) -> dict[str, torch.Tensor]:
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.float32))   # noqa: E731
     return {"mel_out": f32(out), "mel_target": f32(target), "attn_soft": f32(attn),
             "mel_len": torch.tensor(mel_len, dtype=torch.int64), "text_len": torch.tensor(text_len, dtype=torch.int64)}
+
+
+# (kind, samples, peak amplitude) of the feature extractor's test clips; FEATURE_CASES name the fixture's batches
+# (tests/golden/features.npz).  Lengths cover one frame (256), the YIN pad edge (281 / 282 / 283) and the pitch-count
+# quirk (k 256 + 25 / 26 / 27).
+CLIP_KINDS = ("harmonic", "noise", "silence", "edge_hi", "edge_lo", "chirp")
+FEATURE_CASES = {
+    "edges": [("harmonic", 256, 0.5), ("noise", 257, 0.3), ("edge_hi", 281, 0.9), ("harmonic", 282, 1.0),
+              ("chirp", 283, 0.5), ("edge_lo", 2 * 256 + 25, 0.5), ("harmonic", 3 * 256 + 26, 0.2),
+              ("noise", 4 * 256 + 27, 0.5), ("harmonic", 5 * 256, 0.7)],
+    "voices": [("harmonic", 11025, 0.8), ("chirp", 12000, 0.6), ("edge_hi", 6400 + 26, 1.0), ("edge_lo", 9000, 0.9),
+               ("noise", 7000, 0.5), ("silence", 5000, 0.0), ("harmonic", 8192, 1e-4), ("chirp", 10000 + 25, 1e-2)],
+}
+
+
+def make_clip(kind: str, samples: int, amplitude: float = 0.5, seed: int = SEED, sample_rate: int = 22050) -> torch.Tensor:
+    """A deterministic fp32 test waveform from a keyed stream, peak |x| = amplitude: "harmonic" (six partials of a 90-300 Hz
+    f0 with 5.5 Hz vibrato, plus a little noise), "noise", "silence", "edge_hi" (a 700 -> 800 Hz glide up to torch-yin's upper
+    search edge) / "edge_lo" (a tone at its 42 Hz lower edge), "chirp" (a 100 -> 400 Hz sweep gated on and off every 0.1 s, noise in the gaps)."""
+    if kind not in CLIP_KINDS:
+        raise ValueError(f"unknown clip kind {kind!r}")
+    g = _rng(f"clip/{kind}/{samples}/{amplitude!r}", seed)
+    t = np.arange(samples, dtype=np.float64) / sample_rate
+    if kind == "harmonic":
+        f0 = g.uniform(90.0, 300.0) * (1.0 + 0.03 * np.sin(2 * np.pi * 5.5 * t + g.uniform(0, 2 * np.pi)))
+        ph = 2 * np.pi * np.cumsum(f0) / sample_rate
+        x = sum(0.7 ** h * np.sin(h * ph + g.uniform(0, 2 * np.pi)) for h in range(1, 7)) + 0.01 * g.standard_normal(samples)
+    elif kind == "noise":
+        x = g.standard_normal(samples)
+    elif kind == "silence":
+        x = np.zeros(samples)
+    elif kind == "edge_hi":         # 700 -> 800 Hz: periods from 31.5 down to the 27.6 samples of torch-yin's upper edge
+        x = np.sin(2 * np.pi * np.cumsum(700.0 + 100.0 * t / max(t[-1], 1e-9)) / sample_rate + g.uniform(0, 2 * np.pi))
+    elif kind == "edge_lo":
+        x = np.sin(2 * np.pi * 42.0 * t + g.uniform(0, 2 * np.pi)) + 0.3 * np.sin(2 * np.pi * 84.0 * t)
+    else:
+        f = 100.0 * 4.0 ** (t / max(t[-1], 1e-9)) if samples > 1 else np.full(samples, 100.0)
+        voiced = (np.floor(t / 0.1) % 2) == 0
+        x = np.where(voiced, np.sin(2 * np.pi * np.cumsum(f) / sample_rate), 0.3 * g.standard_normal(samples))
+    peak = np.abs(x).max() if samples else 0.0
+    x = x * (amplitude / peak) if peak > 0 else x
+    return torch.from_numpy(x.astype(np.float32))
+
+
+def make_feature_case(case: str, seed: int = SEED) -> list[torch.Tensor]:
+    return [make_clip(k, n, a, seed) for k, n, a in FEATURE_CASES[case]]

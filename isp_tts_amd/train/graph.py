@@ -28,19 +28,30 @@ class GraphedTrainStep:
     `evaluator` (e.g. acoustic.AcousticModelEvaluator, the reference's `metrics = self.evaluator(inputs, outputs)` of
     experiments/trainer.py:557-559): the captured step also runs it on the step's forward outputs, before the backward;
     after each replay `step.metrics` holds its dict and `step.outputs` the (detached) AcousticModelOutput it saw.  It must
-    issue device work only (the acoustic evaluator is one libispk launch pair)."""
+    issue device work only (the acoustic evaluator is one libispk launch pair).
+    `features` (data.AcousticFeatures, the reference dataset's providers): the batch carries text, text_len, audio [B, S]
+    and audio_len instead of mel, mel_len, pitch and energy, and the captured step starts with the extractor's one launch;
+    after each replay `step.features` holds its outputs (the step's mel, mel_len, pitch and energy)."""
 
     KEYS = ("text", "text_len", "mel", "mel_len", "pitch", "energy")
+    AUDIO_KEYS = ("text", "text_len", "audio", "audio_len")
 
     def __init__(self, model, opt: FlatAdamW, batch: dict, amp: bool = True, train_aligner: bool = True, warmup: int = 2,
-                 evaluator=None):
+                 evaluator=None, features=None):
         assert opt.world == 1 and opt.grad_accum_steps == 1, "one rank, no accumulation"
         self.model, self.opt, self.amp, self.train_aligner = model, opt, amp, train_aligner
         self.evaluator, self.metrics, self.outputs = evaluator, None, None
+        self.extractor, self.features = features, None
         dev = batch["text"].device
         if evaluator is not None and hasattr(evaluator, "mcd_evaluator"):
             evaluator.mcd_evaluator.dct(dev)                # (its DCT basis reaches the device before, not inside, the capture)
-        self.static = {k: batch[k].clone() for k in self.KEYS}
+        keys = self.KEYS
+        if features is not None:
+            assert features.pitch and features.energy, "the training step needs pitch and energy"
+            keys = self.AUDIO_KEYS
+            features.device_tables(dev)                     # (its tables reach the device before, not inside, the capture)
+            self.features = features.empty_outputs(*batch["audio"].shape, dev)
+        self.static = {k: batch[k].clone() for k in keys}
         b, l = batch["text"].shape
         self.static["flow_x0"] = batch["flow_x0"].clone() if "flow_x0" in batch else torch.randn(b, l, 3, device=dev)
         self.static["flow_t"] = batch["flow_t"].clone() if "flow_t" in batch else torch.rand(b, device=dev)
@@ -84,7 +95,7 @@ class GraphedTrainStep:
     def close(self) -> None:
         """Forget the graph and what the module-global caches still hold of its private pool (weight images staged during the
         capture, the capture stream's workspace), so that the pool's memory can be returned."""
-        self.graph, self.out, self.metrics, self.outputs = None, None, None, None
+        self.graph, self.out, self.metrics, self.outputs, self.features = None, None, None, None, None
         for m in self.model.modules():
             m.__dict__.pop("_train_images", None)
         if getattr(self, "_capture_stream_key", None) is not None:
@@ -101,6 +112,8 @@ class GraphedTrainStep:
 
     def _body(self):
         s = self.static
+        if self.extractor is not None:
+            s = dict(s, **self.extractor(s["audio"], s["audio_len"], out=self.features))
         if self.evaluator is None:
             _, total, losses = acoustic_train_forward(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"],
                                                       s["energy"], flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
