@@ -667,6 +667,40 @@ int32_t ispk_audio_features_f32(const float* audio, int64_t ld_audio, const int6
                                 int64_t table_floats, const int32_t* fb_index, int32_t n_mels, float* mel, int64_t* mel_len, float* pitch, float* energy,
                                 int32_t B, int32_t S, int32_t M, int32_t tau_min, int32_t tau_max, float sample_rate,
                                 float threshold, float pitch_mean, float pitch_std, ispk_stream_t stream);
+/* Vocos vocoder (mel variant, VocosBackbone + ISTFTHead, padding "same", n_fft 1024, hop 256; isp_tts_amd/vocoder.py): the
+ * three kernels besides ispk_gemm_* and ispk_layernorm_*.  Utterance b is frames [0, len_b) of [B][.][T] rows, len_b =
+ * mel_len[b] (mel_len NULL: every utterance has all T frames).  A device mel_len outside [0, T] counts as 0: zero rows,
+ * audio_len 0, nothing read.  Rows are r = b T + t.  B = 0 is a no-op.  One launch each, every sum in a fixed order, no
+ * atomics: repeated calls and graph replays are bit-identical.
+ *
+ * ispk_vocoder_unfold        the embedding Conv1d(C -> dim, kernel 7, padding 3) as GEMM rows:
+ *                            rows[r][j C + c] = mel(b, c, t + j - 3) inside [0, len_b), 0 outside it, at k >= 7 C (K padding)
+ *                            and on rows t >= len_b.  mel fp32 (mel_f16 = 0) or fp16 at element (b, c, t) = b sb + c sc + t st
+ *                            (any strides: a transposed view works); rows fp32 or bf16 (rows_bf16) at row stride ldr >= K.
+ *                            K % 8 == 0, K >= 7 C, 1 <= C <= 128.  row_mask (may be NULL): byte [B T], 1 where t < len_b.
+ *                            Nothing at or past len_b is read, so padding may hold NaN.
+ * ispk_dwconv7_ln_f32        y[r] = LayerNorm(dwconv7(x)[r]) for t < len_b, 0 for t >= len_b: the depthwise Conv1d(D, 7,
+ *                            padding 3, groups D) with taps w [D][7] and bias [D] over rows t - 3 .. t + 3 of the same
+ *                            utterance (0 outside [0, len_b)), then LayerNorm over D (biased variance, gamma / beta, eps).
+ *                            x fp32 [B T][ldx]; y fp32 or bf16 (y_bf16) [B T][ldy].  D % 64 == 0, 64 <= D <= 1024.
+ * ispk_istft_head_f32        audio from the head Linear's rows h [B T][ldh >= 1026] (fp32, bias added): bins k <= 512,
+ *                            S_k = min(exp(h[r][k]), 100) (cos + i sin)(h[r][513 + k]) (NaN stays NaN), frame t = irfft_1024(S)
+ *                            (imaginary parts of bins 0 and 512 ignored) times the window, overlap-added at stride 256 over
+ *                            the utterance's own len_b frames, divided by the overlap-added window^2 of those frames, and
+ *                            trimmed by 384 samples at both ends: audio[b][m], m < 256 len_b; 0 for 256 len_b <= m < S.
+ *                            audio_len[b] = 256 len_b (may be NULL).  tables: fp32 [4096] W_2048^m (re, im) made in float64
+ *                            (data.features.twiddles()), then the 1024-point window; table_floats >= 5120.  S >= 256 T,
+ *                            ld_audio >= S.
+ * Refused: NULL required pointers (-1); shapes out of range (-2). */
+int32_t ispk_vocoder_unfold(const void* mel, int32_t mel_f16, int64_t sb, int64_t sc, int64_t st, const int64_t* mel_len,
+                            void* rows, int32_t rows_bf16, int64_t ldr, uint8_t* row_mask, int32_t B, int32_t C, int32_t T,
+                            int32_t K, ispk_stream_t stream);
+int32_t ispk_dwconv7_ln_f32(const float* x, int64_t ldx, const float* w, const float* bias, const float* gamma,
+                            const float* beta, float eps, const int64_t* mel_len, void* y, int32_t y_bf16, int64_t ldy,
+                            int32_t B, int32_t T, int32_t D, ispk_stream_t stream);
+int32_t ispk_istft_head_f32(const float* h, int64_t ldh, const int64_t* mel_len, const float* tables, int64_t table_floats,
+                            float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B, int32_t T, int32_t S,
+                            ispk_stream_t stream);
 int32_t ispk_aligner_scores_bwd_f32(const float* attn_logits, const float* attn_soft, const float* d_soft, const float* d_logits,
                                     const int64_t* text_len, const int64_t* mel_len, float* dS, int64_t ld_s, float* dSt,
                                     int64_t ld_t, int32_t B, int32_t M, int32_t L, float scale, ispk_stream_t stream);

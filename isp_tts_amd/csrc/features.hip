@@ -11,11 +11,13 @@
 //                             tau_max wraps) -> |X_k|^2 -> inverse real FFT -> the linear autocorrelation r(t), t < tau_max;
 //                             torch-yin's difference function and cmdf from in-workgroup scans; the first-index searches as
 //                             min-reductions; tau -> Hz with torch's reciprocal-then-multiply; (pitch - mean) / std.
-//                    Every FFT pass is radix 4 (one radix-2 pass for 512 points) in LDS with a float64-made twiddle table.
+//                    Every FFT pass is radix 4 (one radix-2 pass for 512 points) in LDS with a float64-made twiddle table
+//                    (fft.h, shared with the vocoder's ISTFT head).
 // Every sum runs in a fixed order and there are no atomics: repeated calls and graph replays give the same bits.
 #include <algorithm>
 
 #include "common.h"
+#include "fft.h"
 
 namespace {
 
@@ -32,68 +34,6 @@ constexpr int kMaxFbWeights = 2 * kBins;            // a bin lies inside at most
 constexpr int kTw = 2048;                           // twiddle table: W_2048^m, m < 2048
 constexpr int kTableHead = 2 * kTw + 1024;          // tables: twiddles, then the window, then the filterbank weights
 constexpr float kClip = 1e-5f;                      // F.dynamic_range_compression clip_val; also pitch.py:85's floor
-
-typedef float2 cf;
-
-__device__ __forceinline__ cf cadd(cf a, cf b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cf csub(cf a, cf b) { return make_float2(a.x - b.x, a.y - b.y); }
-template <bool kInv>
-__device__ __forceinline__ cf ctw(cf a, cf w) {      // a * w, or a * conj(w) for the inverse transform
-    return kInv ? make_float2(a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y)
-                : make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-
-// One Stockham autosort pass of an N-point complex DFT, in -> out; Ns = the product of the radices before it.
-template <int R, bool kInv>
-__device__ __forceinline__ void fft_pass(const cf* in, cf* out, int N, int Ns, int lt, const cf* tw) {
-    const int q = N / R;
-    for (int j = lt; j < q; j += kHalf) {
-        const int k = j & (Ns - 1);
-        const int s = (kTw / (R * Ns)) * k;
-        const int idx = (j - k) * R + k;
-        if (R == 4) {
-            const cf a0 = in[j], a1 = ctw<kInv>(in[j + q], tw[s]), a2 = ctw<kInv>(in[j + 2 * q], tw[2 * s]),
-                     a3 = ctw<kInv>(in[j + 3 * q], tw[3 * s]);
-            const cf t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), d = csub(a1, a3);
-            const cf t3 = kInv ? make_float2(-d.y, d.x) : make_float2(d.y, -d.x);     // d * (+-i)
-            out[idx] = cadd(t0, t2);
-            out[idx + Ns] = cadd(t1, t3);
-            out[idx + 2 * Ns] = csub(t0, t2);
-            out[idx + 3 * Ns] = csub(t1, t3);
-        } else {
-            const cf a0 = in[j], a1 = ctw<kInv>(in[j + q], tw[s]);
-            out[idx] = cadd(a0, a1);
-            out[idx + Ns] = csub(a0, a1);
-        }
-    }
-}
-
-// N-point complex FFT (N = 512 or 1024) of a (ping) -> b (pong): an odd number of passes, so the result is in b.
-template <bool kInv>
-__device__ __forceinline__ void fft(cf* a, cf* b, int N, int lt, const cf* tw) {
-    fft_pass<4, kInv>(a, b, N, 1, lt, tw);
-    __syncthreads();
-    fft_pass<4, kInv>(b, a, N, 4, lt, tw);
-    __syncthreads();
-    fft_pass<4, kInv>(a, b, N, 16, lt, tw);
-    __syncthreads();
-    fft_pass<4, kInv>(b, a, N, 64, lt, tw);
-    __syncthreads();
-    if (N == 1024)
-        fft_pass<4, kInv>(a, b, N, 256, lt, tw);
-    else
-        fft_pass<2, kInv>(a, b, N, 256, lt, tw);
-    __syncthreads();
-}
-
-// X_k (k <= n2) of a real sequence x of 2 n2 points, from Z = DFT_{n2}(x[2n] + i x[2n+1]) (the half-length split)
-__device__ __forceinline__ cf real_split(const cf* Z, int k, int n2, cf w) {
-    const cf zk = Z[k & (n2 - 1)], zm = Z[(n2 - k) & (n2 - 1)];
-    const cf e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));      // (Z_k + conj Z_{-k}) / 2
-    const cf dd = make_float2(zk.x - zm.x, zk.y + zm.y);                       // Z_k - conj Z_{-k}
-    const cf o = make_float2(0.5f * dd.y, -0.5f * dd.x);                       // dd / 2i
-    return cadd(e, ctw<false>(o, w));
-}
 
 // Inclusive scan of v[0, n) by the 256 threads of one half (wave `hw` of 4 within it): consecutive chunks per thread, a
 // shuffle scan per wave, the wave totals in order.  Fixed order throughout.  Ends with a barrier.
@@ -219,7 +159,7 @@ __global__ void __launch_bounds__(kThreads) features_kernel(const float* __restr
                 for (int n = lt; n < 512; n += kHalf)
                     A[n] = make_float2(win[2 * n] * x[2 * n], win[2 * n + 1] * x[2 * n + 1]);
                 __syncthreads();
-                fft<false>(A, Bf, 512, lt, tw);
+                fft<false, kHalf, kTw>(A, Bf, 512, lt, tw);
                 float e2 = 0.f;
                 for (int k = lt; k < kBins; k += kHalf) {
                     const cf X = real_split(Bf, k, 512, tw[2 * k]);
@@ -245,7 +185,7 @@ __global__ void __launch_bounds__(kThreads) features_kernel(const float* __restr
                 for (int n = lt; n < 1024; n += kHalf)
                     A[n] = make_float2(2 * n < FL ? x[2 * n] : 0.f, 2 * n + 1 < FL ? x[2 * n + 1] : 0.f);
                 __syncthreads();
-                fft<false>(A, Bf, 1024, lt, tw);
+                fft<false, kHalf, kTw>(A, Bf, 1024, lt, tw);
                 for (int k = lt; k <= 1024; k += kHalf) {
                     const cf X = real_split(Bf, k, 1024, tw[k]);
                     Af[k] = X.x * X.x + X.y * X.y;                  // |X_k|^2, real and even in k
@@ -258,7 +198,7 @@ __global__ void __launch_bounds__(kThreads) features_kernel(const float* __restr
                     Bf[k] = make_float2(e - o.y, o.x);
                 }
                 __syncthreads();
-                fft<true>(Bf, A, 1024, lt, tw);                     // A[n] = 1024 (r[2n] + i r[2n+1])
+                fft<true, kHalf, kTw>(Bf, A, 1024, lt, tw);         // A[n] = 1024 (r[2n] + i r[2n+1])
                 // squares -> prefix sums (Bff[0, FL)); the difference function from lag 1 (Bff[FL, FL + tau_max - 1))
                 for (int i = lt; i < FL; i += kHalf) Bff[i] = x[i] * x[i];
                 __syncthreads();

@@ -132,6 +132,9 @@ SIGNATURES = {
     "ispk_adamw_f32_dev": [_P, _P, _P, _P, _I64, _I64, _P, _P, _P],
     "ispk_adam_args_f32": [_F32, _F32, _F32, _F32, _F32, _I32, _F32, _F32, _P],
     "ispk_set_dropout_seed_source": [_P],
+    "ispk_vocoder_unfold": [_P, _I32, _I64, _I64, _I64, _P, _P, _I32, _I64, _P, _I32, _I32, _I32, _I32, _P],
+    "ispk_dwconv7_ln_f32": [_P, _I64, _P, _P, _P, _P, _F32, _P, _P, _I32, _I64, _I32, _I32, _I32, _P],
+    "ispk_istft_head_f32": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _P],
 }
 
 _lib = None
@@ -1927,3 +1930,79 @@ def adamw(p: Tensor, g: Tensor, m: Tensor, v: Tensor, n_decay: int, lr: float, b
     _launch("adamw_kernel", 0.0, 28.0 * p.numel(), lib().ispk_adamw_f32, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
             p.numel(), n_decay, lr, betas[0], betas[1], eps, weight_decay, step, _ptr(grad_sqnorm), max_norm, grad_scale,
             _stream())
+
+
+# ------------------------------------------------------------------------------------------------- Vocos vocoder
+VOCODER_HOP = 256             # ispk_istft_head_f32: n_fft 1024, hop 256, padding "same"
+VOCODER_TABLE_FLOATS = 2 * 2048 + 1024
+
+
+def _lengths_ptr(mel_len: Optional[Tensor], B: int) -> Optional[int]:
+    if mel_len is None:
+        return None
+    if mel_len.dtype != torch.int64 or mel_len.shape != (B,) or not mel_len.is_contiguous():
+        raise ValueError(f"mel_len: contiguous int64 [{B}], got {mel_len.dtype} {tuple(mel_len.shape)}")
+    return mel_len.data_ptr()
+
+
+def vocoder_unfold(mel: Tensor, mel_len: Optional[Tensor], rows: Tensor, row_mask: Optional[Tensor] = None) -> Tensor:
+    """ispk_vocoder_unfold: mel fp32 / fp16 [B, C, T] (any strides) -> the embedding convolution's GEMM rows [B*T, K] (fp32 or
+    bf16, K % 8 == 0, K >= 7 C; column j*C + c = tap j of channel c), zero past mel_len; row_mask bool [B*T] (t < mel_len)."""
+    _dev(mel, mel_len, rows, row_mask)
+    assert mel.ndim == 3 and mel.dtype in (torch.float32, torch.float16)
+    B, C, T = mel.shape
+    assert rows.ndim == 2 and rows.shape[0] == B * T and rows.stride(1) == 1 and rows.dtype in (torch.float32, torch.bfloat16)
+    assert row_mask is None or (row_mask.dtype == torch.bool and row_mask.numel() == B * T and row_mask.is_contiguous())
+    K = rows.shape[1]
+    ml = _lengths_ptr(mel_len, B)
+    if B * T == 0:
+        return rows
+    _launch(f"vocoder_unfold_kernel<{'f16' if mel.dtype == torch.float16 else 'f32'},"
+            f"{'bf16' if rows.dtype == torch.bfloat16 else 'f32'}>", 0.0,
+            float(mel.numel() * mel.element_size() + rows.numel() * rows.element_size() + B * T), lib().ispk_vocoder_unfold,
+            mel.data_ptr(), int(mel.dtype == torch.float16), mel.stride(0), mel.stride(1), mel.stride(2), ml, rows.data_ptr(),
+            int(rows.dtype == torch.bfloat16), rows.stride(0), _ptr(row_mask), B, C, T, K, _stream())
+    return rows
+
+
+def dwconv7_ln(x: Tensor, T: int, weight: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, mel_len: Optional[Tensor],
+               eps: float = 1e-6, out_dtype: torch.dtype = torch.float32, out: Optional[Tensor] = None) -> Tensor:
+    """ispk_dwconv7_ln_f32: x fp32 [B*T, D] rows (unit column stride) -> LayerNorm(depthwise conv7(x)) fp32 / bf16 [B*T, D],
+    each utterance's frames [0, mel_len) convolved alone, rows past mel_len zero.  weight fp32 [D, 7] contiguous."""
+    _dev(x, weight, bias, gamma, beta, mel_len, out)
+    assert x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1
+    R, D = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.shape == (D, 7) and weight.is_contiguous()
+    if out is None:
+        out = torch.empty((R, D), dtype=out_dtype, device=x.device)
+    assert out.shape == (R, D) and out.stride(1) == 1 and out.dtype in (torch.float32, torch.bfloat16)
+    ml = _lengths_ptr(mel_len, B)
+    if R == 0:
+        return out
+    _launch(f"dwconv7_ln_kernel<{D // 64},{'bf16' if out.dtype == torch.bfloat16 else 'f32'}>", 18.0 * R * D,
+            float(R * D * (4 + out.element_size())), lib().ispk_dwconv7_ln_f32, x.data_ptr(), x.stride(0), weight.data_ptr(),
+            bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, ml, out.data_ptr(), int(out.dtype == torch.bfloat16),
+            out.stride(0), B, T, D, _stream())
+    return out
+
+
+def istft_head(h: Tensor, T: int, mel_len: Optional[Tensor], tables: Tensor, audio: Tensor,
+               audio_len: Optional[Tensor] = None) -> Tensor:
+    """ispk_istft_head_f32: the head Linear's fp32 rows h [B*T, >= 1026] (log-magnitudes in columns 0-512, phases in 513-1025)
+    -> audio fp32 [B, S] (unit stride on S, S >= 256 T; zero from 256 mel_len on) and audio_len int64 [B] = 256 mel_len."""
+    _dev(h, mel_len, tables, audio, audio_len)
+    assert h.dtype == torch.float32 and h.ndim == 2 and h.stride(1) == 1
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and audio.stride(1) == 1
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= VOCODER_TABLE_FLOATS
+    B, S = audio.shape
+    assert h.shape[0] == B * T
+    assert audio_len is None or (audio_len.dtype == torch.int64 and audio_len.shape == (B,) and audio_len.is_contiguous())
+    ml = _lengths_ptr(mel_len, B)
+    if B == 0:
+        return audio
+    R = B * T
+    _launch("istft_head_kernel", R * 1.25 * (5.0 * 512 * 9 + 20.0 * 513), float(R * 1026 * 4 + B * S * 4),
+            lib().ispk_istft_head_f32, h.data_ptr(), h.stride(0), ml, tables.data_ptr(), tables.numel(), audio.data_ptr(),
+            audio.stride(0), _ptr(audio_len), B, T, S, _stream())
+    return audio

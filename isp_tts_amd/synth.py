@@ -283,3 +283,47 @@ def make_clip(kind: str, samples: int, amplitude: float = 0.5, seed: int = SEED,
 
 def make_feature_case(case: str, seed: int = SEED) -> list[torch.Tensor]:
     return [make_clip(k, n, a, seed) for k, n, a in FEATURE_CASES[case]]
+
+
+VOCODER_DIMS = {"official": (80, 512, 1536, 8), "small": (100, 384, 1152, 3)}   # (n_mels, dim, intermediate, layers)
+
+
+def make_vocoder_state_dict(dims=VOCODER_DIMS["official"], seed: int = SEED, gamma: bool = True) -> dict[str, torch.Tensor]:
+    """Synthetic Vocos (mel variant) weights in the official state-dict layout (backbone.*, head.*), from keyed streams.
+    dims = (n_mels, dim, intermediate, layers).  The head is scaled so that, on LayerNorm-ed rows, the log-magnitude
+    (N(0.5, 2.5^2)-like) lies on both sides of the log(100) clip and the phase carries a per-bin offset of up to +-300 rad
+    (sincos far outside [-pi, pi]) plus an N(0, 2^2) data-dependent part."""
+    n_mels, dim, inter, layers = dims
+    u = lambda name, shape, lo, hi: torch.from_numpy(_rng(name, seed).uniform(lo, hi, size=tuple(shape)).astype(np.float32))
+    sd = {"backbone.embed.weight": _normal("voc/embed.w", (dim, n_mels, 7), 1.0 / math.sqrt(7 * n_mels), seed=seed),
+          "backbone.embed.bias": _normal("voc/embed.b", (dim,), 0.1, seed=seed),
+          "backbone.norm.weight": _normal("voc/norm.w", (dim,), 0.1, 1.0, seed=seed),
+          "backbone.norm.bias": _normal("voc/norm.b", (dim,), 0.1, seed=seed)}
+    for i in range(layers):
+        p = f"backbone.convnext.{i}."
+        sd[p + "dwconv.weight"] = _normal(f"voc/{i}/dw.w", (dim, 1, 7), 1.0 / math.sqrt(7), seed=seed)
+        sd[p + "dwconv.bias"] = _normal(f"voc/{i}/dw.b", (dim,), 0.1, seed=seed)
+        sd[p + "norm.weight"] = _normal(f"voc/{i}/ln.w", (dim,), 0.1, 1.0, seed=seed)
+        sd[p + "norm.bias"] = _normal(f"voc/{i}/ln.b", (dim,), 0.1, seed=seed)
+        sd[p + "pwconv1.weight"] = _normal(f"voc/{i}/pw1.w", (inter, dim), 1.0 / math.sqrt(dim), seed=seed)
+        sd[p + "pwconv1.bias"] = _normal(f"voc/{i}/pw1.b", (inter,), 0.1, seed=seed)
+        sd[p + "pwconv2.weight"] = _normal(f"voc/{i}/pw2.w", (dim, inter), 1.0 / math.sqrt(inter), seed=seed)
+        sd[p + "pwconv2.bias"] = _normal(f"voc/{i}/pw2.b", (dim,), 0.1, seed=seed)
+        if gamma:
+            sd[p + "gamma"] = u(f"voc/{i}/gamma", (dim,), 0.05, 0.5)
+    sd["backbone.final_layer_norm.weight"] = _normal("voc/fln.w", (dim,), 0.1, 1.0, seed=seed)
+    sd["backbone.final_layer_norm.bias"] = _normal("voc/fln.b", (dim,), 0.1, seed=seed)
+    sd["head.out.weight"] = torch.cat([_normal("voc/head.mag.w", (513, dim), 2.5 / math.sqrt(dim), seed=seed),
+                                       _normal("voc/head.ph.w", (513, dim), 2.0 / math.sqrt(dim), seed=seed)])
+    sd["head.out.bias"] = torch.cat([_normal("voc/head.mag.b", (513,), 0.5, 0.5, seed=seed),
+                                     u("voc/head.ph.b", (513,), -300.0, 300.0)])
+    sd["head.istft.window"] = torch.hann_window(1024)
+    return sd
+
+
+def make_vocoder_mel(B: int, n_mels: int, T: int, seed: int = SEED) -> torch.Tensor:
+    """A log-mel-like fp32 [B, n_mels, T] input (smooth in time, values around -11 .. 2)."""
+    g = _rng(f"voc/mel/{B}/{n_mels}/{T}", seed)
+    x = g.standard_normal((B, n_mels, T + 4)) * 1.5
+    x = (x[..., :-4] + x[..., 1:-3] + x[..., 2:-2] + x[..., 3:-1] + x[..., 4:]) / 5 * 2.0
+    return torch.from_numpy((x - 4.5 + np.linspace(1.5, -1.5, n_mels)[None, :, None]).astype(np.float32))
