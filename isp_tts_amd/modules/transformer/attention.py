@@ -101,36 +101,35 @@ class Attention(nn.Module, Constructor):
         return self._cache.get("wqc", (self.to_q.weight, self.to_kv.weight),
                                lambda: runtime.chunk_k16(self._staged(torch.bfloat16)[0]))
 
+    def qkv_lnin(self, x: Tensor, norm, stats: Optional[Tensor] = None) -> Tensor:
+        """q/kv rows of norm(x) with the LayerNorm applied by the GEMM itself while it stages the fp32 rows x (bf16 path): from
+        the row statistics the producing kernel handed over, or (None) computed by the GEMM's own waves."""
+        assert self.compute_dtype == torch.bfloat16 and x.dtype == torch.float32
+        return runtime.gemm_lnin(x, stats, norm.weight, norm.bias, self._staged(torch.bfloat16)[0], ln_eps=norm.eps)
+
     def forward(self, x: Tensor, mask: Optional[Tensor] = None, context: Optional[Tensor] = None,
                 context_mask: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
                 cache: Optional[AttentionIntermediates] = None,
                 shared_cache: Optional[AttentionSharedIntermediates] = None, *, key_len: Optional[Tensor] = None,
-                residual: Optional[Tensor] = None, prenorm: Optional[tuple] = None, defer_out: bool = False,
-                qkv: Optional[Tensor] = None):
+                residual: Optional[Tensor] = None, qkv: Optional[Tensor] = None, defer_out: bool = False):
         """x [B,N,dim] (fp32, or bf16 when compute_dtype is bf16); mask [B,N] bool, True = valid, a length mask.
         `key_len` (int64 [B]) may be passed to skip recomputing mask.sum(1); `residual` (fp32 [B,N,dim]) fuses
         `residual + mask * to_out(...)` into the output GEMM.  Returns (out, AttentionIntermediates,
         AttentionSharedIntermediates) like the reference; `rel_pos_bias` is None because no bias tensor exists.
-        `prenorm` = (row_stats | None, weight, bias, eps): x is the fp32 input of the LayerNorm that precedes this block
-        and the q/kv GEMM applies that LayerNorm while staging x (bf16 path; statistics from the producing kernel, or
-        computed by the GEMM's own waves when None).  `defer_out` (bf16 path): the first element is the attention output
-        BEFORE `to_out` (bf16 [B,N,heads*64]) - the caller's next kernel applies `to_out`, mask and residual itself
-        (`runtime.attn_out_ffn`).  `qkv` (bf16 [B,N,heads*64+128]): the q/kv rows of norm(x), already produced by the previous
-        layer's kernel - no projection here."""
+        `qkv` (bf16 [B,N,heads*64+128]): the q/kv rows of norm(x), already produced - by the previous layer's kernel or by
+        `qkv_lnin` - so no projection here (x gives the shape only).  `defer_out` (bf16 path): the first element is the
+        attention output BEFORE `to_out` (bf16 [B,N,heads*64]) - the caller's next kernel applies `to_out`, mask and residual
+        itself (`runtime.attn_out_ffn`).  Which of these a layer uses is `plan.select_plan`'s decision."""
         if context is not None or context_mask is not None or attention_mask is not None or cache is not None:
             raise NotImplementedError("cross-attention, explicit attention masks and KV caches are not on the "
                                       "acoustic-model forward path and are not built")
-        b, n, _ = x.shape
+        b, n = x.shape[-3:-1]
         dt = self.compute_dtype
         wqkv, wo, slopes = self._staged(dt)
         if mask is not None and key_len is None:
             key_len = mask.sum(dim=1)
         if dt == torch.float16:   # split-fp16 path (x fp32, or already split planes [2, B, N, dim])
-            if x.dtype == torch.float16:
-                b, n = x.shape[1], x.shape[2]
-                xs = x
-            else:
-                xs = runtime.split_f16(x.float().contiguous())
+            xs = x if x.dtype == torch.float16 else runtime.split_f16(x.float().contiguous())
             qkv = runtime.gemm_split(xs, wqkv)
             o = runtime.alibi_mqa_attention_split(qkv, self.heads, slopes, key_len)
             out = runtime.gemm_split(o, wo, resid=residual, mask=mask, flags=runtime.EP_MASK_ACC if mask is not None else 0)
@@ -140,9 +139,6 @@ class Attention(nn.Module, Constructor):
             return out, inter, AttentionSharedIntermediates(rel_pos_bias=None)
         if qkv is not None:
             assert dt == torch.bfloat16 and qkv.dtype == dt and qkv.shape == (b, n, self.heads * 64 + 128)
-        elif prenorm is not None:
-            assert dt == torch.bfloat16 and x.dtype == torch.float32
-            qkv = runtime.gemm_lnin(x, prenorm[0], prenorm[1], prenorm[2], wqkv, ln_eps=prenorm[3])
         else:
             if x.dtype != dt:
                 x = runtime.cast_bf16(x) if dt == torch.bfloat16 else x.float()

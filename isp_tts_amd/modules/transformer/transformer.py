@@ -1,6 +1,7 @@
 """`TransformerLayer` / `Transformer` (tts/modules/transformer/transformer.py:37-211 of the reference).
 
-Pre-norm layer, as launched here (7 kernels, activations make one HBM round trip between them):
+Pre-norm layer with nothing fused (7 kernels, activations make one HBM round trip between them): the exact-fp32 path, the
+split-fp16 path (the same seven on csrc/split.hip's kernels, operands as hi / lo fp16 planes), adaptive norms, bf16 below 128 rows
     h  = LN/AdaLN(x)                                   ispk_layernorm
     qkv = h · [Wq;Wkv]ᵀ                                ispk_gemm
     o  = ALiBi-MQA(qkv)                                ispk_alibi_mqa_attn
@@ -10,12 +11,10 @@ Pre-norm layer, as launched here (7 kernels, activations make one HBM round trip
     y  = mask * (x1 + f · W2ᵀ)                         ispk_gemm, epilogue residual + MASK_OUT   (:105-110)
 The residual stream (x, x1, y) is always fp32; with compute_dtype = bf16 the GEMM/attention operands are bf16.
 
-bf16 path, decoder-sized batches (dim 384 = heads * 64, >= 16,385 rows): a layer is TWO launches -
-    o  = ALiBi-MQA(qkv)                                ispk_alibi_mqa_attn_bf16      (qkv comes from the previous layer's kernel)
-    y, qkv_next = ...                                  ispk_attn_out_ffn_qkv_bf16:   x1 = x + mask * (o · Woᵀ) in the accumulators,
-                                                       y = mask * (x1 + FFN(LN(x1))), qkv_next = LN_next(y) · [Wq;Wkv]_nextᵀ
-(first layer: q/kv by ispk_gemm_bf16_lnin; last layer: ispk_attn_out_ffn_bf16).  Small batches: LayerNorm folded into the split
-feed-forward's combine pass, see `FeedForward.forward_prenorm_split`.
+bf16 path, plain LayerNorms: `plan.select_plan` folds these launches into each other by the stack's size (table: DESIGN.md 4.1d).
+Dim 384 from 16,385 rows (decoder): TWO launches a layer, attention and ispk_attn_out_ffn_qkv_bf16 (to_out, y and the NEXT layer's
+q/kv rows; the last layer's writes the stack's final norm instead).  Dim 384, 128 .. 16,384 rows (text encoder): the feed-forward
+split over the inner dimension + one combine pass that applies the consuming LayerNorm, 5 launches a layer (4 from 8,192 rows).
 """
 from __future__ import annotations
 
@@ -33,6 +32,7 @@ from .attend import AttentionIntermediates
 from .attention import Attention, AttentionConfig, AttentionSharedIntermediates
 from .feedforward import FeedForward, FeedForwardConfig
 from .normalization import AdaptiveLayerNorm, LayerNorm
+from .plan import ATTN_OUT_FFN_FORMS, Consumer, Form, Hand, Handed, Next, Plan, Qkv, Seams, select_plan
 
 
 class TransformerLayerIntermediates(NamedTuple):
@@ -40,10 +40,10 @@ class TransformerLayerIntermediates(NamedTuple):
 
 
 class TransformerLayerOutput(NamedTuple):
-    out: Tensor
+    out: Optional[Tensor]            # (None when the plan stores only what it hands on)
     intermediates: Optional[TransformerLayerIntermediates] = None
     shared_intermediates: Optional[AttentionSharedIntermediates] = None
-    next_normed: Optional[Tensor] = None   # LN_next(out) when the feed-forward kernel produced it (not in the reference)
+    handed: Handed = Handed()        # what the layer's kernels already produced for the consumer of `out` (not in the reference)
 
 
 @dataclass
@@ -57,19 +57,6 @@ class TransformerLayerConfig(ModuleConfig):
 
 
 class TransformerLayer(nn.Module, Constructor):
-    # Path switches are plain class attributes (set them on the class or on an instance; nothing reads the environment).
-    # LayerNorm applied by the consuming GEMM's own waves (ispk_gemm_bf16_lnin with row_stats = NULL), decoder-sized batches:
-    lnin_self = True
-    # to_out + residual + feed_forward_norm + feed-forward + residual as ONE kernel (ispk_attn_out_ffn_bf16; x1 never reaches
-    # memory), bf16 path, dim 384 = heads * 64, decoder-sized batches:
-    proj_ffn = True
-    final_norm_fused = True    # the stack's final LayerNorm from the last layer's fused kernel (ispk_attn_out_ffn_norm_bf16)
-    # ... and in every workgroup of the split feed-forward (ispk_attn_out_ffn_split_bf16) - where that pays: with 2 splits (16,384
-    # decoder rows = 32 utterances per GPU: 1.512 -> 1.498 ms per step); with 4 - 8 splits per row block the repeated projection
-    # costs more than the to_out launch it saves (6,400 rows: 2.004 -> 2.012 ms; 8 utterances per GPU: 1.014 -> 1.066 ms)
-    proj_ffn_split = True
-    proj_ffn_split_min_rows = 8192
-
     def __init__(self, dim: int = 384, attention=None, feed_forward=None, pre_norm: bool = True,
                  adaptive_norm: bool = False, condition_dim: Optional[int] = None):
         super().__init__()
@@ -77,105 +64,78 @@ class TransformerLayer(nn.Module, Constructor):
             raise NotImplementedError("post-norm layers are unused by the recipes and not built")
         assert not adaptive_norm or condition_dim is not None
         self.pre_norm, self.adaptive_norm = pre_norm, adaptive_norm
-        # LayerNorm inside the consuming GEMM with statistics computed by the GEMM's own waves: pays from decoder-sized
-        # batches on (33.0 vs 22.1 + 15.0 us at 32,768 rows); at 6,400 rows the output is split over many workgroups that
-        # each repeat the fp32 staging, and the separate 4.9-us LayerNorm is cheaper (18.6 vs 9.4 + 4.9 us)
-        self.lnin_self_min_rows = 128 * 128
         norm = (lambda: AdaptiveLayerNorm(dim, condition_dim=condition_dim)) if adaptive_norm else (lambda: LayerNorm(dim))
         self.attention_norm = norm()
         self.attention = Attention.init(attention if attention is not None else AttentionConfig(), dim=dim)
         self.feed_forward_norm = norm()
         self.feed_forward = FeedForward.init(feed_forward if feed_forward is not None else FeedForwardConfig(), dim=dim)
 
+    def _plan(self, dim: int, rows: int, prev: Handed, consumer: Consumer, seams: Optional[Seams]) -> Plan:
+        """This layer's facts as plain values, through `select_plan`."""
+        att, ff = self.attention, self.feed_forward
+        plain = all(isinstance(n, nn.LayerNorm) and n.weight is not None and n.bias is not None
+                    for n in (self.attention_norm, self.feed_forward_norm))
+        nxt = consumer.attention
+        return select_plan(cdt=att.compute_dtype, dim=dim, heads=att.heads, out_dim=att.out_dim, inner=ff.net[0].weight.shape[0],
+                           rows=rows, plain_norms=plain, bias1=ff.net[0].bias is not None, bias2=ff.net[3].bias is not None,
+                           gelu=ff.act_flag == runtime.EP_GELU, dropout=ff.training and ff.dropout_p > 0, prev=prev.kind,
+                           consumer=consumer.kind, consumer_dtype=consumer.dtype, next_heads=nxt.heads if nxt is not None else 0,
+                           next_dim=nxt.dim if nxt is not None else 0, only_normed=consumer.only_normed, seams=seams)
+
     def forward(self, x: Tensor, mask: Optional[Tensor] = None, context: Optional[Tensor] = None,
                 context_mask: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
                 adaptive_condition: Optional[Tensor] = None, cache: Optional[TransformerLayerIntermediates] = None,
                 shared_cache: Optional[AttentionSharedIntermediates] = None, *, key_len: Optional[Tensor] = None,
-                ada: Optional[tuple] = None, normed: Optional[Tensor] = None, next_norm: Optional[tuple] = None,
-                skip_out: bool = False):
-        """`normed`: attention_norm(x) when the previous layer's feed-forward kernel already produced it; `next_norm`
-        = (weight, bias, eps, apply_mask, dtype) of the norm that will consume this layer's output - if the fused
-        feed-forward kernel can emit it, the output carries it in `next_normed` (bf16 path, decoder-sized batches).
-        `skip_out`: the caller consumes only `next_normed` (the last layer of a stack whose output goes through the final norm) -
-        a kernel that produces the norm itself may then leave `out` unwritten (None)."""
+                ada: Optional[tuple] = None, prev: Handed = Handed(), consumer: Consumer = Consumer(),
+                seams: Optional[Seams] = None):
+        """`ada`: the (scale, shift) pairs of the two adaptive norms, already projected from the condition.  `prev`: what the
+        previous layer's kernels already produced of this layer's attention_norm.  `consumer`: the LayerNorm that will read this
+        layer's output - where the plan's kernels can serve it, the output carries the result in `handed` (and `out` is None if
+        the consumer reads nothing else).  `seams`: the path switches, None = `plan.SEAMS`."""
         assert not self.adaptive_norm or adaptive_condition is not None or ada is not None, \
             "`adaptive_condition` should be provided for AdaptiveLayerNorm"
         if cache is not None:
             raise NotImplementedError("KV caches are not on the acoustic-model forward path")
+        if context is not None or context_mask is not None or attention_mask is not None:
+            raise NotImplementedError("cross-attention / explicit attention masks are not on the forward path")
         x = x.float().contiguous()
-        cdt = self.attention.compute_dtype
         if mask is not None and key_len is None:
             key_len = mask.sum(dim=1)
-        if cdt == torch.float16:
-            if context is not None or attention_mask is not None:
-                raise NotImplementedError("cross-attention / explicit attention masks are not on the forward path")
-            return self._forward_split(x, mask, key_len, adaptive_condition, ada)
-        kw1 = {"scale_shift": ada[0]} if ada is not None else {}
-        kw2 = {"scale_shift": ada[1]} if ada is not None else {}
-        handed = normed is not None and normed.dtype == torch.float32 and normed.shape[-1] == 2
-        qkv_in = (normed is not None and cdt == torch.bfloat16 and normed.dtype == torch.bfloat16
-                  and normed.shape[-1] == self.attention.heads * 64 + 128 != x.shape[-1])   # q/kv rows from the previous layer's kernel
-        own = (normed is None and ada is None and isinstance(self.attention_norm, nn.LayerNorm) and context is None
-               and attention_mask is None and x.shape[-1] in (256, 384) and self.attention_norm.weight is not None
-               and self.attention_norm.bias is not None and self.lnin_self
-               and x.numel() // x.shape[-1] >= self.lnin_self_min_rows)
-        final = next_norm is not None and next_norm[4] != "stats"    # the stack's final norm: only the split path's combine serves it
-        fuse = (cdt == torch.bfloat16 and self.proj_ffn and ada is None and context is None and attention_mask is None
-                and self.attention.out_dim == x.shape[-1] and self.feed_forward.proj_ok(x, self.feed_forward_norm))
-        # small batches: the same prologue in every workgroup of the split feed-forward (ispk_attn_out_ffn_split_bf16)
-        split_ok = (ada is None and (next_norm is None or next_norm[4] == "stats" or next_norm[4] in (cdt, torch.float32))
-                    and self.feed_forward.split_ok(x, self.feed_forward_norm))
-        fuse_split = (not fuse and split_ok and cdt == torch.bfloat16 and self.proj_ffn_split and context is None
-                      and attention_mask is None and self.attention.out_dim == x.shape[-1] == 384
-                      and x.numel() // x.shape[-1] >= self.proj_ffn_split_min_rows)
-        if qkv_in:
-            x1, inter, shared = self.attention(x, mask=mask, key_len=key_len, residual=x, defer_out=fuse or fuse_split, qkv=normed)
-        elif cdt == torch.bfloat16 and (handed or own):
-            # attention_norm inside the q/kv GEMM, applied while it stages x: with the row statistics the previous layer's
-            # feed-forward kernel handed over, or (first layer of a stack) computed by the GEMM's own waves
-            an = self.attention_norm
-            x1, inter, shared = self.attention(x, mask=mask, key_len=key_len, residual=x, defer_out=fuse or fuse_split,
-                                               prenorm=(normed if handed else None, an.weight, an.bias, an.eps))
-        else:
-            h = normed if normed is not None else self.attention_norm(x, adaptive_condition, out_dtype=cdt, **kw1)
-            x1, inter, shared = self.attention(h, mask=mask, context=context, context_mask=context_mask,
-                                               attention_mask=attention_mask, key_len=key_len, residual=x, defer_out=fuse or fuse_split)
-        hn = None
-        if fuse:    # (x1 is the attention output before to_out)
-            fin = final and self.final_norm_fused and next_norm[0] is not None and next_norm[1] is not None
-            y, hn = self.feed_forward.forward_proj_prenorm(x, x1, self.attention._chunked_wo(), self.feed_forward_norm, mask=mask,
-                                                           next_norm=next_norm if (fin or not final) else None,
-                                                           want_out=not (fin and skip_out))
-            return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                          shared_intermediates=shared, next_normed=hn)
-        if ada is None and self.feed_forward.prenorm_ok(x1, self.feed_forward_norm):
-            # feed_forward_norm inside the fused feed-forward kernel (its waves own whole rows); the `* mask` of :102
-            # cannot reach a kept value because the same mask multiplies the block's output (:110)
-            y, hn = self.feed_forward.forward_prenorm(x1, self.feed_forward_norm, mask=mask, next_norm=None if final else next_norm)
-            return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                          shared_intermediates=shared, next_normed=hn)
-        if split_ok:
-            # small batches: feed_forward_norm + feed-forward split over the inner dimension, then ONE pass that adds the
-            # partial products, the residual and the mask and already applies the norm that consumes the result
-            nn_ = None if next_norm is None else (next_norm[0], next_norm[1], next_norm[2], next_norm[3],
-                                                  torch.float32 if next_norm[4] == torch.float32 else cdt)
-            if fuse_split:    # (x1 is the attention output before to_out)
-                y, hn = self.feed_forward.forward_prenorm_split(x, self.feed_forward_norm, mask=mask, next_norm=nn_,
-                                                                attn_proj=(x1, self.attention._chunked_wo()))
-            else:
-                y, hn = self.feed_forward.forward_prenorm_split(x1, self.feed_forward_norm, mask=mask, next_norm=nn_)
-            return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                          shared_intermediates=shared, next_normed=hn)
-        if ada is None and self.feed_forward.prenorm_unfused_ok(x1, self.feed_forward_norm):
-            # small batches (two-GEMM feed-forward): feed_forward_norm inside the first Linear's GEMM
-            y = self.feed_forward.forward_prenorm_unfused(x1, self.feed_forward_norm, mask=mask)
-            return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                          shared_intermediates=shared, next_normed=None)
-        h2 = self.feed_forward_norm(x1, adaptive_condition, row_mask=mask, out_dtype=cdt, **kw2)
-        y = self.feed_forward(h2, residual=x1, mask=mask)
-        return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                      shared_intermediates=shared, next_normed=hn)
+        att, ff, fn = self.attention, self.feed_forward, self.feed_forward_norm
+        cdt = att.compute_dtype
+        p = self._plan(x.shape[-1], x.numel() // x.shape[-1], prev, consumer, seams)
 
+        def norm(n, t: Tensor, scale_shift: Optional[tuple], row_mask: Optional[Tensor] = None) -> Tensor:
+            if cdt == torch.float16:   # (split fp16 planes out)
+                return self._norm_split(n, t, adaptive_condition, scale_shift, row_mask)
+            kw = {} if scale_shift is None else {"scale_shift": scale_shift}
+            return n(t, adaptive_condition, row_mask=row_mask, out_dtype=cdt, **kw)
+
+        qkv = None
+        if p.qkv is Qkv.HANDED_QKV:
+            qkv = prev.tensor
+        elif p.qkv in (Qkv.LNIN_STATS, Qkv.LNIN_SELF):
+            qkv = att.qkv_lnin(x, self.attention_norm, prev.tensor if p.qkv is Qkv.LNIN_STATS else None)
+        h = x if qkv is not None else prev.tensor if p.qkv is Qkv.HANDED_ROWS else norm(self.attention_norm, x, ada and ada[0])
+        # (with `defer_out`, x1 is the attention output before to_out)
+        x1, inter, shared = att(h, mask=mask, key_len=key_len, residual=x, qkv=qkv, defer_out=p.defer_out)
+
+        second = None
+        served = consumer if p.hands is not Hand.NONE else None
+        if p.form in ATTN_OUT_FFN_FORMS:
+            y, second = ff.attn_out_ffn(x, x1, att._chunked_wo(), fn, mask, p.form, served, p.store_out)
+        elif p.form in (Form.FFN_PRENORM2, Form.FFN_PRENORM):
+            y, second = ff.prenorm(x1, fn, mask, p.form is Form.FFN_PRENORM2, served.eps if served is not None else None)
+        elif p.form is Form.SPLIT_PROJ:
+            y, second = ff.prenorm_split(x, fn, mask, p.splits, served, p.hand_dtype, attn_proj=(x1, att._chunked_wo()))
+        elif p.form is Form.SPLIT:
+            y, second = ff.prenorm_split(x1, fn, mask, p.splits, served, p.hand_dtype)
+        elif p.form is Form.LNIN_GEMM:
+            y = ff.lnin_gemm(x1, fn, mask)
+        else:   # NORM_FFN_FUSED, NORM_FFN_GEMMS, SPLIT_FP16
+            y = ff(norm(fn, x1, ada and ada[1], mask), residual=x1, mask=mask, fused=p.form is Form.NORM_FFN_FUSED)
+        return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
+                                      shared_intermediates=shared, handed=Handed(p.hands, second))
 
     def _norm_split(self, norm, x: Tensor, condition: Optional[Tensor], scale_shift: Optional[tuple],
                     row_mask: Optional[Tensor]) -> Tensor:
@@ -190,30 +150,6 @@ class TransformerLayer(nn.Module, Constructor):
             rows_per_batch = x.numel() // (x.shape[0] * x.shape[-1])
             return runtime.layernorm_split(x, None, None, scale_shift[0], scale_shift[1], rows_per_batch, row_mask, norm.eps)
         return runtime.layernorm_split(x, norm.weight, norm.bias, row_mask=row_mask, eps=norm.eps)
-
-    def _forward_split(self, x: Tensor, mask: Optional[Tensor], key_len: Optional[Tensor],
-                       adaptive_condition: Optional[Tensor], ada: Optional[tuple]) -> "TransformerLayerOutput":
-        """The layer on the split-fp16 kernels (csrc/split.hip: fp32-grade products, three fp16 MFMAs each) - the same seven
-        launches as the exact-fp32 path, the operands of every product carried as hi / lo fp16 planes:
-            h  = LN(x) -> planes;  qkv = h [Wq;Wkv]^T (fp32);  o = attention(qkv) -> planes
-            x1 = x + mask * (o Wo^T);  h2 = mask * LN(x1) -> planes;  f = gelu(h2 W1^T) -> planes;  y = mask * (x1 + f W2^T)"""
-        att, ff = self.attention, self.feed_forward
-        wqkv, wo, slopes = att._staged(torch.float16)
-        w1, w2 = ff._staged(torch.float16)
-        b, n, _ = x.shape
-        h = self._norm_split(self.attention_norm, x, adaptive_condition, None if ada is None else ada[0], None)
-        qkv = runtime.gemm_split(h, wqkv)
-        o = runtime.alibi_mqa_attention_split(qkv, att.heads, slopes, key_len)
-        x1 = runtime.gemm_split(o, wo, resid=x, mask=mask, flags=runtime.EP_MASK_ACC if mask is not None else 0)
-        h2 = self._norm_split(self.feed_forward_norm, x1, adaptive_condition, None if ada is None else ada[1], mask)
-        f = runtime.gemm_split(h2, w1, bias=ff.net[0].bias, flags=ff.act_flag, out_split=True)
-        y = runtime.gemm_split(f, w2, bias=ff.net[3].bias, resid=x1, mask=mask,
-                               flags=runtime.EP_MASK_OUT if mask is not None else 0)
-        hq = att.heads * 64
-        inter = AttentionIntermediates(queries=qkv[..., :hq].view(b, n, att.heads, 64).transpose(1, 2),
-                                       keys=qkv[..., hq:hq + 64], values=qkv[..., hq + 64:])
-        return TransformerLayerOutput(out=y, intermediates=TransformerLayerIntermediates(attention=inter),
-                                      shared_intermediates=AttentionSharedIntermediates(rel_pos_bias=None), next_normed=None)
 
 
 class TransformerOutput(NamedTuple):
@@ -233,6 +169,8 @@ class TransformerConfig(ModuleConfig):
 
 
 class Transformer(nn.Module, Constructor):
+    seams: Optional[Seams] = None    # this stack's path switches (set on an instance; tests): None = `plan.SEAMS`
+
     def __init__(self, dim: int = 384, depth: int = 6, transformer_layer=None, emb_dim: Optional[int] = None,
                  use_abs_pos_emb: bool = True, adaptive_norm: bool = False, condition_dim: Optional[int] = None):
         super().__init__()
@@ -268,12 +206,6 @@ class Transformer(nn.Module, Constructor):
                  for i in range(len(norms))]
         return [(parts[2 * li], parts[2 * li + 1]) for li in range(len(self.layers))]
 
-    # The LayerNorm that consumes a layer's output moves only its STATISTICS: the fused feed-forward kernel writes (mean, rstd) per row and the
-    # next layer's q/kv GEMM (ispk_gemm_bf16_lnin) normalises while it stages its fp32 input - no normalised copy in HBM.
-    # ON: the feed-forward kernel is unchanged in time (106.6 us), q/kv goes 21.8 -> 26.6 us and the 15.0-us LayerNorm
-    # launch disappears: 2.636 -> 2.587 ms per step with one batch in flight, 2.162 -> 2.147 with two.
-    stats_layernorm = True
-
     def set_compute_dtype(self, dtype: torch.dtype):
         """fp32 (exact-fp32 MFMAs), bf16 (throughput path) or fp16 = the split-fp16 path: fp32-grade products as three fp16
         MFMAs over hi / lo terms (csrc/split.hip)."""
@@ -282,6 +214,20 @@ class Transformer(nn.Module, Constructor):
             layer.attention.compute_dtype = dtype
             layer.feed_forward.compute_dtype = dtype
         return self
+
+    def _consumer(self, li: int, mask: Optional[Tensor], out_dtype: torch.dtype, final_norm: bool) -> Consumer:
+        """The LayerNorm that reads layer `li`'s output: the next layer's attention_norm or, after the last layer, the stack's
+        own final norm (row-masked, transformer.py:205-206), which is all the caller then reads.  Whether a layer's kernels
+        serve it is the plan's decision."""
+        if li + 1 < len(self.layers):
+            nxt = self.layers[li + 1]
+            c = Consumer(Next.LAYER, nxt.attention_norm.weight, nxt.attention_norm.bias, nxt.attention_norm.eps,
+                         attention=nxt.attention)
+        else:
+            c = Consumer(Next.FINAL, self.norm.weight, self.norm.bias, self.norm.eps, mask is not None, out_dtype,
+                         only_normed=True)
+        served = not self.adaptive_norm and (li + 1 < len(self.layers) or final_norm)
+        return c if served and c.weight is not None and c.bias is not None else Consumer()
 
     def forward(self, x: Tensor, mask: Optional[Tensor] = None, context: Optional[Tensor] = None,
                 context_mask: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
@@ -303,38 +249,21 @@ class Transformer(nn.Module, Constructor):
             key_len = mask.sum(dim=1)
         intermediates = []
         ada = self._ada_all(adaptive_condition) if (self.adaptive_norm and adaptive_condition is not None) else None
-        # bf16, plain LayerNorm: a layer's fused feed-forward kernel also emits the row statistics of the LayerNorm that
-        # consumes its output (the next layer's attention_norm), which that layer's q/kv GEMM applies while it stages x
-        cdt = self.layers[0].attention.compute_dtype
-        stats = (self.stats_layernorm and not self.adaptive_norm
-                 and cdt == torch.bfloat16 and context is None and attention_mask is None)
-        chain = stats
-        normed = None
+        handed = Handed()
         for li, layer in enumerate(self.layers):
-            nxt = None
-            if chain:
-                if li + 1 < len(self.layers):
-                    nn_ = self.layers[li + 1].attention_norm
-                    nxt = (nn_.weight, nn_.bias, nn_.eps, False, "stats", self.layers[li + 1].attention)
-                elif final_norm and out_dtype in (torch.float32, torch.bfloat16):
-                    # last layer: the stack's own final norm (row-masked, transformer.py:205-206) - the split feed-forward's
-                    # combine pass applies it from the same read (small batches), the fused layer kernel from the registers that
-                    # store the rows (decoder-sized batches, ispk_attn_out_ffn_norm_bf16); the plain fused kernel ignores it
-                    nxt = (self.norm.weight, self.norm.bias, self.norm.eps, mask is not None, out_dtype)
-                if nxt is not None and (nxt[0] is None or nxt[1] is None):
-                    nxt = None
             res = layer(out, mask=mask, context=context, context_mask=context_mask, attention_mask=attention_mask,
                         adaptive_condition=adaptive_condition, key_len=key_len, ada=None if ada is None else ada[li],
-                        normed=normed, next_norm=nxt, skip_out=final_norm and li + 1 == len(self.layers))
-            out, normed = res.out, res.next_normed
+                        prev=handed, consumer=self._consumer(li, mask, out_dtype, final_norm), seams=self.seams)
+            out, handed = res.out, res.handed
             if return_intermediates:
                 intermediates.append(res.intermediates)
         if not final_norm:
             return TransformerOutput(out=out, intermediates=intermediates)
-        if normed is None:
-            if out_dtype == torch.float16:   # split fp16 planes [2, B, N, D] for a split-fp16 consumer GEMM
-                normed = runtime.layernorm_split(out, self.norm.weight, self.norm.bias, row_mask=mask, eps=self.norm.eps)
-            else:
-                normed = runtime.layernorm(out, self.norm.weight, self.norm.bias, row_mask=mask, eps=self.norm.eps,
-                                           out_dtype=out_dtype)
+        if handed.kind is Hand.ROWS:     # the last layer's kernel already applied the final norm
+            normed = handed.tensor
+        elif out_dtype == torch.float16:   # split fp16 planes [2, B, N, D] for a split-fp16 consumer GEMM
+            normed = runtime.layernorm_split(out, self.norm.weight, self.norm.bias, row_mask=mask, eps=self.norm.eps)
+        else:
+            normed = runtime.layernorm(out, self.norm.weight, self.norm.bias, row_mask=mask, eps=self.norm.eps,
+                                       out_dtype=out_dtype)
         return TransformerOutput(out=normed, intermediates=intermediates)

@@ -2,6 +2,8 @@
 against the golden fixtures generated from the real reference, and against the oracle on other seeded inputs.
 
 Tolerances: BASELINE.json's bar is mel L-inf < 1e-4 (fp32); per-op outputs are held to 5e-5."""
+from dataclasses import replace
+
 import numpy as np
 import pytest
 import torch
@@ -11,7 +13,7 @@ from conftest import crc, golden
 pytestmark = pytest.mark.gpu
 
 from isp_tts_amd import runtime, synth  # noqa: E402
-from isp_tts_amd.modules.transformer import FeedForward, Transformer, TransformerLayer  # noqa: E402
+from isp_tts_amd.modules.transformer import plan  # noqa: E402
 from oracle import acoustic_oracle as orc  # noqa: E402
 
 DEV = "cuda"
@@ -601,12 +603,10 @@ def test_bf16_fused_ffn_matches_two_gemm_path_at_full_size(gpu_model):
     try:
         dec.set_compute_dtype(torch.bfloat16)
         fused = dec(x, mask=mask, key_len=lens).out
-        for layer in dec.layers:
-            layer.feed_forward.fused_min_rows = 1 << 30
+        dec.seams = replace(plan.SEAMS, fused_min_rows=1 << 30)
         plain = dec(x, mask=mask, key_len=lens).out
     finally:
-        for layer in dec.layers:
-            layer.feed_forward.fused_min_rows = 128 * 128 + 1
+        dec.seams = None
         dec.set_compute_dtype(torch.float32)
     assert (fused - plain).abs().max() < 4e-2 and (fused - plain).pow(2).mean().sqrt() < 3e-3
     assert (fused * ~mask[..., None]).abs().max() == 0
@@ -616,9 +616,9 @@ def test_bf16_fused_ffn_matches_two_gemm_path_at_full_size(gpu_model):
 
 def test_bf16_layernorm_statistics_handoff_matches_separate_layernorm_at_full_size(gpu_model, monkeypatch):
     """Decoder stack at the benchmark shape with layers 2..6's attention LayerNorm applied inside the q/kv GEMM from the
-    previous feed-forward kernel's row statistics (`Transformer.stats_layernorm`) against separate LayerNorm launches:
+    previous feed-forward kernel's row statistics (`plan.Seams.stats_layernorm`) against separate LayerNorm launches:
     same fp32 statistics up to the reduction tree, so only 1-ulp bf16 roundings of the normalised operand differ."""
-    monkeypatch.setattr(FeedForward, "prenorm_fused", False)   # isolate the hand-off (ispk_ffn_bf16_ln -> ispk_gemm_bf16_lnin)
+    monkeypatch.setattr(plan, "SEAMS", replace(plan.SEAMS, prenorm_fused=False))   # (without the fused feed-forward kernels)
     x = synth._normal("t/chain/x", (64, 512, 384)).to(DEV)
     lens = torch.full((64,), 512, device=DEV)
     lens[2::5] = 211
@@ -626,12 +626,12 @@ def test_bf16_layernorm_statistics_handoff_matches_separate_layernorm_at_full_si
     dec = gpu_model.decoder
     try:
         dec.set_compute_dtype(torch.bfloat16)
-        dec.stats_layernorm = False
+        dec.seams = replace(plan.SEAMS, stats_layernorm=False)
         plain = dec(x, mask=mask, key_len=lens, out_dtype=torch.bfloat16).out
-        dec.stats_layernorm = True
+        dec.seams = replace(plan.SEAMS, stats_layernorm=True)
         handed = dec(x, mask=mask, key_len=lens, out_dtype=torch.bfloat16).out
     finally:
-        del dec.stats_layernorm              # back to the class default
+        dec.seams = None                     # back to the default
         dec.set_compute_dtype(torch.float32)
     diff = (handed.float() - plain.float()).abs()
     assert diff.max() < 6e-2 and diff.pow(2).mean().sqrt() < 5e-3
@@ -640,7 +640,7 @@ def test_bf16_layernorm_statistics_handoff_matches_separate_layernorm_at_full_si
 
 def test_bf16_prenorm_feed_forward_matches_separate_layernorm_at_full_size(gpu_model, monkeypatch):
     """Decoder stack at the benchmark shape with feed_forward_norm computed inside the fused feed-forward kernel
-    (ispk_ffn_bf16_prenorm, the default) against separate LayerNorm launches (ISPK_FFN_PRENORM=0)."""
+    (ispk_attn_out_ffn_bf16, the default) against separate LayerNorm launches (`plan.Seams` with the fused forms off)."""
     x = synth._normal("t/chain/x", (64, 512, 384)).to(DEV)
     lens = torch.full((64,), 512, device=DEV)
     lens[2::5] = 211
@@ -649,10 +649,7 @@ def test_bf16_prenorm_feed_forward_matches_separate_layernorm_at_full_size(gpu_m
     try:
         dec.set_compute_dtype(torch.bfloat16)
         fused = dec(x, mask=mask, key_len=lens, out_dtype=torch.bfloat16).out
-        monkeypatch.setattr(FeedForward, "prenorm_fused", False)
-        monkeypatch.setattr(Transformer, "stats_layernorm", False)
-        monkeypatch.setattr(FeedForward, "lnin_self", False)
-        monkeypatch.setattr(TransformerLayer, "lnin_self", False)
+        monkeypatch.setattr(plan, "SEAMS", replace(plan.SEAMS, prenorm_fused=False, stats_layernorm=False, lnin_self=False))
         plain = dec(x, mask=mask, key_len=lens, out_dtype=torch.bfloat16).out
     finally:
         dec.set_compute_dtype(torch.float32)
@@ -671,20 +668,15 @@ def test_bf16_encoder_with_layernorms_inside_the_gemms_matches_separate_layernor
     lens[1::3] = 37
     mask = torch.arange(100, device=DEV)[None] < lens[:, None]
     enc = gpu_model.encoder
-    saved = [(l.lnin_self_min_rows, l.feed_forward.fused_min_rows) for l in enc.layers]
     try:
         enc.set_compute_dtype(torch.bfloat16)
-        for l in enc.layers:                 # (by default only decoder-sized batches take these paths)
-            l.lnin_self_min_rows = 0
-            l.feed_forward.fused_min_rows = 0
-            l.feed_forward.prenorm_fused = False
+        # (by default only decoder-sized batches take these paths)
+        enc.seams = replace(plan.SEAMS, lnin_self_min_rows=0, fused_min_rows=0, prenorm_fused=False)
         fused = enc(x, mask=mask, key_len=lens).out
-        monkeypatch.setattr(FeedForward, "lnin_self", False)
-        monkeypatch.setattr(TransformerLayer, "lnin_self", False)
+        enc.seams = replace(enc.seams, lnin_self=False)
         plain = enc(x, mask=mask, key_len=lens).out
     finally:
-        for l, (a, b) in zip(enc.layers, saved):
-            l.lnin_self_min_rows, l.feed_forward.fused_min_rows, l.feed_forward.prenorm_fused = a, b, True
+        enc.seams = None
         enc.set_compute_dtype(torch.float32)
     diff = (fused - plain).abs()
     assert diff.max() < 6e-2 and diff.pow(2).mean().sqrt() < 5e-3
@@ -722,24 +714,21 @@ def test_decoder_stack_with_the_layer_halves_in_one_kernel(gpu_model, bsz, frame
     projection) as ONE kernel per layer (`ispk_attn_out_ffn_bf16` / `_qkv_bf16`, decoder-sized batches; `_split_bf16` from 8,192
     rows) against the same stack with those switches off (separate to_out GEMM, feed-forward kernel and q/kv GEMM): the same
     bf16 products in another fp32 summation order - agreement far inside the bf16 path's own error; masked rows exactly zero."""
-    from isp_tts_amd.modules.transformer.feedforward import FeedForward
-    from isp_tts_amd.modules.transformer.transformer import TransformerLayer
     x = synth._normal(f"t/halves/x{bsz}", (bsz, frames, 384)).to(DEV)
     lens = torch.full((bsz,), frames, device=DEV)
     lens[1::3] = frames // 2 + 3
     mask = torch.arange(frames, device=DEV)[None] < lens[:, None]
     dec = gpu_model.decoder
-    saved = (TransformerLayer.proj_ffn, TransformerLayer.proj_ffn_split, FeedForward.next_qkv)
     try:
         dec.set_compute_dtype(torch.bfloat16)
         fused = dec(x, mask=mask, key_len=lens).out
         assert torch.equal(fused, dec(x, mask=mask, key_len=lens).out)
-        TransformerLayer.proj_ffn = TransformerLayer.proj_ffn_split = FeedForward.next_qkv = False
+        dec.seams = replace(plan.SEAMS, proj_ffn=False, proj_ffn_split=False, next_qkv=False)
         plain = dec(x, mask=mask, key_len=lens).out
-        TransformerLayer.proj_ffn, TransformerLayer.proj_ffn_split = saved[0], saved[1]
+        dec.seams = replace(plan.SEAMS, next_qkv=False)
         no_qkv = dec(x, mask=mask, key_len=lens).out
     finally:
-        TransformerLayer.proj_ffn, TransformerLayer.proj_ffn_split, FeedForward.next_qkv = saved
+        dec.seams = None
         dec.set_compute_dtype(torch.float32)
     scale = plain.abs().max().item()
     for name, got in (("all in one", fused), ("without the q/kv epilogue", no_qkv)):

@@ -511,3 +511,113 @@ def test_bench_rejects_a_step_count_below_one():
     for argv in (["--steps", "0"], ["--warmup", "-1"]):
         with pytest.raises(SystemExit):
             bench.parse(argv)
+
+
+def test_layer_plan_of_every_stack_position_size_and_seam():
+    """`plan.select_plan`, the one place that chooses a transformer layer's kernels, for the first, a middle and the last
+    layer of every stack the model has (text encoder / decoder: dim 384, 6 heads; embedding stack: dim 256, ONE layer; flow
+    predictor: dim 256, adaptive norms) in fp32, bf16 and split fp16, at the benchmark's row counts (6,400 and 32,768) and either
+    side of every threshold, with every seam the tests move also at its other value.  The expected plans are written out from
+    the launch traces of the commit that introduced the function (`runtime.LaunchProfiler` labels per stack, size and seam,
+    identical before and after), not from the function."""
+    from dataclasses import replace
+    from isp_tts_amd.modules.transformer.plan import Form, Hand, Next, Plan, Qkv, SEAMS, select_plan
+    f32, bf16, f16 = torch.float32, torch.bfloat16, torch.float16
+    ROWS = (127, 128, 6400, 8191, 8192, 16383, 16384, 16385, 32768)
+    stacks = {"encoder / decoder": (dict(dim=384, heads=6, out_dim=384, inner=1536, plain_norms=True), 3),
+              "embedding": (dict(dim=256, heads=4, out_dim=256, inner=1024, plain_norms=True), 1),
+              "flow predictor": (dict(dim=256, heads=4, out_dim=256, inner=1024, plain_norms=False), 3)}
+
+    def walk(name, cdt, rows, seams, final):
+        facts, depth = stacks[name]
+        plans, prev = [], Hand.NONE
+        for li in range(depth):
+            last = li == depth - 1
+            p = select_plan(cdt=cdt, rows=rows, bias1=False, bias2=False, gelu=True, dropout=False, prev=prev,
+                            consumer=Next.FINAL if last else Next.LAYER, consumer_dtype=final if last else None,
+                            next_heads=facts["heads"], next_dim=facts["dim"], only_normed=last, seams=seams, **facts)
+            plans.append(p)
+            prev = p.hands
+        return plans
+
+    def same(qkv, form, defer=False, splits=0):                  # nothing handed on: every layer alike
+        return [Plan(qkv, defer, form, splits)] * 3
+
+    def split(splits, proj, final, first=Qkv.NORM_GEMM):         # the combine pass hands the consuming norm's rows on
+        form = Form.SPLIT_PROJ if proj else Form.SPLIT
+        return [Plan(first, proj, form, splits, Hand.ROWS, bf16), Plan(Qkv.HANDED_ROWS, proj, form, splits, Hand.ROWS, bf16),
+                Plan(Qkv.HANDED_ROWS, proj, form, splits, Hand.ROWS, final)]
+
+    def chain(form, hands, handed, final, first=Qkv.LNIN_SELF):  # decoder-sized: one kernel after attention
+        return [Plan(first, True, form, 0, hands), Plan(handed, True, form, 0, hands),
+                Plan(handed, True, Form.ATTN_OUT_FFN_NORM, 0, Hand.ROWS, final, False)]
+
+    seven = same(Qkv.NORM_GEMM, Form.NORM_FFN_GEMMS)
+
+    def dim384(final):            # seams (as keyword set) -> rows -> plans; rows not listed: as with the default seams
+        default = {127: seven, 128: split(8, False, final), 6400: split(4, False, final), 8191: split(4, False, final),
+                   8192: split(4, True, final), 16383: split(2, True, final), 16384: split(2, True, final, Qkv.LNIN_SELF),
+                   16385: chain(Form.ATTN_OUT_FFN_QKV, Hand.QKV, Qkv.HANDED_QKV, final),
+                   32768: chain(Form.ATTN_OUT_FFN_QKV, Hand.QKV, Qkv.HANDED_QKV, final)}
+        big = (16385, 32768)
+        prenorm2 = [Plan(Qkv.LNIN_SELF, False, Form.FFN_PRENORM2, 0, Hand.STATS),
+                    Plan(Qkv.LNIN_STATS, False, Form.FFN_PRENORM2, 0, Hand.STATS), Plan(Qkv.LNIN_STATS, False, Form.FFN_PRENORM2)]
+        no_hand = {r: same(p[0].qkv, p[0].form, p[0].defer_out, p[0].splits) for r, p in default.items() if r < 16385}
+        return {
+            (): default,
+            (("prenorm_fused", False),): {r: same(Qkv.LNIN_SELF, Form.LNIN_GEMM) for r in big},
+            (("lnin_self", False),): {16384: split(2, True, final),
+                                      **{r: chain(Form.ATTN_OUT_FFN_QKV, Hand.QKV, Qkv.HANDED_QKV, final, Qkv.NORM_GEMM) for r in big}},
+            (("next_qkv", False),): {r: chain(Form.ATTN_OUT_FFN_STATS, Hand.STATS, Qkv.LNIN_STATS, final) for r in big},
+            (("proj_ffn", False),): {r: prenorm2 for r in big},
+            (("proj_ffn_split", False),): {8192: split(4, False, final), 16383: split(2, False, final),
+                                           16384: split(2, False, final, Qkv.LNIN_SELF)},
+            (("stats_layernorm", False),): {**no_hand, **{r: same(Qkv.LNIN_SELF, Form.ATTN_OUT_FFN, True) for r in big}},
+            (("fused_min_rows", 1 << 30),): {r: split(1, True, final, Qkv.LNIN_SELF) for r in big},
+            (("prenorm_fused", False), ("stats_layernorm", False), ("lnin_self", False)):
+                {**no_hand, 16384: same(Qkv.NORM_GEMM, Form.SPLIT_PROJ, True, 2),
+                 **{r: same(Qkv.NORM_GEMM, Form.NORM_FFN_FUSED) for r in big}},
+            (("proj_ffn", False), ("proj_ffn_split", False), ("next_qkv", False)):
+                {8192: split(4, False, final), 16383: split(2, False, final), 16384: split(2, False, final, Qkv.LNIN_SELF),
+                 **{r: prenorm2 for r in big}},
+            (("lnin_self_min_rows", 0), ("fused_min_rows", 0), ("prenorm_fused", False)):
+                {r: same(Qkv.LNIN_SELF, Form.LNIN_GEMM) for r in ROWS},
+            (("lnin_self_min_rows", 0), ("fused_min_rows", 0), ("prenorm_fused", False), ("lnin_self", False)):
+                {r: same(Qkv.NORM_GEMM, Form.NORM_FFN_FUSED) for r in ROWS},
+        }
+
+    def dim256(adaptive):         # one embedding layer (first and last), three adaptive flow-predictor layers
+        n = 3 if adaptive else 1
+        small = [Plan(Qkv.NORM_GEMM, False, Form.NORM_FFN_GEMMS)] * n
+        default = {r: small for r in ROWS}
+        if adaptive:
+            default.update({r: [Plan(Qkv.NORM_GEMM, False, Form.NORM_FFN_FUSED)] * 3 for r in (16385, 32768)})
+            return {(): default, (("fused_min_rows", 1 << 30),): {r: small for r in (16385, 32768)},
+                    **{((k, False),): {} for k in ("prenorm_fused", "lnin_self", "next_qkv", "proj_ffn", "proj_ffn_split",
+                                                   "stats_layernorm")}}
+        default.update({16384: [Plan(Qkv.LNIN_SELF, False, Form.NORM_FFN_GEMMS)],
+                        16385: [Plan(Qkv.LNIN_SELF, False, Form.FFN_PRENORM)], 32768: [Plan(Qkv.LNIN_SELF, False, Form.FFN_PRENORM)]})
+        big = (16385, 32768)
+        return {(): default,
+                (("prenorm_fused", False),): {r: [Plan(Qkv.LNIN_SELF, False, Form.LNIN_GEMM)] for r in big},
+                (("lnin_self", False),): {16384: small, **{r: [Plan(Qkv.NORM_GEMM, False, Form.FFN_PRENORM)] for r in big}},
+                (("fused_min_rows", 1 << 30),): {r: [Plan(Qkv.LNIN_SELF, False, Form.NORM_FFN_GEMMS)] for r in big},
+                **{((k, False),): {} for k in ("next_qkv", "proj_ffn", "proj_ffn_split", "stats_layernorm")}}
+
+    checked = 0
+    for final in (f32, bf16):
+        tables = {"encoder / decoder": dim384(final), "embedding": dim256(False), "flow predictor": dim256(True)}
+        for name, table in tables.items():
+            depth = stacks[name][1]
+            for moved, changed in table.items():
+                seams = replace(SEAMS, **dict(moved))
+                for rows in ROWS:
+                    want = changed.get(rows, table[()][rows])
+                    assert walk(name, bf16, rows, seams, final) == want[:depth], (name, moved, rows, final)
+                    # the exact-fp32 and the split-fp16 paths fold nothing, whatever the seams say
+                    assert walk(name, f32, rows, seams, final) == [Plan(Qkv.NORM_GEMM, False, Form.NORM_FFN_GEMMS)] * depth
+                    assert walk(name, f16, rows, seams, final) == [Plan(Qkv.NORM_GEMM, False, Form.SPLIT_FP16)] * depth
+                    checked += 1
+    assert checked == 2 * 9 * (12 + 8 + 8)
+    # the split count of the benchmark's text encoder (6,400 rows) and of 32 utterances per GPU in the decoder (16,384 rows)
+    assert tables["encoder / decoder"][()][6400][0].splits == 4 and tables["encoder / decoder"][()][16384][0].splits == 2
