@@ -667,6 +667,44 @@ int32_t ispk_audio_features_f32(const float* audio, int64_t ld_audio, const int6
                                 int64_t table_floats, const int32_t* fb_index, int32_t n_mels, float* mel, int64_t* mel_len, float* pitch, float* energy,
                                 int32_t B, int32_t S, int32_t M, int32_t tau_min, int32_t tau_max, float sample_rate,
                                 float threshold, float pitch_mean, float pitch_std, ispk_stream_t stream);
+/* ispk_resample_f32            data/providers.py:203-212 (AudioProvider): torchaudio.transforms.Resample ("sinc_interp_hann")
+ *                              and the mean over channels, as one polyphase kernel.  With o = orig and n = dest the REDUCED
+ *                              rates (divided by their gcd), output sample m = q n + p of utterance b is
+ *                                sum_{t < T} taps[p][t] * x(q o + first[p] + t - width),  x(i) = mean_c audio[b][c][i] inside
+ *                              [0, audio_len[b]) and 0 outside it (the reference's zero padding of width and width + o), for
+ *                              m < out_len[b] = ceil(n audio_len[b] / o); 0 for out_len[b] <= m < S_out.
+ *   audio, ld_b, ld_c          fp32 [B][C][S] at batch stride ld_b and channel stride ld_c (ignored for C = 1), unit stride on
+ *                              S.  Nothing at or past audio_len[b] is read.  float4 loads when the strides are multiples of 4
+ *                              and the base is 16-byte aligned.
+ *   audio_len                  int64 [B] on the device; a length below 0 or above S counts as 0 (a zero row, out_len 0).
+ *   taps, tap_floats, first    fp32 [n][T] and int32 [n]: phase p's compact run of non-zero taps and the index of its first tap
+ *                              in the dense 2 width + o (data.Resampler builds both in float64, rounded once).  first[p] is
+ *                              device data: it is clamped to [0, 2 width + o - T].  tap_floats = n T <= 12288.
+ *   out, ld_out, out_len       fp32 [B][S_out] at row stride ld_out, S_out = ceil(n S / o), written in full; int64 [B] or NULL.
+ * Refused: a NULL required pointer (-1); n < 1, n > 1024, o < 1, T < 1, T > 2 width + o, B < 1, B > 65535, C < 1, C > 64,
+ * S < 0, S_out != ceil(n S / o), short strides (-2); a tap table above 12288 floats or an output block wider than the
+ * 8184 staged samples (-4).  One launch, ascending tap order, no atomics: repeats and graph replays are bit-identical.
+ *
+ * ispk_feature_stats_f64       data/dataset.py:174-221 (AcousticDataset.compute_stats) with functions.py:27-32 (remove_outliers).
+ *                              For utterance b and feature f (0 pitch, 1 energy), v = x[b][0, mel_len[b]): p25 / p75 the
+ *                              linear-interpolation quantiles at q (n - 1) of the sorted values, kept where
+ *                              p25 - 1.5 IQR < v < p75 + 1.5 IQR (strict) and, for pitch, v > 0; any NaN in v keeps nothing.
+ *   pitch, energy              fp32 [B][M] at row strides ld_pitch, ld_energy >= M; M <= 4096.
+ *   mel_len                    int64 [B] on the device; a length below 0 or above M counts as 0.
+ *   partial                    float64 [B][2][5]: (count, mean, M2, min, max) of the kept values of each (utterance, feature),
+ *                              (0, 0, 0, +inf, -inf) when nothing is kept.  Quantiles, bounds and sums are float64.
+ *   state                      float64 [2][5], the running pooled (count, mean, M2, min, max) per feature: the partials are
+ *                              folded into it in utterance order with Chan's merge.  reset != 0 starts from the empty state
+ *                              instead of reading it; B = 0 with reset only writes the empty state.
+ * Refused: NULL state, or another NULL pointer with B > 0 (-1); B < 0, B > 65535, M < 0, M > 4096, short row strides (-2).
+ * Two launches, fixed-order sums, no atomics, no host read. */
+int32_t ispk_resample_f32(const float* audio, int64_t ld_b, int64_t ld_c, const int64_t* audio_len, const float* taps,
+                          int64_t tap_floats, const int32_t* first, float* out, int64_t ld_out, int64_t* out_len, int32_t B,
+                          int32_t C, int32_t S, int32_t S_out, int32_t orig, int32_t dest, int32_t width, int32_t T,
+                          ispk_stream_t stream);
+int32_t ispk_feature_stats_f64(const float* pitch, int64_t ld_pitch, const float* energy, int64_t ld_energy,
+                               const int64_t* mel_len, double* partial, double* state, int32_t B, int32_t M, int32_t reset,
+                               ispk_stream_t stream);
 /* Vocos vocoder (mel variant, VocosBackbone + ISTFTHead, padding "same", n_fft 1024, hop 256; isp_tts_amd/vocoder.py): the
  * three kernels besides ispk_gemm_* and ispk_layernorm_*.  Utterance b is frames [0, len_b) of [B][.][T] rows, len_b =
  * mel_len[b] (mel_len NULL: every utterance has all T frames).  A device mel_len outside [0, T] counts as 0: zero rows,

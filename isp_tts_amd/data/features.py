@@ -7,7 +7,7 @@ dataset.py:152 and `AcousticCollator` (data/collator.py:27-95).
 no host read, so it can run inside a captured training step (train.GraphedTrainStep(..., features=)).  Per utterance the
 result is the reference's providers on that utterance alone, unpadded, then collated.  The filterbank the reference takes
 from torchaudio.functional.melscale_fbanks is restated below from torchaudio's documented definition (torchaudio is not a
-dependency).  Decoding and resampling stay on the host (AudioProvider).
+dependency).  Decoding stays on the host (AudioProvider); data.Resampler resamples on the device.
 """
 from __future__ import annotations
 
@@ -214,6 +214,13 @@ class AcousticFeatures:
                    f_max=None if ms.get("f_max", 8000.0) is None else float(ms.get("f_max", 8000.0)), pitch=pitch is not None,
                    pitch_mean=float(pstats.get("mean", 0.0)), pitch_std=float(pstats.get("std", 1.0)),
                    energy=_section(d, "energy", d) is not None, mel_sample_rate=int(ms.get("sample_rate", sr)), **kw)
+
+    def set_pitch_stats(self, mean: float, std: float) -> None:
+        """The dataset's pitch mean / std (e.g. DatasetStats.result().pitch) for the normalisation.  Both are plain arguments
+        of the launch: no table is rebuilt.  (A graph captured earlier keeps the values it was captured with.)"""
+        if float(std) == 0.0:
+            raise ValueError("pitch std is 0")
+        self.pitch_mean, self.pitch_std = float(mean), float(std)
 
     def device_tables(self, device) -> tuple[Tensor, Tensor]:
         """(tables, fb_index) on `device`, copied once per device (before, not inside, a graph capture)."""

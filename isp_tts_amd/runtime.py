@@ -115,6 +115,8 @@ SIGNATURES = {
                                   _I32, _I32, _I32, _I32, _P],
     "ispk_audio_features_f32": [_P, _I64, _P, _P, _I64, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F32, _F32, _F32,
                                 _F32, _P],
+    "ispk_resample_f32": [_P, _I64, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "ispk_feature_stats_f64": [_P, _I64, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_aligner_scores_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_masked_instnorm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_soft_average_bwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P],
@@ -1738,6 +1740,71 @@ def audio_features(audio: Tensor, audio_len: Tensor, tables: Tensor, fb_index: O
             audio.data_ptr(), audio.stride(0), audio_len.data_ptr(), tables.data_ptr(), tables.numel(), _ptr(fb_index), n_mels, _ptr(mel),
             _ptr(mel_len), _ptr(pitch), _ptr(energy), B, S, M if M is not None else feature_frames(S), tau_min, tau_max,
             sample_rate, threshold, pitch_mean, pitch_std, _stream())
+
+
+def resampled_samples(samples: int, orig: int, dest: int) -> int:
+    """ceil(dest * samples / orig): the output length of `samples` input samples at the reduced rates orig -> dest."""
+    return (samples * dest + orig - 1) // orig
+
+
+def resample(audio: Tensor, audio_len: Tensor, taps: Tensor, first: Tensor, orig: int, dest: int, width: int,
+             out: Optional[Tensor] = None, out_len: Optional[Tensor] = None):
+    """ispk_resample_f32, one launch, no host read: fp32 audio [B, S] or [B, C, S] (unit stride on S) with int64 lengths
+    [B] -> (fp32 [B, ceil(dest S / orig)], int64 [B]); several channels are averaged.  `orig`, `dest` are the reduced rates,
+    taps fp32 [dest, T] / first int32 [dest] the compact polyphase table (data.Resampler builds it)."""
+    _dev(audio, audio_len, taps, first, out, out_len)
+    if audio.dtype != torch.float32 or audio.ndim not in (2, 3) or audio.stride(-1) != 1:
+        raise ValueError(f"audio: fp32 [B, S] or [B, C, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} "
+                         f"strides {tuple(audio.stride())}")
+    B, S = audio.shape[0], audio.shape[-1]
+    C = audio.shape[1] if audio.ndim == 3 else 1
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    assert taps.dtype == torch.float32 and taps.ndim == 2 and taps.is_contiguous() and taps.shape[0] == dest
+    assert first.dtype == torch.int32 and first.shape == (dest,) and first.is_contiguous()
+    S_out = resampled_samples(S, orig, dest)
+    if out is None:
+        out = torch.empty((B, S_out), dtype=torch.float32, device=audio.device)
+    if out_len is None:
+        out_len = torch.empty((B,), dtype=torch.int64, device=audio.device)
+    if out.dtype != torch.float32 or out.shape != (B, S_out) or out.stride(1) != 1:
+        raise ValueError(f"out: fp32 [{B}, {S_out}] with unit stride on the samples, got {out.dtype} {tuple(out.shape)}")
+    if out_len.dtype != torch.int64 or out_len.shape != (B,) or not out_len.is_contiguous():
+        raise ValueError(f"out_len: contiguous int64 [{B}], got {out_len.dtype} {tuple(out_len.shape)}")
+    if B == 0:
+        return out, out_len
+    _launch("resample_kernel", 2.0 * taps.shape[1] * B * S_out, 4.0 * (B * C * S + B * S_out), lib().ispk_resample_f32,
+            audio.data_ptr(), audio.stride(0), audio.stride(1) if audio.ndim == 3 else 0, audio_len.data_ptr(),
+            taps.data_ptr(), taps.numel(), first.data_ptr(), out.data_ptr(), out.stride(0), out_len.data_ptr(), B, C, S, S_out,
+            orig, dest, width, taps.shape[1], _stream())
+    return out, out_len
+
+
+STATS_MAX_FRAMES = 4096    # ispk_feature_stats_f64 sorts an utterance in LDS
+
+
+def feature_stats(pitch: Optional[Tensor], energy: Optional[Tensor], mel_len: Optional[Tensor], partial: Optional[Tensor],
+                  state: Tensor, reset: bool = False) -> None:
+    """ispk_feature_stats_f64, a launch pair, no host read: the per-utterance outlier-filtered (count, mean, M2, min, max) of
+    pitch / energy fp32 [B, M] into partial float64 [B, 2, 5], folded in utterance order into state float64 [2, 5].  With
+    pitch None (and reset) it only writes the empty state."""
+    _dev(pitch, energy, mel_len, partial, state)
+    assert state.dtype == torch.float64 and state.shape == (2, 5) and state.is_contiguous()
+    if pitch is None:
+        _launch("stats_fold_kernel", 0.0, 80.0, lib().ispk_feature_stats_f64, None, 0, None, 0, None, None, state.data_ptr(),
+                0, 0, int(reset), _stream())
+        return
+    for name, t in (("pitch", pitch), ("energy", energy)):
+        if t.dtype != torch.float32 or t.ndim != 2 or t.stride(1) != 1 or t.shape != pitch.shape:
+            raise ValueError(f"{name}: fp32 {tuple(pitch.shape)} with unit stride on the frames, got {t.dtype} {tuple(t.shape)} "
+                             f"strides {tuple(t.stride())}")
+    B, M = pitch.shape
+    if mel_len.dtype != torch.int64 or mel_len.shape != (B,) or not mel_len.is_contiguous():
+        raise ValueError(f"mel_len: contiguous int64 [{B}], got {mel_len.dtype} {tuple(mel_len.shape)}")
+    assert partial.dtype == torch.float64 and partial.shape == (B, 2, 5) and partial.is_contiguous()
+    _launch("feature_stats_kernel", 0.0, 8.0 * B * M, lib().ispk_feature_stats_f64, pitch.data_ptr(), pitch.stride(0),
+            energy.data_ptr(), energy.stride(0), mel_len.data_ptr(), partial.data_ptr(), state.data_ptr(), B, M, int(reset),
+            _stream())
 
 
 def flow_loss_bwd(pred_raw: Tensor, flow: Tensor, mask: Tensor, grad_out: float = 1.0) -> Tensor:

@@ -327,3 +327,109 @@ def make_vocoder_mel(B: int, n_mels: int, T: int, seed: int = SEED) -> torch.Ten
     x = g.standard_normal((B, n_mels, T + 4)) * 1.5
     x = (x[..., :-4] + x[..., 1:-3] + x[..., 2:-2] + x[..., 3:-1] + x[..., 4:]) / 5 * 2.0
     return torch.from_numpy((x - 4.5 + np.linspace(1.5, -1.5, n_mels)[None, :, None]).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------------- dataset statistics
+# Batches for data.DatasetStats (tests/golden/dataset_stats.npz holds the reference's results on them): pitch in Hz as the
+# extractor delivers it with mean 0 / std 1 - the discrete values fl(fl(1 / tau) * 22050), tau in 27 .. 524, 0 on unvoiced
+# frames and on the trailing frame of dataset.py:152 - and a smooth positive energy.
+STATS_CASES = ("voices", "mostly_unvoiced", "constant", "single_frame", "nan", "empty_len")
+STATS_MAX_FRAMES = 1723          # the data bound of the recipe (441,088 samples at hop 256)
+
+
+def stats_bounds(v: np.ndarray):
+    """float64 (p25, p75, lower, upper) of remove_outliers (functions.py:27-32) on one utterance's values: the
+    linear-interpolation quantiles at q (n - 1) of the sorted values and the 1.5 IQR fences."""
+    s = np.sort(v.astype(np.float64))
+    n = len(s)
+
+    def quant(r4):                      # position r4 / 4
+        lo = r4 // 4
+        return s[lo] + 0.25 * (r4 % 4) * (s[min(lo + 1, n - 1)] - s[lo])
+
+    p25, p75 = quant(n - 1), quant(3 * (n - 1))
+    return p25, p75, p25 - 1.5 * (p75 - p25), p75 + 1.5 * (p75 - p25)
+
+
+def stats_margin_ok(v: np.ndarray) -> bool:
+    """Whether the keep / drop decision of every value is the same in fp32 and float64 arithmetic: IQR == 0 (the fences are
+    exact in any precision), or no value within 2^-20 (|p25| + |p75|) of a fence."""
+    if len(v) == 0 or np.isnan(v).any():
+        return True
+    p25, p75, lower, upper = stats_bounds(v)
+    if p75 == p25:
+        return True
+    eps = 2.0 ** -20 * (abs(p25) + abs(p75))
+    x = v.astype(np.float64)
+    return bool((np.abs(x - lower) > eps).all() and (np.abs(x - upper) > eps).all())
+
+
+def _stats_utterance(g: np.random.Generator, frames: int, unvoiced: float):
+    """One utterance: (pitch fp32 [frames], energy fp32 [frames]).  `unvoiced`: the fraction of unvoiced frames, in runs."""
+    f32 = np.float32
+    t = np.arange(frames)
+    tau = g.uniform(70.0, 260.0) * np.exp(0.25 * np.sin(2 * np.pi * t / g.uniform(40.0, 160.0) + g.uniform(0, 2 * np.pi))
+                                          + 0.02 * np.cumsum(g.standard_normal(frames)) / np.sqrt(np.maximum(t, 1)))
+    tau = np.clip(np.rint(tau), 27, 524)
+    jumps = g.random(frames) < 0.02                                 # octave errors: half or double the lag
+    tau = np.where(jumps, np.clip(np.where(g.random(frames) < 0.5, np.rint(tau / 2), tau * 2), 27, 524), tau)
+    hz = (f32(1) / tau.astype(f32)) * f32(22050)
+    voiced = np.ones(frames, dtype=bool)
+    want = int(round(unvoiced * frames))
+    while frames and (~voiced).sum() < want:
+        a = int(g.integers(0, frames))
+        voiced[a:a + int(g.integers(1, 12))] = False
+    if want < frames:                                               # trim the runs back to exactly `want` unvoiced frames
+        off = np.flatnonzero(~voiced)
+        voiced[off[want:]] = True
+    pitch = np.where(voiced, hz, f32(0)).astype(f32)
+    if frames:
+        pitch[-1] = 0                                               # the pad of dataset.py:152
+    energy = 3.0 + 1.2 * np.sin(2 * np.pi * t / g.uniform(30.0, 90.0) + g.uniform(0, 2 * np.pi)) + 0.15 * g.standard_normal(frames)
+    energy = np.where(g.random(frames) < 0.01, energy + g.uniform(4.0, 8.0), energy)      # a few bursts above the fence
+    return pitch, np.maximum(energy, 0.05).astype(f32)
+
+
+def make_stats_case(case: str, seed: int = SEED) -> dict[str, torch.Tensor]:
+    """{"pitch": fp32 [B, M], "energy": fp32 [B, M], "mel_len": int64 [B]}, zero past each mel_len.  Every utterance satisfies
+    stats_margin_ok (one that does not is redrawn from the same stream), so kept counts are comparable exactly across
+    precisions.  "voices": B = 64, lengths up to 1,723, 5-60 % unvoiced; "mostly_unvoiced": 75 % or more unvoiced (no pitch is
+    kept) beside one ordinary utterance; "constant": a constant energy, a constant pitch, both; "single_frame": mel_len 1;
+    "nan": a NaN in one utterance's pitch and in another's energy; "empty_len": mel_len 0."""
+    if case not in STATS_CASES:
+        raise ValueError(f"unknown stats case {case!r}")
+    g = _rng(f"stats/{case}", seed)
+    if case == "voices":
+        lens = [STATS_MAX_FRAMES, 2] + [int(v) for v in g.integers(40, STATS_MAX_FRAMES, 62)]
+        unv = [float(v) for v in g.uniform(0.05, 0.6, 64)]
+    elif case == "mostly_unvoiced":
+        lens, unv = [400, 401, 333, 512, 250], [0.75, 0.8, 0.95, 1.0, 0.3]
+    elif case == "constant":
+        lens, unv = [300, 200, 150, 280], [0.2, 0.0, 0.0, 0.4]
+    elif case == "single_frame":
+        lens, unv = [1, 1, 240], [0.0, 0.0, 0.3]
+    elif case == "nan":
+        lens, unv = [200, 300, 260], [0.3, 0.2, 0.25]
+    else:
+        lens, unv = [0, 180, 0], [0.0, 0.3, 0.0]
+    M = max(lens)
+    pitch, energy = np.zeros((len(lens), M), np.float32), np.zeros((len(lens), M), np.float32)
+    for b, (n, u) in enumerate(zip(lens, unv)):
+        for _ in range(16):
+            p, e = _stats_utterance(g, n, u)
+            if case == "constant":
+                if b in (0, 2):
+                    e[:] = np.float32(2.5)
+                if b in (1, 2):
+                    p[:] = np.float32(1) / np.float32(110) * np.float32(22050)       # (no trailing 0 either: IQR 0 at 200.45 Hz)
+            if case == "nan" and b == 0:
+                p[n // 3] = np.nan
+            if case == "nan" and b == 1:
+                e[n // 2] = np.nan
+            if stats_margin_ok(p) and stats_margin_ok(e):
+                break
+        else:
+            raise AssertionError(f"stats/{case}[{b}]: no draw with a safe margin")
+        pitch[b, :n], energy[b, :n] = p, e
+    return {"pitch": torch.from_numpy(pitch), "energy": torch.from_numpy(energy),
+            "mel_len": torch.tensor(lens, dtype=torch.int64)}
