@@ -633,7 +633,50 @@ int32_t ispk_acoustic_metrics_f32(const float* mel_out, int64_t out_sb, int64_t 
                                   const float* attn_soft, int64_t attn_sb, int64_t attn_st, const float* dct, float* workspace,
                                   int64_t workspace_floats, float* out, int32_t B, int32_t C, int32_t T, int32_t L,
                                   int32_t n_mfcc, ispk_stream_t stream);
-/* ispk_audio_features_f32      data/providers.py:35-64 (SpectrogramProvider), :70-111 (MelScaleProvider with
+/* ispk_dtw_f32                 Dynamic time warping of a given cost matrix (no counterpart in the reference, whose evaluator is
+ *                              teacher-forced only): D[0][0] = c[0][0], D[i][j] = c[i][j] + min(D[i-1][j-1], D[i-1][j],
+ *                              D[i][j-1]); ties go to the diagonal, then to (i-1, j), then to (i, j-1); the backtrace runs from
+ *                              (n_len - 1, m_len - 1) to (0, 0).
+ *   cost                       fp32 element (b, i, j) at b*cost_sb + i*cost_sn + j, i < N, j < M.  Only the cells i < n_len[b],
+ *                              j < m_len[b] are read.
+ *   n_len, m_len               int64 [B].  1 <= n_len <= N and 1 <= m_len <= M are required; the lengths are device data, so a
+ *                              violation cannot be refused by the return code: that item gets total = NaN, steps = 0 and a
+ *                              path of -1.
+ *   total, steps               fp32 [B] D[n_len-1][m_len-1] and int32 [B] the number K of cells on the path.
+ *   path                       int16 [B][N + M - 1][2] or NULL: the cells (i, j) from (0, 0) to (n_len-1, m_len-1), -1 past K.
+ *   workspace                  16-byte aligned, >= B * 256 * ((M + 255) * R + ceil(M * R / 16)) floats with R = 1, 2, 4, 8 for
+ *                              N <= 256, 512, 1024, 2048: a skewed copy of the cost matrix (one row of it is what one wave reads
+ *                              in one step) and the 2-bit back-pointers.
+ * Refused (nothing written): a NULL required pointer, B < 0 or B > 65535, N or M outside 1 .. 2048, a short or misaligned
+ * workspace (-3).  B = 0 is a no-op.  Two launches, one workgroup per item in the second; bit-identical across calls and
+ * graph replays.
+ *
+ * ispk_mcd_dtw_f32             Scores free-running synthesis against a recording: MCD after DTW, and F0 RMSE / voicing error
+ *                              along the same path.  c[i][j] = |cep_out[i] - cep_target[j]| over the cepstral coefficients
+ *                              1 .. n_mfcc - 1 (cep = mel frame . dct, computed once per frame), then ispk_dtw_f32's recurrence.
+ *   mel_out, mel_target        as for ispk_acoustic_metrics_f32 (element (b, c, t) at b*sb + c*sc + t*st), with N frames of
+ *                              the output and M frames of the target; dct [C][n_mfcc].
+ *   pitch_out, pitch_target    fp32 Hz, 0 = unvoiced, frame i of item b at b*sb + i; both or neither.
+ *   per_item                   fp32 [4][B]: [0] mcd_dtw = 10 sqrt(2) / ln 10 * total / K; [1] f0_rmse_cents = the RMS of
+ *                              1200 log2(f_i / f_j) over the path's pairs with both frames voiced, NaN when there is none;
+ *                              [2] vuv_error = the share of the path's pairs whose voicing differs; [3] length_ratio =
+ *                              n_len / m_len.  Rows 1 and 2 are written only with the pitch tracks.  An item whose lengths
+ *                              are out of range gets NaN in every written row.
+ *   means                      fp32 [4]: the plain batch means of the rows of per_item that were written.
+ *   cost_out                   NULL, or fp32 [B][N][M]: the cost matrix as the dynamic programme saw it, cells i < n_len, j < m_len
+ *                              only (ispk_dtw_f32 on it gives the path the scores were taken along).
+ *   workspace                  16-byte aligned: ispk_dtw_f32's, plus B (N + M) kp floats of cepstra with kp = n_mfcc - 1 rounded
+ *                              up to 4, plus 2 B floats.  The costs go straight into the skewed layout.
+ * Refused as ispk_dtw_f32, and C < 1, C > 128, n_mfcc < 1 or n_mfcc > C.  Four launches. */
+int32_t ispk_dtw_f32(const float* cost, int64_t cost_sb, int64_t cost_sn, const int64_t* n_len, const int64_t* m_len,
+                     float* total, int32_t* steps, int16_t* path, float* workspace, int64_t workspace_floats, int32_t B,
+                     int32_t N, int32_t M, ispk_stream_t stream);
+int32_t ispk_mcd_dtw_f32(const float* mel_out, int64_t out_sb, int64_t out_sc, int64_t out_st, const float* mel_target,
+                         int64_t tgt_sb, int64_t tgt_sc, int64_t tgt_st, const float* dct, const int64_t* n_len,
+                         const int64_t* m_len, const float* pitch_out, int64_t pitch_out_sb, const float* pitch_target,
+                         int64_t pitch_target_sb, float* workspace, int64_t workspace_floats, float* per_item, float* means,
+                         float* cost_out, int32_t B, int32_t C, int32_t N, int32_t M, int32_t n_mfcc, ispk_stream_t stream);
+/* ispk_audio_features_f32     data/providers.py:35-64 (SpectrogramProvider), :70-111 (MelScaleProvider with
  *                              functions.py:19-20), :178-188 (EnergyProvider), :280-348 (PitchProvider, torch-yin, with
  *                              data/pitch.py:17-100), the pitch pad of data/dataset.py:152 and the collator's zero padding
  *                              (data/collator.py:27-95), for n_fft = win_length = 1024, hop 256, pad 384, center=False, power 1.

@@ -9,6 +9,7 @@ is restated below from torchaudio's documented definition (torchaudio is not a d
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import numpy as np
 import torch
@@ -122,6 +123,56 @@ class AcousticModelEvaluator:
             "images/eval/mel_spectrogram": _figure({"target": mel, "predicted": predicted}, title=name, xlabel="Frames",
                                                    ylabel="Channels"),
         }
+
+
+class SynthesisEvaluator:
+    """Objective scores of free-running synthesis (`AcousticModel.infer`, which picks its own durations) against a recording:
+    MCD after dynamic time warping, F0 RMSE in cents and voiced / unvoiced error along the same warping path, and the length
+    ratio.  The reference has no counterpart (its evaluator is teacher-forced); the definitions are include/ispk.h's.
+
+    `evaluator(mel_out, mel_out_len, mel_target, mel_target_len, pitch_out=None, pitch_target=None)` ->
+    {"metrics/mcd_dtw_13", "metrics/f0_rmse_cents", "metrics/vuv_error", "metrics/length_ratio"}: 0-dim fp32 batch means,
+    views of one device buffer written by one ispk_mcd_dtw_f32 call (the F0 keys only with both pitch tracks: fp32 [B, T] in
+    Hz, 0 = unvoiced, what AcousticFeatures gives with pitch_mean=0, pitch_std=1).  `per_item=True`: the [B] vectors instead.
+    The mels may differ in length and follow MCD's layout rule.  No ATen compute op and no host read: capturable."""
+
+    def __init__(self, n_mel_channels: int = 80, n_mfcc: int = 13):
+        self.mcd_evaluator = MCD(n_mel_channels, n_mfcc)
+
+    @torch.no_grad()
+    def __call__(self, mel_out: Tensor, mel_out_len: Tensor, mel_target: Tensor, mel_target_len: Tensor,
+                 pitch_out: Optional[Tensor] = None, pitch_target: Optional[Tensor] = None, per_item: bool = False) -> dict:
+        if (pitch_out is None) != (pitch_target is None):
+            raise ValueError("give both pitch tracks or neither")
+        items, means = runtime.mcd_dtw(mel_out, mel_out_len, mel_target, mel_target_len, self.mcd_evaluator.dct(mel_out.device),
+                                       pitch_out, pitch_target)
+        src = items if per_item else means
+        out = {f"metrics/mcd_dtw_{self.mcd_evaluator.n_mfcc}": src[0]}
+        if pitch_out is not None:
+            out["metrics/f0_rmse_cents"] = src[1]
+            out["metrics/vuv_error"] = src[2]
+        out["metrics/length_ratio"] = src[3]
+        return out
+
+    @torch.no_grad()
+    def score_infer(self, model, inputs, vocoder=None, features=None, per_item: bool = False, **infer_kwargs) -> dict:
+        """`model.infer` on inputs["text"] / ["text_len"] (with ["speaker"] if present; `infer_kwargs` go to it: steps,
+        flow_noise, max_dec_len ...), its mel and dec_lengths scored against inputs["mel"] / ["mel_len"].  With a Vocoder and
+        an AcousticFeatures (pitch in Hz: pitch_mean=0, pitch_std=1) the mel is also vocoded, the waveform's pitch extracted and
+        scored against inputs["pitch_hz"].  Capturable with torch.cuda.graph when `max_dec_len` is given (infer's own rule)."""
+        if (vocoder is None) != (features is None):
+            raise ValueError("give both the vocoder and the feature extractor or neither")
+        if features is not None and (not features.pitch or features.pitch_mean != 0.0 or features.pitch_std != 1.0):
+            raise ValueError("the feature extractor must deliver pitch in Hz (pitch=True, pitch_mean=0, pitch_std=1)")
+        speaker = inputs.get("speaker") if isinstance(inputs, dict) else getattr(inputs, "speaker", None)
+        if speaker is not None:
+            infer_kwargs = {**infer_kwargs, "speaker": speaker}
+        mel, adaptor = model.infer(_field(inputs, "text"), text_lengths=_field(inputs, "text_len"), **infer_kwargs)
+        pitch_out = pitch_target = None
+        if vocoder is not None:
+            audio, audio_len = vocoder(mel, adaptor.dec_lengths)
+            pitch_out, pitch_target = features(audio, audio_len)["pitch"], _field(inputs, "pitch_hz")
+        return self(mel, adaptor.dec_lengths, _field(inputs, "mel"), _field(inputs, "mel_len"), pitch_out, pitch_target, per_item=per_item)
 
 
 def _figure(panels: dict, title=None, xlabel=None, ylabel=None):

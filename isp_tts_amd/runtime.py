@@ -113,6 +113,9 @@ SIGNATURES = {
     "ispk_mel_loss_f32": [_P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _P],
     "ispk_acoustic_metrics_f32": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I32,
                                   _I32, _I32, _I32, _I32, _P],
+    "ispk_dtw_f32": [_P, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P],
+    "ispk_mcd_dtw_f32": [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I32,
+                         _I32, _I32, _I32, _I32, _P],
     "ispk_audio_features_f32": [_P, _I64, _P, _P, _I64, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F32, _F32, _F32,
                                 _F32, _P],
     "ispk_resample_f32": [_P, _I64, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
@@ -1693,6 +1696,92 @@ def acoustic_metrics(mel_out: Optional[Tensor], mel_target: Optional[Tensor], me
             attn_soft.stride(0) if attn_soft is not None else 0, attn_soft.stride(1) if attn_soft is not None else 0,
             _ptr(dct), ws.data_ptr(), ws.numel(), out.data_ptr(), B, C, T, L, n_mfcc, _stream())
     return out
+
+
+DTW_MAX_LEN = 2048     # frames per side of ispk_dtw_f32 / ispk_mcd_dtw_f32
+DTW_LANES = 256        # lanes per item; each owns 1, 2, 4 or 8 rows
+
+
+def dtw_workspace_floats(B: int, N: int, M: int) -> int:
+    """ispk_dtw_f32: per item the skewed copy of the costs ((M + 255) rows of 256 R floats: a row is one step of a wave) and the
+    2-bit back-pointers (per lane, words of 16 / R columns x R rows)."""
+    R = 1 if N <= 256 else (2 if N <= 512 else (4 if N <= 1024 else 8))
+    return B * DTW_LANES * ((M + DTW_LANES - 1) * R + (M * R + 15) // 16)
+
+
+def mcd_dtw_workspace_floats(B: int, N: int, M: int, n_mfcc: int) -> int:
+    """ispk_mcd_dtw_f32: ispk_dtw_f32's, the cepstra of both mels, totals and steps."""
+    kp = (n_mfcc - 1 + 3) // 4 * 4
+    return dtw_workspace_floats(B, N, M) + B * (N + M) * kp + 2 * B
+
+
+def dtw(cost: Tensor, n_len: Tensor, m_len: Tensor, want_path: bool = True):
+    """ispk_dtw_f32.  cost fp32 [B, N, M] (unit stride on M), lengths int64 [B] on the device -> (total fp32 [B], steps int32
+    [B], path int16 [B, N + M - 1, 2] | None): the cells of the warping path from (0, 0), -1 past `steps`.  No host read."""
+    _dev(cost, n_len, m_len)
+    assert cost.dtype == torch.float32 and cost.ndim == 3
+    if cost.stride(2) != 1:
+        cost = cost.contiguous()
+    B, N, M = cost.shape
+    n_len, m_len = n_len.to(torch.int64).contiguous(), m_len.to(torch.int64).contiguous()
+    assert n_len.shape == (B,) and m_len.shape == (B,)
+    total = torch.empty((B,), dtype=torch.float32, device=cost.device)
+    steps = torch.empty((B,), dtype=torch.int32, device=cost.device)
+    path = torch.empty((B, N + M - 1, 2), dtype=torch.int16, device=cost.device) if want_path else None
+    if B == 0:
+        return total, steps, path
+    ws = workspace(cost.device, dtw_workspace_floats(B, N, M))
+    _launch("dtw_kernel", 4.0 * B * N * M, 12.25 * B * N * M, lib().ispk_dtw_f32, cost.data_ptr(), cost.stride(0), cost.stride(1),
+            n_len.data_ptr(), m_len.data_ptr(), total.data_ptr(), steps.data_ptr(), _ptr(path), ws.data_ptr(), ws.numel(), B, N,
+            M, _stream())
+    return total, steps, path
+
+
+def mcd_dtw(mel_out: Tensor, mel_out_len: Tensor, mel_target: Tensor, mel_target_len: Tensor, dct: Tensor,
+            pitch_out: Optional[Tensor] = None, pitch_target: Optional[Tensor] = None, out: Optional[Tensor] = None,
+            cost_out: Optional[Tensor] = None):
+    """ispk_mcd_dtw_f32 -> (per_item fp32 [4, B], means fp32 [4]), two views of ONE device buffer of 4 B + 4 floats (`out`,
+    when given): rows / elements 0 .. 3 are (mcd_dtw, f0_rmse_cents, vuv_error, length_ratio).  mels fp32 [B, C, T] or
+    [B, T, C] under the layout rule of `_mel_strides`, dct fp32 [C, n_mfcc] on the device, lengths int64 [B], pitch fp32
+    [B, >= T] in Hz with 0 = unvoiced (both or neither: without them rows 1 and 2 are not written).  `cost_out`: fp32 [B, N, M]
+    (contiguous) that receives each item's n_len x m_len costs.  No host read.  B = 0 gives NaN means without a launch."""
+    _dev(mel_out, mel_out_len, mel_target, mel_target_len, dct, pitch_out, pitch_target, out, cost_out)
+    assert mel_out.dtype == torch.float32 and mel_target.dtype == torch.float32 and dct.dtype == torch.float32
+    assert mel_out.ndim == 3 and mel_target.ndim == 3 and dct.ndim == 2 and dct.is_contiguous()
+    assert (pitch_out is None) == (pitch_target is None)
+    B = mel_out_len.shape[0]
+    C, n_mfcc = dct.shape
+    m, mt = _mel_strides(mel_out, C), _mel_strides(mel_target, C)
+    if m[0] != C or mt[0] != C or mel_out.shape[0] != B or mel_target.shape[0] != B or mel_target_len.shape[0] != B:
+        raise ValueError(f"mels {tuple(mel_out.shape)} / {tuple(mel_target.shape)} do not match {C} channels and {B} lengths")
+    N, M = m[1], mt[1]
+    if out is None:
+        out = torch.empty((4 * B + 4,), dtype=torch.float32, device=mel_out.device)
+    assert out.dtype == torch.float32 and out.shape == (4 * B + 4,) and out.is_contiguous()
+    per_item, means = out[:4 * B].view(4, B), out[4 * B:]
+    if B == 0:
+        out.fill_(float("nan"))
+        return per_item, means
+    n_len, m_len = mel_out_len.to(torch.int64).contiguous(), mel_target_len.to(torch.int64).contiguous()
+    if pitch_out is not None:
+        assert pitch_out.dtype == torch.float32 and pitch_target.dtype == torch.float32
+        assert pitch_out.ndim == 2 and pitch_target.ndim == 2 and pitch_out.shape[0] == B and pitch_target.shape[0] == B
+        if pitch_out.shape[1] < N or pitch_target.shape[1] < M:
+            raise ValueError(f"pitch tracks {tuple(pitch_out.shape)} / {tuple(pitch_target.shape)} are shorter than the mels")
+        if pitch_out.stride(1) != 1:
+            pitch_out = pitch_out.contiguous()
+        if pitch_target.stride(1) != 1:
+            pitch_target = pitch_target.contiguous()
+    ws = workspace(mel_out.device, mcd_dtw_workspace_floats(B, N, M, n_mfcc))
+    if cost_out is not None:
+        assert cost_out.dtype == torch.float32 and cost_out.shape == (B, N, M) and cost_out.is_contiguous()
+    _launch("mcd_dtw_kernels", 2.0 * B * (N + M) * C * n_mfcc + 3.0 * B * N * M * n_mfcc, 8.25 * B * N * M,
+            lib().ispk_mcd_dtw_f32, mel_out.data_ptr(), m[2], m[3], m[4], mel_target.data_ptr(), mt[2], mt[3], mt[4],
+            dct.data_ptr(), n_len.data_ptr(), m_len.data_ptr(), _ptr(pitch_out),
+            pitch_out.stride(0) if pitch_out is not None else 0, _ptr(pitch_target),
+            pitch_target.stride(0) if pitch_target is not None else 0, ws.data_ptr(), ws.numel(), per_item.data_ptr(),
+            means.data_ptr(), _ptr(cost_out), B, C, N, M, n_mfcc, _stream())
+    return per_item, means
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
