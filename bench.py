@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: mel-frames/s of the acoustic-model forward path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W            # starts N fresh worker processes itself when N > 1
+    python bench.py --gpus N --steps K --warmup W            # the headline alone; starts N fresh workers itself when N > 1
+    python bench.py --gpus N --steps K --warmup W --full     # the headline, then everything else this file measures
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                # or under a launcher (RANK / LOCAL_RANK / WORLD_SIZE set)
 
@@ -12,13 +13,15 @@ Workload = BASELINE config 3: B = 64 utterances x 100 phonemes x 512 mel frames,
 are independent end to end, so the only exchange is ONE RCCL gather of the mel outputs per step, inside the timed
 region.  `value` is measured with ONE batch in flight per GPU; the double-buffered figure is a named extra.
 
-Rank 0 prints ONE JSON line: the contract fields plus
+A plain run does only what the headline needs: set up, warm up, time the K steps, write `--dump-outputs`, print the line.
+Rank 0 prints ONE JSON line: the contract fields and, with `--full` only, after the same headline measurement,
   "roofline"      the dominant kernel of the step (HIP events on the launch stream): achieved algorithmic FLOP/s or B/s
                   against the gfx950 peak, PMC traffic from profiles/, every other kernel under "kernels";
   "cpu_baseline"  the oracle (CPU restatement of the reference's algorithm, oracle/) on this host's cores, N = 1 only;
   extras          two_batches_in_flight, strong_scaling (N > 1), config4 (B = 256 variable-length, sharded by cost,
                   gathered and un-permuted), and at N = 1: infer_steps4, config2_fp32, f32_parity_path,
                   fp32_alignment_chain.
+`--no-extras`, `--extras NAMES`, `--no-kernel-events` and `--no-cpu-baseline` narrow what `--full` adds.
 No work is skipped in any timed region; synthetic weights and inputs (isp_tts_amd.synth).
 """
 from __future__ import annotations
@@ -64,15 +67,19 @@ def parse(argv=None):
     ap.add_argument("--in-flight", type=int, default=1,
                     help="batches in flight per GPU for the headline value (graph instances replayed round-robin on their "
                          "own streams); the 2-in-flight figure is always reported as an extra")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline measurement (+ roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: the per-kernel roofline object, the CPU baseline, "
+                         "the other precisions, sizes and configurations, the accuracy figures and the training step "
+                         "(off by default: a plain run times the headline and prints its line)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the headline measurement (+ roofline)")
     ap.add_argument("--three-graphs", action="store_true",
                     help="headline step as three HIP graphs on two streams (graph.SegmentedForward) instead of one")
     ap.add_argument("--linear-graph", action="store_true",
                     help="headline graph without the forward's side-stream branches (experiments: graph turnaround)")
-    ap.add_argument("--extras", default="", help="comma-separated names: run only these extra lines (default: all)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP events (no roofline object)")
+    ap.add_argument("--extras", default="", help="with --full, comma-separated names: run only these extra lines (default: all)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: skip per-launch HIP events (no roofline object)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=64, help="utterances in the CPU-baseline sample")
     ap.add_argument("--cpu-iters", type=int, default=5)
     ap.add_argument("--c4-batch", type=int, default=256, help="config 4: utterances in total")
@@ -86,6 +93,8 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.extras and not args.full:
+        ap.error("--extras names lines of the full run: give --full with it")
     return args
 
 
@@ -464,7 +473,7 @@ def worker(args) -> int:
         }
 
     # ---------------------------------------------------------------------------------------------- roofline (rank 0)
-    if rank == 0 and not args.no_kernel_events:
+    if rank == 0 and args.full and not args.no_kernel_events:
         # graph replays cannot carry timing events: time the SAME kernels, launched eagerly, right after the timed region
         prof = runtime.LaunchProfiler()
         runtime.set_profiler(prof)
@@ -478,6 +487,9 @@ def worker(args) -> int:
                                       "(the timed region replays them as one HIP graph)")
     if use_dist:
         dist.barrier()
+
+    # everything below is what --full adds to the line; a plain run goes straight on to printing it
+    extras = args.full and not args.no_extras
 
     def extra(name, fn):
         """Extras never take the headline down: an exception is reported in place of the figure.  (Every rank runs the
@@ -495,7 +507,7 @@ def worker(args) -> int:
         torch.cuda.synchronize()
         gc.collect()
 
-    if not args.no_extras and not args.no_graph:
+    if extras and not args.no_graph:
         # ------------------------------------------------------------------------- two batches in flight (all ranks)
         lanes = pipes = step = None          # release the headline's graph instance before the next capture
         torch.cuda.synchronize()
@@ -612,7 +624,7 @@ def worker(args) -> int:
         extra("config4", config4)
 
     # ---------------------------------------------------------------------------------------------- N = 1 extras
-    if world == 1 and rank == 0 and not args.no_extras and not args.no_graph:
+    if world == 1 and rank == 0 and extras and not args.no_graph:
         def timed_graph(g, n):
             g.replay()
             torch.cuda.synchronize()
@@ -841,7 +853,7 @@ def worker(args) -> int:
                 line["gpu_over_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
 
     # ---------------------------------------------------------------------------------------------- training step (all ranks)
-    if not args.no_extras:
+    if extras:
         def train_line():
             """one optimizer step of BASELINE config 5 under the reference's total loss (mel + flow + CTC +
             binarisation, loss.py:140-182) over every parameter of the model - text embedding, TextEncoder, aligner

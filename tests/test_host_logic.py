@@ -513,6 +513,19 @@ def test_bench_rejects_a_step_count_below_one():
             bench.parse(argv)
 
 
+def test_bench_full_is_off_by_default_and_the_narrowing_options_belong_to_it():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` is the headline alone: `--full` is off unless given, and `--extras`,
+    which picks among the lines only a full run has, is refused without it."""
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert plain.full is False and plain.dump_outputs is None
+    full = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--extras", "train_step", "--no-cpu-baseline"])
+    assert full.full is True and full.extras == "train_step" and full.no_cpu_baseline
+    assert bench.parse(["--no-extras", "--no-kernel-events"]).full is False      # harmless without --full
+    with pytest.raises(SystemExit):
+        bench.parse(["--extras", "train_step"])
+
+
 def test_layer_plan_of_every_stack_position_size_and_seam():
     """`plan.select_plan`, the one place that chooses a transformer layer's kernels, for the first, a middle and the last
     layer of every stack the model has (text encoder / decoder: dim 384, 6 heads; embedding stack: dim 256, ONE layer; flow
