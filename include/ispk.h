@@ -748,6 +748,57 @@ int32_t ispk_resample_f32(const float* audio, int64_t ld_b, int64_t ld_c, const 
 int32_t ispk_feature_stats_f64(const float* pitch, int64_t ld_pitch, const float* energy, int64_t ld_energy,
                                const int64_t* mel_len, double* partial, double* state, int32_t B, int32_t M, int32_t reset,
                                ispk_stream_t stream);
+/* Audio conditioning (no counterpart in the reference): silence trimming, ITU-R BS.1770-4 loudness and PCM16, on a padded
+ * mono batch fp32 [B][S] at row stride ld_audio >= S with int64 audio_len [B] on the device (a length below 0 or above S
+ * counts as 0).  Nothing at or past audio_len[b] is read.  float4 loads when the row stride is a multiple of 4 and the
+ * base is 16-byte aligned.  B = 0 is a no-op; B > 65535 and S > 2^24 are refused (-2).
+ *
+ * ispk_audio_measure_f64     bounds int64 [B][2] = (start, end), loudness float64 [B] (LKFS, -inf when no block passes the
+ *                            gates), peak fp32 [B] = max |x| over [start, end), gain fp32 [B].
+ *   Trim                     frames t = 0 .. ceil(len / 256) - 1, frame t = x[256 t, 256 t + 1024) cut at len, p_t = (sum of
+ *                            squares) / 1024 in float64; active when p_t > thr, thr = trim_threshold * max_t p_t (trim_mode 1)
+ *                            or trim_threshold itself (trim_mode 2: the caller's constant reference, already multiplied in).
+ *                            No active frame: start = end = 0.  Otherwise, f and l the first and last active frames,
+ *                            start = max(0, 256 (f - pad_frames)), end = min(len, 256 (l + pad_frames) + 1024).
+ *                            trim_mode 0: start = 0, end = len.
+ *   Loudness                 of x[start, end) with zero filter state at start.  table float64 [152]: [0, 7) = b0, b1, b2, a1,
+ *                            a2 of the K-weighting shelf and a1, a2 of its high-pass (numerator 1, -2, 1) at sample_rate, [7]
+ *                            unused, then nine row-major 4 x 4 matrices A^(32 2^k), k = 0 .. 8, A the state transition of the
+ *                            cascade in transposed direct form II (states: shelf s1, s2, high-pass s1, s2), made by the host
+ *                            in float64 (data.AudioConditioner).  Blocks of 4 steps of sample_rate / 10 samples, one every
+ *                            step, only those wholly inside [start, end); z_j = the block's mean square, l_j = -0.691 +
+ *                            10 log10 z_j; gates l_j > -70 and l_j > -0.691 + 10 log10(mean z over the first gate's blocks)
+ *                            - 10; L = -0.691 + 10 log10(mean z over the blocks passing both).  Filter, sums and gates are
+ *                            float64.
+ *   Gain                     gain_mode 0: 1.  Otherwise 10^((target_lufs - L) / 20), capped at peak_limit / peak when
+ *                            peak > 0; 1 when L = -inf.
+ *   workspace                8-byte aligned, >= 2 (B (NH + 1041 W + NS)) floats with W = max(1, ceil(S / 8192)), NH =
+ *                            max(1, ceil(S / 256)), NS = S / step + 1 (runtime.audio_measure_workspace_floats): 256-sample
+ *                            square sums, the final state of every 32-sample chunk and 8,192-sample segment, per-segment step
+ *                            partials and peaks, step sums.
+ * Refused: a NULL pointer (-1); sample_rate % 10 != 0, a table of another size, trim_mode outside 0 .. 2, pad_frames outside
+ * 0 .. 65536, a negative threshold, peak_limit <= 0 with gain_mode (-2); a short or misaligned workspace (-3); sample_rate
+ * outside 8000 .. 768000 (-4).  Three launches.  An item's results depend on that item alone (not on B): every sum runs in
+ * a fixed order, no atomics, no host read - repeated calls and graph replays are bit-identical.
+ *
+ * ispk_audio_apply_f32       out[b][i] = gain[b] * audio[b][start_b + i] (one fp32 product) for i < n_b = min(end_b - start_b,
+ *                            S_out), 0 for n_b <= i < S_out; out_len[b] = n_b (may be NULL).  bounds int64 [B][2] is device
+ *                            data: a pair outside 0 <= start <= end <= S counts as (0, 0).  gain may be NULL (1).  out fp32
+ *                            [B][S_out] at row stride ld_out; it may not overlap audio (-2).  One launch.
+ * ispk_pcm16                 out int16 [B][S] at row stride ld_out: q = clamp(rint(32768 x + d), -32768, 32767) (half to
+ *                            even, a NaN gives 0) for i < audio_len[b], 0 past it.  dither 0: d = 0.  Otherwise the TPDF
+ *                            d = (h(2 i) - h(2 i + 1)) 2^-32, h(k) = mix32(k ^ lo(r)) ^ hi(r) (csrc/dropout.h) with r =
+ *                            splitmix64(splitmix64(seed) + b): a pure function of (seed, b, i), so a captured graph repeats
+ *                            its dither on every replay.  One launch. */
+int32_t ispk_audio_measure_f64(const float* audio, int64_t ld_audio, const int64_t* audio_len, const double* table,
+                               int64_t table_doubles, int64_t* bounds, double* loudness, float* peak, float* gain,
+                               float* workspace, int64_t workspace_floats, int32_t B, int32_t S, int32_t sample_rate,
+                               int32_t trim_mode, double trim_threshold, int32_t pad_frames, int32_t gain_mode,
+                               double target_lufs, double peak_limit, ispk_stream_t stream);
+int32_t ispk_audio_apply_f32(const float* audio, int64_t ld_audio, const int64_t* bounds, const float* gain, float* out,
+                             int64_t ld_out, int64_t* out_len, int32_t B, int32_t S, int32_t S_out, ispk_stream_t stream);
+int32_t ispk_pcm16(const float* audio, int64_t ld_audio, const int64_t* audio_len, int16_t* out, int64_t ld_out, int32_t B,
+                   int32_t S, int32_t dither, uint64_t seed, ispk_stream_t stream);
 /* Vocos vocoder (mel variant, VocosBackbone + ISTFTHead, padding "same", n_fft 1024, hop 256; isp_tts_amd/vocoder.py): the
  * three kernels besides ispk_gemm_* and ispk_layernorm_*.  Utterance b is frames [0, len_b) of [B][.][T] rows, len_b =
  * mel_len[b] (mel_len NULL: every utterance has all T frames).  A device mel_len outside [0, T] counts as 0: zero rows,

@@ -138,12 +138,18 @@ class AudioFrontEnd:
     """Resampler, then AcousticFeatures, as one callable with the interface train.GraphedTrainStep(features=) uses: two
     launches, no ATen compute op, no host read.  Mono [B, S] at the resampler's input rate; S is the INPUT width.
 
-    The returned dict is the extractor's (mel, mel_len, pitch, energy) plus "audio_resampled" / "audio_resampled_len"."""
+    The returned dict is the extractor's (mel, mel_len, pitch, energy) plus "audio_resampled" / "audio_resampled_len".
 
-    def __init__(self, resampler: Resampler, features):
+    With `conditioner` (data.AudioConditioner at the extractor's rate) the order is resample, condition, extract: the
+    extractor sees the trimmed, loudness-normalised audio, which the dict also returns as "audio_conditioned" /
+    "audio_conditioned_len" (four more launches).  Without one nothing changes."""
+
+    def __init__(self, resampler: Resampler, features, conditioner=None):
         if resampler.new_freq != features.sample_rate:
             raise ValueError(f"the resampler delivers {resampler.new_freq} Hz, the extractor expects {features.sample_rate} Hz")
-        self.resampler, self.features = resampler, features
+        if conditioner is not None and conditioner.sample_rate != features.sample_rate:
+            raise ValueError(f"the conditioner meters at {conditioner.sample_rate} Hz, the extractor expects {features.sample_rate} Hz")
+        self.resampler, self.features, self.conditioner = resampler, features, conditioner
 
     @property
     def pitch(self) -> bool:
@@ -154,11 +160,16 @@ class AudioFrontEnd:
         return self.features.energy
 
     def device_tables(self, device):
-        return self.resampler.device_tables(device), self.features.device_tables(device)
+        t = self.resampler.device_tables(device), self.features.device_tables(device)
+        return t if self.conditioner is None else t + (self.conditioner.device_tables(device),)
 
     def empty_outputs(self, B: int, S: int, device) -> dict:
         a, ln = self.resampler.empty_outputs(B, S, device)
-        return dict(self.features.empty_outputs(B, a.shape[1], device), audio_resampled=a, audio_resampled_len=ln)
+        out = dict(self.features.empty_outputs(B, a.shape[1], device), audio_resampled=a, audio_resampled_len=ln)
+        if self.conditioner is not None:
+            c = self.conditioner.empty_outputs(B, a.shape[1], device)
+            out.update(audio_conditioned=c.pop("audio"), audio_conditioned_len=c.pop("audio_len"), **c)
+        return out
 
     def __call__(self, audio: Tensor, audio_len: Tensor, out: Optional[dict] = None) -> dict:
         if audio.ndim != 2:
@@ -166,5 +177,9 @@ class AudioFrontEnd:
         if out is None:
             out = self.empty_outputs(audio.shape[0], audio.shape[1], audio.device)
         a, ln = self.resampler(audio, audio_len, out=(out["audio_resampled"], out["audio_resampled_len"]))
+        if self.conditioner is not None:
+            c = dict(out, audio=out["audio_conditioned"], audio_len=out["audio_conditioned_len"])
+            self.conditioner(a, ln, out=c)
+            a, ln = c["audio"], c["audio_len"]
         self.features(a, ln, out=out)
         return out

@@ -20,7 +20,7 @@ EP_GELU, EP_SILU, EP_MASK_ACC, EP_MASK_OUT, EP_BIAS_ROW, EP_MASK_COL, EP_OUT_BF1
     1, 2, 4, 8, 16, 32, 64, 128, 256, 512)
 
 _P, _I32, _I64, _U32, _F32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
-_U64 = ctypes.c_uint64
+_U64, _F64 = ctypes.c_uint64, ctypes.c_double
 
 # name -> argtypes; must list EVERY symbol of include/ispk.h (tests/test_abi.py checks header == this table == .so)
 SIGNATURES = {
@@ -120,6 +120,10 @@ SIGNATURES = {
                                 _F32, _P],
     "ispk_resample_f32": [_P, _I64, _I64, _P, _P, _I64, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_feature_stats_f64": [_P, _I64, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P],
+    "ispk_audio_measure_f64": [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _F64, _I32, _I32, _F64,
+                               _F64, _P],
+    "ispk_audio_apply_f32": [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _P],
+    "ispk_pcm16": [_P, _I64, _P, _P, _I64, _I32, _I32, _I32, _U64, _P],
     "ispk_aligner_scores_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_masked_instnorm_bwd_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P],
     "ispk_soft_average_bwd_f32": [_P, _P, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P],
@@ -1894,6 +1898,101 @@ def feature_stats(pitch: Optional[Tensor], energy: Optional[Tensor], mel_len: Op
     _launch("feature_stats_kernel", 0.0, 8.0 * B * M, lib().ispk_feature_stats_f64, pitch.data_ptr(), pitch.stride(0),
             energy.data_ptr(), energy.stride(0), mel_len.data_ptr(), partial.data_ptr(), state.data_ptr(), B, M, int(reset),
             _stream())
+
+
+CONDITION_TABLE_DOUBLES = 152     # 7 coefficients, one unused, nine 4 x 4 powers of the state transition (include/ispk.h)
+CONDITION_MAX_SAMPLES = 1 << 24
+CONDITION_RATES = (8000, 768000)
+
+
+def audio_measure_workspace_floats(B: int, S: int, sample_rate: int) -> int:
+    """ispk_audio_measure_f64: per item the 256-sample square sums, the final states of every 32-sample chunk (4 doubles) and
+    8,192-sample segment, 12 step partials and a peak per segment, and the step sums - in doubles, two floats each."""
+    W, NH, NS = max(1, -(-S // 8192)), max(1, -(-S // 256)), S // (sample_rate // 10) + 1
+    return 2 * B * (NH + W * (256 * 4 + 4 + 12 + 1) + NS)
+
+
+def _mono_batch(audio: Tensor, audio_len: Optional[Tensor]) -> tuple[int, int]:
+    if audio.dtype != torch.float32 or audio.ndim != 2 or audio.stride(1) != 1:
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    if S > CONDITION_MAX_SAMPLES or B > 65535:
+        raise ValueError(f"audio: at most 65535 utterances of {CONDITION_MAX_SAMPLES} samples, got {tuple(audio.shape)}")
+    if audio_len is not None and (audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous()):
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    return B, S
+
+
+def _out_like(name: str, t: Tensor, dtype, shape) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or (t.ndim and t.stride(-1) != 1) or (t.ndim == 1 and not t.is_contiguous()):
+        raise ValueError(f"{name}: {dtype} {tuple(shape)} with unit stride on the last axis, got {t.dtype} {tuple(t.shape)}")
+
+
+def audio_measure(audio: Tensor, audio_len: Tensor, table: Tensor, sample_rate: int, trim_mode: int, trim_threshold: float,
+                  pad_frames: int, gain_mode: int, target_lufs: float, peak_limit: float, bounds: Optional[Tensor] = None,
+                  loudness: Optional[Tensor] = None, peak: Optional[Tensor] = None, gain: Optional[Tensor] = None):
+    """ispk_audio_measure_f64, three launches, no host read: fp32 audio [B, S] (unit stride on S) with int64 lengths [B] ->
+    (bounds int64 [B, 2], loudness float64 [B], peak fp32 [B], gain fp32 [B]).  `table` float64 [152] as include/ispk.h lays
+    it out (data.AudioConditioner builds it)."""
+    _dev(audio, audio_len, table, bounds, loudness, peak, gain)
+    B, S = _mono_batch(audio, audio_len)
+    assert table.dtype == torch.float64 and table.shape == (CONDITION_TABLE_DOUBLES,) and table.is_contiguous()
+    dev = audio.device
+    bounds = torch.empty((B, 2), dtype=torch.int64, device=dev) if bounds is None else bounds
+    loudness = torch.empty((B,), dtype=torch.float64, device=dev) if loudness is None else loudness
+    peak = torch.empty((B,), dtype=torch.float32, device=dev) if peak is None else peak
+    gain = torch.empty((B,), dtype=torch.float32, device=dev) if gain is None else gain
+    _out_like("bounds", bounds, torch.int64, (B, 2))
+    if not bounds.is_contiguous():
+        raise ValueError("bounds: contiguous int64 [B, 2]")
+    _out_like("loudness", loudness, torch.float64, (B,))
+    _out_like("peak", peak, torch.float32, (B,))
+    _out_like("gain", gain, torch.float32, (B,))
+    if B == 0:
+        return bounds, loudness, peak, gain
+    ws = workspace(dev, audio_measure_workspace_floats(B, S, sample_rate))
+    _launch("audio_measure_kernels", 56.0 * B * S, 4.0 * 2 * B * S + 2.0 * 8 * B * S / 8, lib().ispk_audio_measure_f64, audio.data_ptr(),
+            audio.stride(0), audio_len.data_ptr(), table.data_ptr(), table.numel(), bounds.data_ptr(), loudness.data_ptr(),
+            peak.data_ptr(), gain.data_ptr(), ws.data_ptr(), ws.numel(), B, S, int(sample_rate), int(trim_mode),
+            float(trim_threshold), int(pad_frames), int(gain_mode), float(target_lufs), float(peak_limit), _stream())
+    return bounds, loudness, peak, gain
+
+
+def audio_apply(audio: Tensor, bounds: Tensor, gain: Optional[Tensor], out: Optional[Tensor] = None,
+                out_len: Optional[Tensor] = None):
+    """ispk_audio_apply_f32, one launch: out[b, i] = gain[b] * audio[b, start_b + i] below end_b - start_b, then zeros; the
+    lengths go to out_len.  `out` fp32 [B, S_out] may not overlap `audio`."""
+    _dev(audio, bounds, gain, out, out_len)
+    B, S = _mono_batch(audio, None)
+    dev = audio.device
+    out = torch.empty((B, S), dtype=torch.float32, device=dev) if out is None else out
+    out_len = torch.empty((B,), dtype=torch.int64, device=dev) if out_len is None else out_len
+    if out.ndim != 2:
+        raise ValueError(f"out: fp32 [{B}, S_out], got {tuple(out.shape)}")
+    _out_like("out", out, torch.float32, (B, out.shape[1]))
+    _out_like("out_len", out_len, torch.int64, (B,))
+    _out_like("bounds", bounds, torch.int64, (B, 2))
+    if gain is not None:
+        _out_like("gain", gain, torch.float32, (B,))
+    if B == 0:
+        return out, out_len
+    _launch("cond_apply_kernel", 1.0 * B * S, 4.0 * (B * S + out.numel()), lib().ispk_audio_apply_f32, audio.data_ptr(), audio.stride(0),
+            bounds.data_ptr(), _ptr(gain), out.data_ptr(), out.stride(0), out_len.data_ptr(), B, S, out.shape[1], _stream())
+    return out, out_len
+
+
+def pcm16(audio: Tensor, audio_len: Tensor, dither: bool = False, seed: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """ispk_pcm16, one launch: fp32 [B, S] -> int16 [B, S], clamp(rint(32768 x + d)), zero past audio_len."""
+    _dev(audio, audio_len, out)
+    B, S = _mono_batch(audio, audio_len)
+    out = torch.empty((B, S), dtype=torch.int16, device=audio.device) if out is None else out
+    _out_like("out", out, torch.int16, (B, S))
+    if B == 0 or S == 0:
+        return out
+    _launch("pcm16_kernel", 0.0, 6.0 * B * S, lib().ispk_pcm16, audio.data_ptr(), audio.stride(0), audio_len.data_ptr(),
+            out.data_ptr(), out.stride(0), B, S, int(bool(dither)), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream())
+    return out
 
 
 def flow_loss_bwd(pred_raw: Tensor, flow: Tensor, mask: Tensor, grad_out: float = 1.0) -> Tensor:
