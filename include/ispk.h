@@ -394,6 +394,12 @@ int32_t ispk_infer_features_f32(const float* pred, const float* duration_target_
                                 const float* pitch_target, const float* energy_target, float duration_factor, float pitch_factor,
                                 float pitch_delta, float energy_factor, float energy_delta, float* duration, float* features,
                                 int32_t B, int32_t L, ispk_stream_t stream);
+/* The same with hard durations (soft_duration off, :355-357): the predicted duration is rounded half to even (torch.round)
+ * before the clamp, duration = max(rint(duration_factor * (exp(pred[..,0]) - 1)), 0); targets >= 0 replace it unrounded. */
+int32_t ispk_infer_features_round_f32(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
+                                      const float* pitch_target, const float* energy_target, float duration_factor,
+                                      float pitch_factor, float pitch_delta, float energy_factor, float energy_delta,
+                                      float* duration, float* features, int32_t B, int32_t L, ispk_stream_t stream);
 int32_t ispk_flow_mix_f32(const float* x0, const float* x1, const float* t, float sigma, float* x_t, float* flow, int32_t B,
                           int32_t L, int32_t C, ispk_stream_t stream);
 int32_t ispk_flow_finish_f32(const float* pred_raw, const float* flow, const float* x0, const uint8_t* mask, float* pred,
@@ -447,6 +453,32 @@ int32_t ispk_length_regulate_split_bf16(const float* alignment, const float* dur
 int32_t ispk_length_regulate_split_f16(const float* alignment, const float* dur_f32, const int64_t* dur_i64, const int64_t* enc_len,
                                 const float* x, int64_t ldx, float* out, int64_t* dec_len, uint8_t* dec_mask, int32_t B,
                                 int32_t M, int32_t L, int32_t D, int32_t max_len, int32_t dur_cols, ispk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Hard durations: FlowTemporalAdaptor with soft_duration off, the reference's constructor default (csrc/hard_duration.hip).
+ * L <= 512 tokens (the aligner's limit), B <= 65535; durations outside the operators' domain (negative, NaN) count as 0.
+ *
+ * ispk_hard_regulate_f32      LengthRegulator without an alignment (temporal_adaptor.py:422-436): reps[b][l] = (float(dur[b][l])
+ *                             + 0.5) truncated, over EVERY token column (the reference applies no enc_len mask here);
+ *                             dec_len[b] = sum_l reps, clamped to max_len when max_len >= 0; out[b][y][:] = x[b][l][:] for the
+ *                             one l with cum[l] <= y < cum[l + 1], zero for y >= dec_len[b]; dec_mask[b][y] = y < dec_len[b]
+ *                             (or NULL).  Exactly one of dur_f32 / dur_i64 [B][L] is given.  x fp32 [B][L][D] rows at stride
+ *                             ldx, D 256 / 384; out [B][frames][D].  A row copy: bit-exact, whatever the compute path.
+ * ispk_hard_regulate_bwd_f32  d_x[b][l][:] = sum of d_out[b][y][:] over the token's frames below min(dec_len[b], rows), added
+ *                             in frame order in fp32 by one owner per value (no atomics: the same bits every run); zero rows
+ *                             for tokens without frames.  d_out [B][rows][D], d_x [B][L][D], both contiguous.
+ * ispk_hard_average_f32       TemporalAverager without an alignment (:451-465) in ispk_soft_average_f32's layout:
+ *                             feats[b][l] = { log1p(dur[b][l]), mask * mean of the NON-ZERO pitch[b][y] over the token's
+ *                             frames cum[l] <= y < cum[l + 1] (0 when there is none), same for energy }, feats [B][L][3], mask =
+ *                             l < text_len[b], cum the running sum of the int64 durations with segment ends cut at M.  Each
+ *                             segment is summed directly (the reference differences two fp32 running sums). */
+int32_t ispk_hard_regulate_f32(const float* dur_f32, const int64_t* dur_i64, const float* x, int64_t ldx, float* out,
+                               int64_t* dec_len, uint8_t* dec_mask, int32_t B, int32_t frames, int32_t L, int32_t D,
+                               int32_t max_len, ispk_stream_t stream);
+int32_t ispk_hard_regulate_bwd_f32(const float* dur_f32, const int64_t* dur_i64, const float* d_out, float* d_x, int32_t B,
+                                   int32_t rows, int32_t L, int32_t D, int32_t max_len, ispk_stream_t stream);
+int32_t ispk_hard_average_f32(const float* pitch, const float* energy, const int64_t* duration, const int64_t* text_len,
+                              float* feats, int32_t B, int32_t M, int32_t L, ispk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Training step (BASELINE config 5): fp32 kernels with the recipes' dropout; under AMP the Linear GEMMs and

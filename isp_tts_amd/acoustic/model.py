@@ -147,13 +147,16 @@ class AcousticModel(nn.Module, Constructor):
         # path needs neither - it is built from attn_soft and the dense targets, and its lengths are sum(durations) =
         # mel_len.  They run on the side stream beside the embedding stack, the length regulator and the decoder.
         branch = side if q_proj is not None else None
+        # Hard durations: the pitch / energy targets and the regulator read the MAS durations, so the decoder path waits for
+        # MAS - it runs on this stream; only the flow predictor leaves for the side stream, and there is no length shortcut.
+        hard = not self.temporal_adaptor.soft_duration
         aligner_output = self.aligner(mel=mel, enc_text=enc_out.transpose(1, 2).detach(), mel_len=mel_len,
-                                      text_len=text_len, q_proj=q_proj, mas_stream=branch)
+                                      text_len=text_len, q_proj=q_proj, mas_stream=None if hard else branch)
         adaptor_output = self.temporal_adaptor(
             enc_out=enc_out, enc_mask=enc_mask, max_dec_len=mel.size(2),
             duration_target=aligner_output.attn_hard_duration, alignment=aligner_output.attn_soft,
             pitch_target_dense=pitch, energy_target_dense=energy, noise=flow_noise, time_steps=flow_time,
-            enc_len=text_len, predictor_stream=branch, duration_sum=mel_len if branch is not None else None)
+            enc_len=text_len, predictor_stream=branch, duration_sum=mel_len if branch is not None and not hard else None)
         dec_len = adaptor_output.dec_lengths
         dec_mask = adaptor_output.dec_mask              # arange(frames) < dec_len, from the length-regulation kernel
         dec_out = self.decoder(adaptor_output.enc_out, mask=dec_mask, key_len=dec_len, out_dtype=self.compute_dtype).out

@@ -4,6 +4,10 @@ The transformer stacks (predictor: dim 256 x 3 with AdaptiveLayerNorm; embedding
 kernels through `Transformer`.  The small tensor algebra around them (soft averaging, soft length regulation,
 soft-path generation: SURVEY row f3 "next") is stock PyTorch-ROCm with the reference's order of operations.
 
+Both duration modes are built: `soft_duration=True` (the recipes': fractional durations, the decoder input is alignment @ x)
+and `soft_duration=False` (the reference's constructor default, FastPitch's arrangement: every token repeated round(duration)
+times, pitch / energy targets plain means over each token's frames - `runtime.hard_regulate`, `runtime.hard_average`).
+
 The flow noise is an explicit, optional input (`noise`, `time_steps`) so that parity runs can feed host-generated
 draws; when omitted it is drawn like the reference (randn_like then rand, temporal_adaptor.py:113-115; randn :148).
 """
@@ -193,13 +197,26 @@ class LengthRegulator(nn.Module):
     products, decoder lengths and the decoder mask from the same launch; the mask of the last call is kept in
     `self.dec_mask` for the caller that needs it next).  `alignment=None` with fp32 durations: the soft path of
     `generate_soft_path` is generated inside the kernel (`infer`).  `split_bf16` (set by `AcousticModel.set_compute_dtype` on the
-    bf16 path): `ispk_length_regulate_split_bf16`, each product as three bf16 MFMAs on hi / lo splits of the fp32 operands."""
+    bf16 path): `ispk_length_regulate_split_bf16`, each product as three bf16 MFMAs on hi / lo splits of the fp32 operands.
+
+    Hard branch (:422-436; no alignment, and `hard=True`, int64 durations or no `frames`): every row of x repeated
+    (float(duration) + .5).long() times by `ispk_hard_regulate_f32` - a row copy, the same bits on every compute path.  Without
+    `frames` the output length is data, as in the reference: the longest decoder length is read back to the host."""
     split_bf16 = False
 
     def forward(self, x: Tensor, durations: Tensor, max_len: Optional[int] = None, alignment: Optional[Tensor] = None, *,
-                enc_len: Optional[Tensor] = None, frames: Optional[int] = None):
-        if alignment is None and (frames is None or durations.dtype == torch.int64):
-            raise NotImplementedError("hard (repeat) length regulation is unused by the recipes (soft_duration: true)")
+                enc_len: Optional[Tensor] = None, frames: Optional[int] = None, hard: bool = False):
+        if alignment is None and (hard or frames is None or durations.dtype == torch.int64):
+            if frames is None:
+                frames = int((durations.float() + 0.5).long().sum(dim=1).max().item())
+            if max_len is not None:
+                frames = min(frames, max_len)
+            if frames == 0:    # nothing to repeat (the reference returns the same empty tensor)
+                self.dec_mask = torch.zeros((x.shape[0], 0), dtype=torch.bool, device=x.device)
+                return x.new_zeros((x.shape[0], 0, x.shape[2])), torch.zeros((x.shape[0],), dtype=torch.int64, device=x.device)
+            out, dec_lens, self.dec_mask = runtime.hard_regulate(x.float(), durations, frames,
+                                                                 max_len=-1 if max_len is None else max_len)
+            return out, dec_lens
         rows = alignment.shape[1] if alignment is not None else frames
         if max_len is not None and alignment is not None:
             rows = min(rows, max_len)
@@ -211,11 +228,22 @@ class LengthRegulator(nn.Module):
 
 
 class TemporalAverager(nn.Module):
-    """temporal_adaptor.py:439-449, soft branch: x[B,1,M] @ A[B,M,L] / (colsum(A) + 1e-5)."""
+    """temporal_adaptor.py:439-465.  Soft branch: x[B,1,M] @ A[B,M,L] / (colsum(A) + 1e-5).  Hard branch (no alignment):
+    the mean of the non-zero entries of x over each token's frames, 0 where there is none (`ispk_hard_average_f32`, each
+    segment summed directly - the reference differences two fp32 running sums, which is the noisier of the two)."""
 
     def forward(self, x: Tensor, durations: Tensor, alignment: Optional[Tensor] = None) -> Tensor:
         if alignment is None:
-            raise NotImplementedError("hard averaging is unused by the recipes (soft_duration: true)")
+            b, c, _ = x.shape
+            if durations.dtype != torch.int64:       # :451 `cumsum(durations).long()`: the segment ends of fractional durations
+                ends = torch.cumsum(durations, dim=1).long()
+                durations = torch.diff(ends, dim=1, prepend=torch.zeros_like(ends[:, :1]))
+            every = torch.full((b,), durations.shape[1], dtype=torch.int64, device=x.device)
+            cols = []
+            for i in range(0, c, 2):                 # the kernel averages two rows at a time (pitch and energy)
+                f = runtime.hard_average(x[:, i], x[:, min(i + 1, c - 1)], durations, every)
+                cols.append(f[..., 1:min(3, 1 + c - i)])
+            return torch.cat(cols, dim=-1).transpose(1, 2)
         return x @ alignment / (alignment.sum(dim=1, keepdim=True) + 1e-5)
 
 
@@ -235,8 +263,9 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
     def __init__(self, encoder_dim: int = 384, predictor=None, embedding=None, pitch: bool = True, energy: bool = True,
                  soft_duration: bool = False):
         super().__init__()
-        if not (pitch and energy and soft_duration):
-            raise NotImplementedError("built for the recipes' adaptor: pitch, energy and soft_duration all on")
+        if not (pitch and energy):
+            raise NotImplementedError("built with pitch and energy both on (either duration mode): without one of them the "
+                                      "feature tensors change shape")
         self.length_regulator = LengthRegulator()
         self.averager = TemporalAverager()
         self.encoder_dim = encoder_dim
@@ -267,15 +296,25 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
             `duration_sum` (int64 [B]) says what that sum is (AcousticModel.forward passes mel_len: the MAS durations add
             up to it by construction, alignment.py:278-282).  `duration_target` itself may then still be in flight on
             `predictor_stream` (MAS runs there); it is only read on that stream (log1p duration target of the predictor).
-        The CALLER joins `predictor_stream` before using the predictor's outputs (`AcousticModel.forward` does)."""
-        assert alignment is not None and duration_target is not None
+        The CALLER joins `predictor_stream` before using the predictor's outputs (`AcousticModel.forward` does).
+
+        With hard durations (`soft_duration` off) `alignment` is ignored (:250-251): the targets are the hard averages over the
+        durations' segments and the regulator repeats rows by them, so the decoder path DOES wait for `duration_target` - it
+        must be complete on the current stream, and `duration_sum` has no use.  The flow predictor may still run beside it."""
+        assert duration_target is not None and (alignment is not None or not self.soft_duration)
         assert pitch_target_dense is not None and energy_target_dense is not None
+        hard = not self.soft_duration
         m3 = enc_mask[..., None]
         if enc_len is None:
             enc_len = enc_mask.sum(dim=1)
         side = predictor_stream if (predictor_stream is not None and enc_out.is_cuda) else None
         cond = enc_out
-        if side is None or duration_sum is None:
+        if hard:
+            alignment = None
+            targets = runtime.hard_average(pitch_target_dense, energy_target_dense, duration_target, enc_len)
+            feats = targets
+            len_src = duration_target
+        elif side is None or duration_sum is None:
             # one stream, or no shortcut for the lengths: the three flow targets (log1p duration, soft-averaged pitch and
             # energy, :257-269) from ONE kernel, read by both branches
             targets = runtime.soft_average(alignment, pitch_target_dense, energy_target_dense, duration_target, enc_len)
@@ -293,7 +332,9 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
 
         def decoder_input(enc_out_):
             enc_out_ = self.embedding(features, mask=m3, key_len=enc_len, residual=enc_out_)   # enc_out + embedding(...)
-            return self.length_regulator(enc_out_, len_src, max_len=max_dec_len, alignment=alignment)
+            # (hard durations: `frames` fixes the output length at max_dec_len, as the alignment's rows do - no host read-back)
+            return self.length_regulator(enc_out_, len_src, max_len=max_dec_len, alignment=alignment,
+                                         frames=max_dec_len if hard else None)
 
         if not (side is not None and self.predictor_first):
             enc_out, dec_lens = decoder_input(enc_out)
@@ -310,7 +351,8 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
             with torch.cuda.stream(side):
                 pred, losses, duration_pred = predict()
             for t in (cond, feats, alignment, pitch_target_dense, energy_target_dense):
-                t.record_stream(side)
+                if t is not None:
+                    t.record_stream(side)
             if self.predictor_first:
                 enc_out, dec_lens = decoder_input(enc_out)
         else:
@@ -326,9 +368,9 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
               pitch_delta: float = 0., energy_target: Optional[Tensor] = None, energy_factor: float = 1.0,
               energy_delta: float = 0., steps: int = 4, *, noise: Optional[Tensor] = None,
               max_dec_len: Optional[int] = None, enc_len: Optional[Tensor] = None) -> TemporalAdaptorOutput:
-        """temporal_adaptor.py:331-408.  Durations stay fractional (soft_duration, :355-356); the embedding transformer
-        gets NO mask even when batched (:384).  `max_dec_len` (optional) fixes the decoder length without reading
-        `dec_lens.max()` back to the host."""
+        """temporal_adaptor.py:331-408.  Durations stay fractional with soft_duration (:355-356) and are rounded without it;
+        the embedding transformer gets NO mask even when batched (:384).  `max_dec_len` (optional) fixes the decoder length
+        without reading `dec_lens.max()` back to the host."""
         m3 = enc_mask[..., None] if enc_mask is not None else None
         pred = self.predictor.infer(enc_out, mask=m3, steps=steps, noise=noise, key_len=enc_len)
         # :351-381 in ONE kernel: duration = clamp(duration_factor * (exp(pred[..., 0]) - 1), 0) with the given targets
@@ -336,12 +378,18 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
         # and fills only the negative entries; per element on the device that is the same values without the round trip,
         # which keeps the call capturable in a HIP graph), and the embedding stack's [pitch, energy] input.
         duration_pred, feats = runtime.infer_features(pred, duration_target, pitch_target, energy_target, duration_factor,
-                                                      pitch_factor, pitch_delta, energy_factor, energy_delta)
+                                                      pitch_factor, pitch_delta, energy_factor, energy_delta,
+                                                      round_duration=not self.soft_duration)
         pitch, energy = feats[..., 0:1], feats[..., 1:2]
         enc_out = self.embedding(feats, residual=enc_out)                                   # no mask, even batched (:384)
         enc_lens = enc_len
         if enc_lens is None and enc_mask is not None:
             enc_lens = enc_mask.sum(dim=1)
+        if not self.soft_duration:    # :397 without an alignment: rows repeated (duration + .5).long() times, dec_lens their sum
+            enc_out, dec_lens = self.length_regulator(enc_out, duration_pred, alignment=None, frames=max_dec_len, hard=True)
+            return TemporalAdaptorOutput(enc_out=enc_out, log_duration=None, duration=duration_pred, dec_lengths=dec_lens,
+                                         pitch=pitch.squeeze(-1), energy=energy.squeeze(-1), pitch_target=pitch_target,
+                                         energy_target=energy_target, dec_mask=self.length_regulator.dec_mask)
         if max_dec_len is None:   # the output shape is data: like the reference, read the longest decoder length back
             max_dec_len = int((duration_pred.sum(dim=1) + 0.5).long().max().item())
         # :388-397: soft path (generate_soft_path) and length regulation in one kernel

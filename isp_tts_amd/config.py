@@ -38,8 +38,9 @@ class AcousticDims:
     key_kernel: int = 5
     query_kernels: tuple = (5, 5)
 
-    def model_config(self) -> dict:
-        """Nested dict in the shape `AcousticModel.init(config)` takes (model.py:60-72 of the reference)."""
+    def model_config(self, soft_duration: bool = True) -> dict:
+        """Nested dict in the shape `AcousticModel.init(config)` takes (model.py:60-72 of the reference).  `soft_duration`: the
+        recipes set it; False is the reference's constructor default (hard durations: rows repeated, targets plain means)."""
         enc = {"dim": self.text_dim, "depth": self.enc_depth, "transformer_layer": _layer(self.heads, self.ffn, 0.1)}
         dec = {"dim": self.text_dim, "depth": self.dec_depth, "transformer_layer": _layer(self.heads, self.ffn, 0.1)}
         ada_layer = _layer(self.ada_heads, self.ada_ffn, 0.3)
@@ -55,7 +56,7 @@ class AcousticDims:
                                               "transformer_layer": ada_layer}},
                 "embedding": {"transformer": {"dim": self.ada_dim, "depth": self.emb_depth,
                                               "transformer_layer": ada_layer}},
-                "pitch": True, "energy": True, "soft_duration": True,
+                "pitch": True, "energy": True, "soft_duration": bool(soft_duration),
             },
             "aligner": {"attention_dim": self.attn_dim, "key_kernel_size": self.key_kernel,
                         "query_kernel_size": list(self.query_kernels), "dropout": 0.1,

@@ -673,6 +673,8 @@ __global__ __launch_bounds__(256) void flow_euler_kernel(const float* __restrict
 //   duration = clamp(duration_factor * (exp(pred[..., 0]) - 1), min 0), replaced by the target where one is given (>= 0; the
 //              reference fills only the negative entries of a target with predictions, :355-362)
 //   features = [ (pitch_target | pred[..., 1]) * pitch_factor + pitch_delta, (energy_target | pred[..., 2]) * ef + ed ]
+// kRound (hard durations, soft_duration off): the prediction is rounded half to even before the clamp, like torch.round (:355-357)
+template <bool kRound>
 __global__ __launch_bounds__(256) void infer_features_kernel(const float* __restrict__ pred, const float* __restrict__ dur_f,
                                                              const int64_t* __restrict__ dur_i, const float* __restrict__ pitch_t,
                                                              const float* __restrict__ energy_t, float df, float pf, float pd,
@@ -682,7 +684,8 @@ __global__ __launch_bounds__(256) void infer_features_kernel(const float* __rest
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float e = expf(pred[3 * i]) - 1.0f;
-    float d = fmaxf(df * e, 0.0f);
+    const float scaled = df * e;
+    float d = fmaxf(kRound ? rintf(scaled) : scaled, 0.0f);
     if (dur_f) { const float t = dur_f[i]; d = t < 0.0f ? d : t; }
     if (dur_i) { const int64_t t = dur_i[i]; d = t < 0 ? d : (float)t; }
     duration[i] = d;
@@ -872,17 +875,41 @@ extern "C" int32_t ispk_flow_euler_f32(const float* x_t, const float* velocity, 
     return ispk_launch_status();
 }
 
-extern "C" int32_t ispk_infer_features_f32(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
-                                           const float* pitch_target, const float* energy_target, float duration_factor,
-                                           float pitch_factor, float pitch_delta, float energy_factor, float energy_delta,
-                                           float* duration, float* features, int32_t B, int32_t L, ispk_stream_t stream) {
+static int32_t infer_features_launch(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
+                                     const float* pitch_target, const float* energy_target, float duration_factor,
+                                     float pitch_factor, float pitch_delta, float energy_factor, float energy_delta,
+                                     float* duration, float* features, int32_t B, int32_t L, ispk_stream_t stream, bool round) {
     ISPK_REQUIRE(pred && duration && features, ISPK_E_NULL, "infer_features: null pointer");
     ISPK_REQUIRE(!(duration_target_f32 && duration_target_i64), ISPK_E_UNSUPPORTED, "infer_features: one duration target at most");
     ISPK_REQUIRE(B >= 0 && L >= 1, ISPK_E_SHAPE, "infer_features: bad shape B=%d L=%d", B, L);
     if (B == 0) return 0;
     const int64_t n = (int64_t)B * L;
-    hipLaunchKernelGGL(infer_features_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), pred, duration_target_f32, duration_target_i64, pitch_target,
-                       energy_target, duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta, duration, features, n);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (round)
+        hipLaunchKernelGGL(infer_features_kernel<true>, grid, dim3(256), 0, s, pred, duration_target_f32, duration_target_i64,
+                           pitch_target, energy_target, duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta,
+                           duration, features, n);
+    else
+        hipLaunchKernelGGL(infer_features_kernel<false>, grid, dim3(256), 0, s, pred, duration_target_f32, duration_target_i64,
+                           pitch_target, energy_target, duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta,
+                           duration, features, n);
     return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_infer_features_f32(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
+                                           const float* pitch_target, const float* energy_target, float duration_factor,
+                                           float pitch_factor, float pitch_delta, float energy_factor, float energy_delta,
+                                           float* duration, float* features, int32_t B, int32_t L, ispk_stream_t stream) {
+    return infer_features_launch(pred, duration_target_f32, duration_target_i64, pitch_target, energy_target, duration_factor,
+                                 pitch_factor, pitch_delta, energy_factor, energy_delta, duration, features, B, L, stream, false);
+}
+
+extern "C" int32_t ispk_infer_features_round_f32(const float* pred, const float* duration_target_f32,
+                                                 const int64_t* duration_target_i64, const float* pitch_target,
+                                                 const float* energy_target, float duration_factor, float pitch_factor,
+                                                 float pitch_delta, float energy_factor, float energy_delta, float* duration,
+                                                 float* features, int32_t B, int32_t L, ispk_stream_t stream) {
+    return infer_features_launch(pred, duration_target_f32, duration_target_i64, pitch_target, energy_target, duration_factor,
+                                 pitch_factor, pitch_delta, energy_factor, energy_delta, duration, features, B, L, stream, true);
 }

@@ -97,6 +97,11 @@ class SegmentedForward:
 
     def __init__(self, model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor, energy: Tensor,
                  flow_noise: Optional[Tensor] = None, flow_time: Optional[Tensor] = None, warmup: int = 2, side_priority: int = 0):
+        if not model.temporal_adaptor.soft_duration:
+            raise NotImplementedError("SegmentedForward is built for soft durations: its back piece (embedding stack, length "
+                                      "regulator, decoder) is launched without waiting for the side piece, and with hard "
+                                      "durations both its targets and its regulator read the MAS durations that piece computes; "
+                                      "use GraphedForward")
         b, l = text.shape
         dev = text.device
         s = self.static = {"text": text.clone(), "text_len": text_len.clone(), "mel": mel.clone(), "mel_len": mel_len.clone(),

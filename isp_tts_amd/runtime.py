@@ -80,6 +80,10 @@ SIGNATURES = {
     "ispk_flow_head_f32": [_P, _I64, _P, _P, _F32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_flow_euler_f32": [_P, _P, _F32, _P, _P, _I32, _I32, _I32, _P],
     "ispk_infer_features_f32": [_P, _P, _P, _P, _P, _F32, _F32, _F32, _F32, _F32, _P, _P, _I32, _I32, _P],
+    "ispk_infer_features_round_f32": [_P, _P, _P, _P, _P, _F32, _F32, _F32, _F32, _F32, _P, _P, _I32, _I32, _P],
+    "ispk_hard_regulate_f32": [_P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
+    "ispk_hard_regulate_bwd_f32": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
+    "ispk_hard_average_f32": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_embed_tokens_f32": [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_add_speaker_f32": [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_time_embedding_f32": [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P],
@@ -989,8 +993,9 @@ def flow_euler(x_t: Tensor, velocity: Tensor, dt: float, mask: Optional[Tensor] 
 
 def infer_features(pred: Tensor, duration_target: Optional[Tensor], pitch_target: Optional[Tensor],
                    energy_target: Optional[Tensor], duration_factor: float = 1.0, pitch_factor: float = 1.0,
-                   pitch_delta: float = 0.0, energy_factor: float = 1.0, energy_delta: float = 0.0):
-    """ispk_infer_features_f32: pred [B, L, 3] -> (duration fp32 [B, L], features fp32 [B, L, 2])."""
+                   pitch_delta: float = 0.0, energy_factor: float = 1.0, energy_delta: float = 0.0, round_duration: bool = False):
+    """ispk_infer_features_f32: pred [B, L, 3] -> (duration fp32 [B, L], features fp32 [B, L, 2]).  `round_duration` (hard
+    durations): ispk_infer_features_round_f32, the predicted durations rounded half to even before the clamp."""
     _dev(pred, duration_target, pitch_target, energy_target)
     B, L, C = pred.shape
     assert C == 3 and pred.dtype == torch.float32
@@ -1006,7 +1011,8 @@ def infer_features(pred: Tensor, duration_target: Optional[Tensor], pitch_target
     et = None if energy_target is None else energy_target.float().reshape(B, L).contiguous()
     duration = torch.empty((B, L), dtype=torch.float32, device=pred.device)
     feats = torch.empty((B, L, 2), dtype=torch.float32, device=pred.device)
-    _launch("infer_features_kernel", 0.0, 24.0 * B * L, lib().ispk_infer_features_f32, pc.data_ptr(), _ptr(dur_f), _ptr(dur_i),
+    _launch("infer_features_kernel<round>" if round_duration else "infer_features_kernel", 0.0, 24.0 * B * L,
+            lib().ispk_infer_features_round_f32 if round_duration else lib().ispk_infer_features_f32, pc.data_ptr(), _ptr(dur_f), _ptr(dur_i),
             _ptr(pt), _ptr(et), float(duration_factor), float(pitch_factor), float(pitch_delta), float(energy_factor),
             float(energy_delta), duration.data_ptr(), feats.data_ptr(), B, L, _stream())
     return duration, feats
@@ -1099,6 +1105,60 @@ def length_regulate(x: Tensor, durations: Tensor, alignment: Optional[Tensor], f
             _ptr(dur_f), _ptr(dur_i), _ptr(enc_len), x.data_ptr(), x.stride(1), out.data_ptr(), dec_len.data_ptr(),
             _ptr(mask), B, frames, L, D, max_len, dur_cols, _stream())
     return out, dec_len, mask
+
+
+def _hard_durations(durations: Tensor, B: int, L: int):
+    """-> (fp32 pointer source | None, int64 pointer source | None) of [B, L] durations: int64 (MAS) or fp32 (`infer`)."""
+    assert durations.shape == (B, L), f"durations {tuple(durations.shape)}: one per token, [{B}, {L}]"
+    if durations.dtype == torch.int64:
+        return None, durations.contiguous()
+    return durations.to(torch.float32).contiguous(), None
+
+
+def hard_regulate(x: Tensor, durations: Tensor, frames: int, max_len: int = -1, want_mask: bool = True):
+    """ispk_hard_regulate_f32 -> (out fp32 [B, frames, D], dec_len int64 [B], dec_mask bool [B, frames] | None): every token row
+    of x [B, L, D] repeated (float(duration) + 0.5).long() times, zero rows behind the last one."""
+    _dev(x, durations)
+    assert x.dtype == torch.float32 and x.ndim == 3
+    if x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
+        x = x.contiguous()
+    B, L, D = x.shape
+    dur_f, dur_i = _hard_durations(durations, B, L)
+    out = torch.empty((B, frames, D), dtype=torch.float32, device=x.device)
+    dec_len = torch.empty((B,), dtype=torch.int64, device=x.device)
+    mask = torch.empty((B, frames), dtype=torch.bool, device=x.device) if want_mask else None
+    _launch("hard_regulate_kernel", 0.0, 4.0 * B * D * (frames + L), lib().ispk_hard_regulate_f32, _ptr(dur_f), _ptr(dur_i),
+            x.data_ptr(), x.stride(1), out.data_ptr(), dec_len.data_ptr(), _ptr(mask), B, frames, L, D, max_len, _stream())
+    return out, dec_len, mask
+
+
+def hard_regulate_bwd(d_out: Tensor, durations: Tensor, max_len: int = -1) -> Tensor:
+    """ispk_hard_regulate_bwd_f32: d_out [B, rows, D] -> d_x [B, L, D], each token the sum of its frames' rows in frame order."""
+    _dev(d_out, durations)
+    assert d_out.dtype == torch.float32 and d_out.ndim == 3
+    d_out = d_out.contiguous()
+    B, rows, D = d_out.shape
+    L = durations.shape[1]
+    dur_f, dur_i = _hard_durations(durations, B, L)
+    d_x = torch.empty((B, L, D), dtype=torch.float32, device=d_out.device)
+    _launch("hard_regulate_bwd_kernel", 1.0 * B * rows * D, 4.0 * B * D * (rows + L), lib().ispk_hard_regulate_bwd_f32, _ptr(dur_f),
+            _ptr(dur_i), d_out.data_ptr(), d_x.data_ptr(), B, rows, L, D, max_len, _stream())
+    return d_x
+
+
+def hard_average(pitch: Tensor, energy: Tensor, duration: Tensor, text_len: Tensor) -> Tensor:
+    """ispk_hard_average_f32 -> feats [B, L, 3] = (log1p(duration), mean of each token's non-zero pitch frames, same for energy);
+    pitch / energy fp32 [B, M], duration int64 [B, L]."""
+    _dev(pitch, energy, duration, text_len)
+    B, M = pitch.shape
+    L = duration.shape[1]
+    assert duration.dtype == torch.int64 and duration.shape == (B, L) and energy.shape == (B, M)
+    feats = torch.empty((B, L, 3), dtype=torch.float32, device=pitch.device)
+    # (copies of strided views stay referenced until the launch is queued: a freed one's block would be handed to the next copy)
+    pc, ec, dc, tc = pitch.float().contiguous(), energy.float().contiguous(), duration.contiguous(), text_len.to(torch.int64).contiguous()
+    _launch("hard_average_kernel", 0.0, 8.0 * B * M + 20.0 * B * L, lib().ispk_hard_average_f32, pc.data_ptr(), ec.data_ptr(),
+            dc.data_ptr(), tc.data_ptr(), feats.data_ptr(), B, M, L, _stream())
+    return feats
 
 
 def cast_bf16(x: Tensor) -> Tensor:

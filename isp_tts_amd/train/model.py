@@ -19,8 +19,8 @@ from .. import runtime
 from .loss import AttentionBinarizationLoss, AttentionCTCLoss, MelLoss, sum_losses
 from .aligner import conv_attention_train
 from .predictor import flow_predictor_loss
-from .stack import (EmbedTokensFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction, fork,
-                    transformer_train_forward)
+from .stack import (EmbedTokensFunction, HardRegulateFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction,
+                    fork, transformer_train_forward)
 
 
 def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor, energy: Tensor,
@@ -31,23 +31,32 @@ def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, m
     `aligner_output.attn_soft` carry the graph, so that the reference's loop body - `outputs = model(**inputs)`;
     `loss, losses = criterion(inputs=inputs, outputs=outputs)`; `optimizer.step(loss)` (experiments/trainer.py:543-549) -
     back-propagates through these kernels.  This is what `AcousticModel.forward` returns when gradients are enabled.
-    `train_aligner=False`: the aligner front-end is frozen (its outputs are values)."""
+    `train_aligner=False`: the aligner front-end is frozen (its outputs are values).
+    With hard durations (`temporal_adaptor.soft_duration` off) the targets are the hard averages over the MAS durations and the
+    regulator repeats rows by them: attn_soft has ONE consumer, the binarisation loss, and the mel loss does not reach the aligner."""
     from ..acoustic.alignment import AlignerOutput
     from ..acoustic.model import AcousticModelOutput
     from ..acoustic.temporal_adaptor import TemporalAdaptorOutput
     ad = model.temporal_adaptor
+    hard = not ad.soft_duration
     emb, enc_mask = EmbedTokensFunction.apply(text, model.text_embedding.weight, text_len)
     enc_out = transformer_train_forward(model.encoder, emb, enc_mask, amp, key_len=text_len)
     keys_t = enc_out.detach().transpose(1, 2)          # model.py:139: the aligner sees the DETACHED encoder output
     if train_aligner:
         attn_soft, attn_logits = conv_attention_train(model.aligner.attention, mel, keys_t, mel_len, text_len, amp)
-        attn_soft, attn_soft_kl = fork(attn_soft)     # two consumers: the length regulator and the binarisation loss
+        if hard:
+            attn_soft_kl = attn_soft
+        else:
+            attn_soft, attn_soft_kl = fork(attn_soft)     # two consumers: the length regulator and the binarisation loss
     with torch.no_grad():
         if not train_aligner:
             attn_soft, attn_logits = model.aligner.attention(mel, keys_t, mel_len, text_len)
             attn_soft_kl = attn_soft
         attn_hard, dur = model.aligner.binarize_attention_parallel(attn_logits.detach(), text_len, mel_len, return_duration=True)
-        targets = runtime.soft_average(attn_soft.detach(), pitch, energy, dur, text_len)       # [log1p duration, pitch, energy]
+        if hard:
+            targets = runtime.hard_average(pitch, energy, dur, text_len)                           # [log1p duration, pitch, energy]
+        else:
+            targets = runtime.soft_average(attn_soft.detach(), pitch, energy, dur, text_len)
     # The averaged pitch / energy enter the embedding stack DETACHED (temporal_adaptor.py:284, :292 `pitch_target.detach()`,
     # `energy_target.detach()`), like the predictor's targets (:112): the mel loss reaches attn_soft - and through it the
     # aligner - only by way of the length regulator (:300).
@@ -66,7 +75,10 @@ def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, m
     pe = runtime.copy2d(feats.reshape(-1, 3)[:, 1:3], torch.empty((b * l, 2), dtype=torch.float32, device=feats.device)).view(b, l, 2)
     h = transformer_train_forward(emod.transformer, pe, enc_mask, amp, key_len=text_len)
     x = MaskedLinearResidualFunction.apply(h, emod.linear_layer.weight, emod.linear_layer.bias, enc_mask, enc_out)
-    dec_in, dec_len, dec_mask = LengthRegulateFunction.apply(x, attn_soft, mel_len.view(-1, 1), mel.shape[2])
+    if hard:
+        dec_in, dec_len, dec_mask = HardRegulateFunction.apply(x, dur, mel.shape[2])
+    else:
+        dec_in, dec_len, dec_mask = LengthRegulateFunction.apply(x, attn_soft, mel_len.view(-1, 1), mel.shape[2])
     dec = transformer_train_forward(model.decoder, dec_in, dec_mask, amp, key_len=dec_len)
     mel_out = ToMelFunction.apply(dec, model.to_mel.weight, model.to_mel.bias, dec_mask, amp)
     adaptor = TemporalAdaptorOutput(enc_out=dec_in, log_duration=x_pred[..., 0], duration=duration_pred, dec_lengths=dec_len,

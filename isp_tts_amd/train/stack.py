@@ -277,6 +277,26 @@ class LengthRegulateFunction(torch.autograd.Function):
         return runtime.gemm_tn_batched(alignment, d_out), d_a, None, None
 
 
+class HardRegulateFunction(torch.autograd.Function):
+    """out[b][y] = x[b][token of frame y] (LengthRegulator without an alignment: temporal_adaptor.py:422-436; forward =
+    `runtime.hard_regulate`).  Backward: d x[b][l] = the sum of the token's d out rows (`runtime.hard_regulate_bwd`: frame order,
+    one owner per value, no atomics).  The durations are integers: no gradient leaves through them."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, durations: Tensor, frames: int):
+        out, dec_len, dec_mask = runtime.hard_regulate(x, durations, frames, max_len=frames)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(durations)
+        ctx.frames = frames
+        ctx.mark_non_differentiable(dec_len, dec_mask)
+        return out, dec_len, dec_mask
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor, _dl, _dm):
+        (durations,) = ctx.saved_tensors
+        return runtime.hard_regulate_bwd(d_out.float().contiguous(), durations, max_len=ctx.frames), None, None
+
+
 class MaskedLinearResidualFunction(torch.autograd.Function):
     """out = residual + mask * (h W^T + b): the output Linear of the adaptor's `TransformerTemporalModule`
     (temporal_adaptor.py:43-59) fused with the caller's `enc_out + embedding(...)` (:297), as the forward path launches it."""
@@ -329,12 +349,20 @@ def acoustic_mel_train_forward(model, text: Tensor, text_len: Tensor, mel: Tenso
     ad = model.temporal_adaptor
     emb, enc_mask = EmbedTokensFunction.apply(text, model.text_embedding.weight, text_len)
     enc_out = transformer_train_forward(model.encoder, emb, enc_mask, amp)
+    hard = not ad.soft_duration
     with torch.no_grad():
-        attn_soft, _ = model.aligner.attention(mel, enc_out.detach().transpose(1, 2), mel_len, text_len)
-        feats = runtime.soft_average(attn_soft, pitch, energy, None, text_len)        # pitch / energy targets (:257-269)
+        attn_soft, attn_logits = model.aligner.attention(mel, enc_out.detach().transpose(1, 2), mel_len, text_len)
+        if hard:     # the targets and the regulator read the MAS durations
+            _, dur = model.aligner.binarize_attention_parallel(attn_logits, text_len, mel_len, return_duration=True)
+            feats = runtime.hard_average(pitch, energy, dur, text_len)
+        else:
+            feats = runtime.soft_average(attn_soft, pitch, energy, None, text_len)    # pitch / energy targets (:257-269)
     emod = ad.embedding
     h = transformer_train_forward(emod.transformer, feats[..., 1:3], enc_mask, amp)
     x = MaskedLinearResidualFunction.apply(h, emod.linear_layer.weight, emod.linear_layer.bias, enc_mask, enc_out)
-    dec_in, dec_len, dec_mask = LengthRegulateFunction.apply(x, attn_soft, mel_len.view(-1, 1), mel.shape[2])
+    if hard:
+        dec_in, dec_len, dec_mask = HardRegulateFunction.apply(x, dur, mel.shape[2])
+    else:
+        dec_in, dec_len, dec_mask = LengthRegulateFunction.apply(x, attn_soft, mel_len.view(-1, 1), mel.shape[2])
     dec = transformer_train_forward(model.decoder, dec_in, dec_mask, amp)
     return ToMelFunction.apply(dec, model.to_mel.weight, model.to_mel.bias, dec_mask)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the hot kernels at the BASELINE config-3 shapes (B=64: 32768 decoder rows, 6400 encoder rows).
-HIP-event timing, interleaved rounds, median.  Usage: python tools/bench_kernels.py [f32|bf16] [--rows 32768]"""
+HIP-event timing, interleaved rounds, median.  Usage: python tools/bench_kernels.py [f32|bf16] [--rows 32768]
+`python tools/bench_kernels.py adaptor`: the temporal adaptor's regulators and averagers instead, hard durations beside soft,
+at B=64, L=100, M=512, D=384, each with its traffic floor at the 6.3 TB/s a float4 copy reaches on the MI355X."""
 import os
 import sys
 
@@ -32,6 +34,45 @@ def time_it(fn, rounds=7, inner=20):
     ts.sort()
     return ts[len(ts) // 2], ts[0]
 
+
+def adaptor_cases():
+    """Hard-duration kernels (csrc/hard_duration.hip) beside the soft ones they stand in for, same run, same inputs."""
+    B, L, M, D = 64, 100, 512, 384
+    inp = synth.make_inputs(B, L, M, variable=True)
+    tl, ml = inp["text_len"], inp["mel_len"]
+    dur = torch.zeros(B, L, dtype=torch.int64)
+    for b in range(B):                                   # integer durations over the valid tokens that sum to mel_len, as MAS gives
+        n, m = int(tl[b]), int(ml[b])
+        dur[b, :n] = m // n
+        dur[b, :m - (m // n) * n] += 1
+    x = synth._normal("b/adaptor/x", (B, L, D)).to(dev)
+    d_out = synth._normal("b/adaptor/dout", (B, M, D)).to(dev)
+    attn = torch.softmax(synth._normal("b/adaptor/attn", (B, M, L)), dim=-1).to(dev)
+    pred = synth._normal("b/adaptor/pred", (B, L, 3)).to(dev)
+    dur_d, dur_f, tl_d = dur.to(dev), dur.float().to(dev), tl.to(dev)
+    pitch, energy = inp["pitch"].to(dev), inp["energy"].to(dev)
+    rows = 4 * B * D * (M + L)
+    return [
+        ("hard regulate (int64 durations)", lambda: runtime.hard_regulate(x, dur_d, M, max_len=M), rows),
+        ("hard regulate (fp32 durations)", lambda: runtime.hard_regulate(x, dur_f, M), rows),
+        ("soft regulate fp32 MFMA", lambda: runtime.length_regulate(x, dur_d, attn, M, max_len=M), rows + 4 * B * M * L),
+        ("soft regulate split bf16", lambda: runtime.length_regulate(x, dur_d, attn, M, max_len=M, split_bf16=True), rows + 4 * B * M * L),
+        ("soft regulate, path from durations", lambda: runtime.length_regulate(x, dur_f, None, M, enc_len=tl_d), rows),
+        ("hard regulate backward", lambda: runtime.hard_regulate_bwd(d_out, dur_d, M), rows),
+        ("soft regulate backward (A^T dOut)", lambda: runtime.gemm_tn_batched(attn, d_out), rows + 4 * B * M * L),
+        ("hard average", lambda: runtime.hard_average(pitch, energy, dur_d, tl_d), 8 * B * M + 20 * B * L),
+        ("soft average", lambda: runtime.soft_average(attn, pitch, energy, dur_d, tl_d), 4 * B * M * L + 8 * B * M + 20 * B * L),
+        ("infer features, rounded", lambda: runtime.infer_features(pred, None, None, None, round_duration=True), 24 * B * L),
+        ("infer features", lambda: runtime.infer_features(pred, None, None, None), 24 * B * L),
+    ]
+
+
+if "adaptor" in sys.argv:
+    print("adaptor kernels, B=64 L=100 M=512 D=384 (floor: bytes / 6.3 TB/s)")
+    for name, fn, nbytes in adaptor_cases():
+        med, mn = time_it(fn)
+        print(f"{name:36s} median {med:7.1f} us  min {mn:7.1f} us  {nbytes / 1e6:7.2f} MB  floor {nbytes / 6.3e6:6.2f} us  {nbytes / med / 1e3:7.1f} GB/s")
+    sys.exit(0)
 
 x384 = synth._normal("b/x", (R, 384)).to(dev).to(dt)
 x1536 = synth._normal("b/x2", (R, 1536)).to(dev).to(dt)
