@@ -169,19 +169,13 @@ constexpr int kAsWaves = 2;
 // 32-key block instead of 64 of 64 cycles) and v_exp_f32 / v_log_f32 instead of libm's expf / logf.
 typedef uint32_t as_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void as_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
     union { as_u32x4 u; bf16x8 f; } h, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        f2 a;
-        a.x = v[2 * e]; a.y = v[2 * e + 1];
-        const uint32_t ph = __builtin_bit_cast(uint32_t, __builtin_convertvector(a, bf2));
-        f2 r;
-        r.x = a.x - __builtin_bit_cast(float, ph << 16);
-        r.y = a.y - __builtin_bit_cast(float, ph & 0xffff0000u);
+        const float a0 = v[2 * e], a1 = v[2 * e + 1];
+        const uint32_t ph = pack_bf16x2(a0, a1);
         h.u[e] = ph;
-        l.u[e] = __builtin_bit_cast(uint32_t, __builtin_convertvector(r, bf2));
+        l.u[e] = pack_bf16x2(a0 - __builtin_bit_cast(float, ph << 16), a1 - __builtin_bit_cast(float, ph & 0xffff0000u));
     }
     hi = h.f;
     lo = l.f;
@@ -552,11 +546,6 @@ __global__ __launch_bounds__(1024) void flow_finish_kernel(const float* __restri
 // the masked squared error, flow_head_finalize_kernel adds them in block order per utterance and takes the batch mean in index
 // order (fixed orders: bit-reproducible).  D = 256 (one float4 per lane), C = 3.
 constexpr int kFhRows = 16;      // rows per workgroup: 4 waves x 4 rows
-__device__ __forceinline__ float fh_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __global__ __launch_bounds__(256) void flow_head_kernel(const float* __restrict__ y, int64_t ldy, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, const float* __restrict__ W,
                                                         const float* __restrict__ bias, const float* __restrict__ flow,
@@ -586,14 +575,14 @@ __global__ __launch_bounds__(256) void flow_head_kernel(const float* __restrict_
         const bool live = l < L;
         const int64_t r = (int64_t)b * L + (live ? l : L - 1);
         const bool m = mask[r] != 0;
-        const float mean = fh_wave_sum((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) * (1.0f / 256.0f);
+        const float mean = wave_sum((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) * (1.0f / 256.0f);
         float q = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float d = v[i][e] - mean;
             q = fmaf(d, d, q);
         }
-        const float rstd = 1.0f / sqrtf(fh_wave_sum(q) * (1.0f / 256.0f) + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / 256.0f) + eps);
         float h[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) h[e] = m ? fmaf((v[i][e] - mean) * rstd, g4[e], b4[e]) : 0.f;      // (LayerNorm's row mask)
@@ -603,7 +592,7 @@ __global__ __launch_bounds__(256) void flow_head_kernel(const float* __restrict_
             float a = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) a = fmaf(h[e], w4[c][e], a);
-            raw[c] = fh_wave_sum(a) + bc[c];
+            raw[c] = wave_sum(a) + bc[c];
         }
         if (live) {
 #pragma unroll

@@ -230,18 +230,6 @@ namespace {
 //     init (see the softmax comment in the kernel).
 // Per 32x32 (key x query) block a wave issues 8 MFMAs (256 cycles) and ~100 VALU instructions incl. 16 v_exp_f32: the
 // kernel is VALU-issue-bound, not MFMA-bound; 3 waves per SIMD overlap one wave's softmax with another's MFMAs.
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-template <int OFF>
-__device__ __forceinline__ void lds_read_tr16_b64(u32x2& dst, uint32_t lds_byte_addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_byte_addr), "n"(OFF) : "memory");
-}
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {   // ONE v_cvt_pk_bf16_f32
-    f32x2 v;
-    v.x = lo; v.y = hi;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
 // max over the two 32-lane halves without the LDS round trip of a bpermute: v_permlane32_swap exchanges the upper half
 // of one register with the lower half of another (gfx950).  (Inline asm: the builtin's second result was miscompiled.)
 // v_max3_f32 without the canonicalising v_max x, x that fmaxf() puts in front of every operand (scores are never sNaN)
@@ -487,7 +475,7 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
             u32x2 vr[2][2][2];   // [st][dim tile][run]: keys key0 + 16st + 4h + 0..3 (run 0) and + 8 (run 1) of this lane's dim
             static_for<0, 8>([&](auto ic) {
                 constexpr int i8 = decltype(ic)::value, st = i8 >> 2, dt = (i8 >> 1) & 1, run = i8 & 1;
-                lds_read_tr16_b64<(16 * st + 8 * run) * 128>(vr[st][dt][run], voff[dt] + blk);
+                lds_read_b64_tr_b16_asm<(16 * st + 8 * run) * 128>(vr[st][dt][run], voff[dt] + blk);
             });
             if (key0 + 32 >= klen && it + 1 < qpw && qt + 1 < nqt) {
                 // the tile's last score product: Q is dead, fetch the next tile's fragments behind the softmax / PV / store
@@ -534,7 +522,7 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
 #pragma unroll
             for (int st = 0; st < 2; ++st)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) pf[st].u[e] = pack_bf16(s[8 * st + 2 * e], s[8 * st + 2 * e + 1]);
+                for (int e = 0; e < 4; ++e) pf[st].u[e] = pack_bf16x2(s[8 * st + 2 * e], s[8 * st + 2 * e + 1]);
             if constexpr (ST) { __builtin_amdgcn_sched_barrier(0); tc = __builtin_readcyclecounter(); ts[3] += tc - tb; }
             lds_wait<0>();
             __builtin_amdgcn_sched_barrier(0);
@@ -556,10 +544,10 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
     uint2 pk[2][4];   // [tile][g]
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        pk[0][g].x = pack_bf16(o0[4 * g] * inv, o0[4 * g + 1] * inv);
-        pk[0][g].y = pack_bf16(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-        pk[1][g].x = pack_bf16(o1[4 * g] * inv, o1[4 * g + 1] * inv);
-        pk[1][g].y = pack_bf16(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
+        pk[0][g].x = pack_bf16x2(o0[4 * g] * inv, o0[4 * g + 1] * inv);
+        pk[0][g].y = pack_bf16x2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+        pk[1][g].x = pack_bf16x2(o1[4 * g] * inv, o1[4 * g + 1] * inv);
+        pk[1][g].y = pack_bf16x2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
     }
     if (wide_store) {      // kernel-uniform
 #pragma unroll

@@ -27,23 +27,10 @@
 
 namespace {
 
-typedef uint32_t au32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 abf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr float kAtLog2e = 1.4426950408889634f, kAtLn2 = 0.6931471805599453f;
 constexpr int kAtResKeys = 512;        // keys staged per round of the forward / dQ kernels
 
-__device__ __forceinline__ uint32_t at_pack(float lo, float hi) {   // one v_cvt_pk_bf16_f32
-    f32x2 v;
-    v.x = lo; v.y = hi;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, abf16x2));
-}
 __device__ __forceinline__ int at_sw(int row) { return (((row >> 1) & 1) << 2) | ((row >> 2) & 3); }
-
-template <int OFF>
-__device__ __forceinline__ void at_read_tr(au32x2& dst, uint32_t lds_byte_addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_byte_addr), "n"(OFF) : "memory");
-}
 
 // Per-lane byte offsets into a 32-row block of an image.
 //   row[ks]: A / row operand of k-step ks - row l31, logical slot 2 ks + h (dims 16 ks + 8 h .. + 7);
@@ -72,16 +59,16 @@ __device__ __forceinline__ void at_read_rows(bf16x8 (&f)[4], uint32_t base, cons
     for (int ks = 0; ks < 4; ++ks) lds_read_b128_asm<0>(f[ks], base + a.row[ks]);
 }
 // t[st][dt][run]: rows 16 st + 8 run + 4 h .. + 3 of this lane's dim of tile dt
-__device__ __forceinline__ void at_read_trs(au32x2 (&t)[2][2][2], uint32_t base, const AtLane& a) {
+__device__ __forceinline__ void at_read_trs(u32x2 (&t)[2][2][2], uint32_t base, const AtLane& a) {
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
         for (int run = 0; run < 2; ++run) {
-            at_read_tr<0>(t[0][dt][run], base + a.tr[dt][run]);
-            at_read_tr<2048>(t[1][dt][run], base + a.tr[dt][run]);
+            lds_read_b64_tr_b16_asm<0>(t[0][dt][run], base + a.tr[dt][run]);
+            lds_read_b64_tr_b16_asm<2048>(t[1][dt][run], base + a.tr[dt][run]);
         }
 }
-__device__ __forceinline__ bf16x8 at_frag(const au32x2& r0, const au32x2& r1) {
+__device__ __forceinline__ bf16x8 at_frag(const u32x2& r0, const u32x2& r1) {
     union { uint32_t u[4]; bf16x8 f; } x;
     x.u[0] = r0[0]; x.u[1] = r0[1]; x.u[2] = r1[0]; x.u[3] = r1[1];
     return x.f;
@@ -92,12 +79,12 @@ __device__ __forceinline__ void at_pack_acc(const float (&w)[16], bf16x8 (&f)[2]
     for (int st = 0; st < 2; ++st) {
         union { uint32_t u[4]; bf16x8 v; } x;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) x.u[e] = at_pack(w[8 * st + 2 * e], w[8 * st + 2 * e + 1]);
+        for (int e = 0; e < 4; ++e) x.u[e] = pack_bf16x2(w[8 * st + 2 * e], w[8 * st + 2 * e + 1]);
         f[st] = x.v;
     }
 }
 // acc[dt] += tile^T (dims 32 dt ..) x w over the tile's 32 rows
-__device__ __forceinline__ void at_tr_mma(f32x16 (&acc)[2], const au32x2 (&t)[2][2][2], const bf16x8 (&w)[2]) {
+__device__ __forceinline__ void at_tr_mma(f32x16 (&acc)[2], const u32x2 (&t)[2][2][2], const bf16x8 (&w)[2]) {
 #pragma unroll
     for (int st = 0; st < 2; ++st) {
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_frag(t[st][0][0], t[st][0][1]), w[st], acc[0], 0, 0, 0);
@@ -124,8 +111,8 @@ __device__ __forceinline__ void at_store_row(uint16_t* rowp, const f32x16 (&acc)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 v;
-            v.x = at_pack(acc[mt][4 * g] * mul, acc[mt][4 * g + 1] * mul);
-            v.y = at_pack(acc[mt][4 * g + 2] * mul, acc[mt][4 * g + 3] * mul);
+            v.x = pack_bf16x2(acc[mt][4 * g] * mul, acc[mt][4 * g + 1] * mul);
+            v.y = pack_bf16x2(acc[mt][4 * g + 2] * mul, acc[mt][4 * g + 3] * mul);
             *reinterpret_cast<uint2*>(rowp + 32 * mt + 8 * g + 4 * h) = v;
         }
 }
@@ -194,7 +181,7 @@ __global__ __launch_bounds__(MAXT) void attn_train_fwd_bf16_kernel(const uint16_
             const int key0 = kc0 + blk * 32;
             bf16x8 kf[4];
             at_read_rows(kf, kbase + blk * 4096, ln);
-            au32x2 vt[2][2][2];
+            u32x2 vt[2][2][2];
             at_read_trs(vt, vbase + blk * 4096, ln);
             lds_wait<0>();
             __builtin_amdgcn_sched_barrier(0);
@@ -308,7 +295,7 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dq_bf16_kernel(const uint16_t* 
                 s = at_dot(kf, qf);
                 dp = at_dot(vf, dof);
             }
-            au32x2 kt[2][2][2];                  // lands under the softmax arithmetic below
+            u32x2 kt[2][2][2];                  // lands under the softmax arithmetic below
             at_read_trs(kt, kbase + blk * 4096, ln);
             const float d0 = (float)(key0 + 4 * h - qi);
             const bool edge = key0 + 32 > klen;
@@ -426,7 +413,7 @@ __global__ __launch_bounds__(MAXT) void attn_bwd_dkv_bf16_kernel(const uint16_t*
                     }
                 }
             }
-            au32x2 t[2][2][2];
+            u32x2 t[2][2][2];
             {
                 bf16x8 da[4], vf[4];
                 at_read_rows(da, dbase, ln);

@@ -134,12 +134,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
 // ((r >> 2) & 3))), and ds_read_b64_tr_b16 hands every lane 4 consecutive ROWS of its column - the k-major operand fragment
 // of v_mfma_f32_32x32x16_bf16 without a transposing pass (both operands take rows 8g .. 8g+3 | 8g+4 .. 8g+7 of a 16-row
 // step for lane half g: any k order is fine as long as A and B agree).  fp32 accumulation, the same workspace / ordered sum.
-typedef uint32_t tn_u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t tn_img_off(int row, int ch) { return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-template <int OFF>
-__device__ __forceinline__ void tn_read_tr(tn_u32x2& dst, uint32_t addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-}
 constexpr int kTnImg = kTnRows * 256;            // bytes of one operand's chunk image
 
 // IN16: the operands are ALREADY bf16 in memory (activations an AMP step keeps in bf16 as their producers wrote them): half the
@@ -219,13 +214,6 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const void* __restric
             }
         }
     };
-    auto pack2 = [](float lo, float hi) {
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        f2 v;
-        v.x = lo; v.y = hi;
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf2));
-    };
     auto stash = [&](int buf) {       // fp32: float4 (columns sq .. sq+3) -> 8 bytes at chunk sq / 8, half (sq / 4) & 1
         char* sa = ldsb + buf * 2 * kTnImg;
         char* sb = sa + kTnImg;
@@ -242,8 +230,8 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const void* __restric
                 const int row = sr + 8 * j;
                 const uint32_t off = tn_img_off(row, sq >> 3) + 8 * ((sq >> 2) & 1);
                 uint2 pa, pb;
-                pa.x = pack2(ra[j][0], ra[j][1]); pa.y = pack2(ra[j][2], ra[j][3]);
-                pb.x = pack2(rb[j][0], rb[j][1]); pb.y = pack2(rb[j][2], rb[j][3]);
+                pa.x = pack_bf16x2(ra[j][0], ra[j][1]); pa.y = pack_bf16x2(ra[j][2], ra[j][3]);
+                pb.x = pack_bf16x2(rb[j][0], rb[j][1]); pb.y = pack_bf16x2(rb[j][2], rb[j][3]);
                 *reinterpret_cast<uint2*>(sa + off) = pa;
                 *reinterpret_cast<uint2*>(sb + off) = pb;
             }
@@ -274,15 +262,15 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const void* __restric
         const bool more = m0 + kTnRows < m_end;
         if (more) fetch(m0 + kTnRows);
         const uint32_t base = lds0 + buf * 2 * kTnImg;
-        tn_u32x2 fa[2][2][2], fb[2][2][2];     // [step][tile][run]
+        u32x2 fa[2][2][2], fb[2][2][2];     // [step][tile][run]
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int run = 0; run < 2; ++run) {
-                    tn_read_tr<0>(fa[ks][t][run], base + aoff[ks][run][t]);
-                    tn_read_tr<0>(fb[ks][t][run], base + boff[ks][run][t]);
+                    lds_read_b64_tr_b16_asm<0>(fa[ks][t][run], base + aoff[ks][run][t]);
+                    lds_read_b64_tr_b16_asm<0>(fb[ks][t][run], base + boff[ks][run][t]);
                 }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -325,7 +313,6 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(const void* __restric
 // 128 KB of transposed reads (≈512) against 1,024 cycles of MFMAs: LDS-bound, and bound by its writes.  The DMA needs no
 // registers and no store instructions; a four-stage ring (64 KB, two workgroups per CU) keeps three chunks in flight.
 // Rows past the range and columns past N1 / N2 come from 16 zero bytes (a DMA cannot zero-fill); N1, N2 multiples of 8.
-__device__ __attribute__((aligned(16))) const uint16_t g_tn_zero16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 template <int kTnDmaStages>
 __global__ __launch_bounds__(256) void gemm_tn_dma_kernel(const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __restrict__ B,
                                                           int64_t ldb, float* __restrict__ part, int M, int N1, int N2,
@@ -361,7 +348,7 @@ __global__ __launch_bounds__(256) void gemm_tn_dma_kernel(const uint16_t* __rest
             const int i = wave * 4 + j, isb = i >> 3, grp = i & 7, row = 4 * grp + drow, m = m0 + row;
             const int ch = dpos ^ (((row & 3) << 2) | ((row >> 2) & 3)), col = (isb ? n2 : n1) + 8 * ch;
             const bool ok = m < m_end && col < (isb ? N2 : N1);
-            const uint16_t* src = ok ? (isb ? B + (int64_t)m * ldb : A + (int64_t)m * lda) + col : g_tn_zero16;
+            const uint16_t* src = ok ? (isb ? B + (int64_t)m * ldb : A + (int64_t)m * lda) + col : g_zero16;
             char* dst = stage + isb * kTnImg + grp * 1024;                       // wave-uniform; lane L lands at + 16 L
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
@@ -402,15 +389,15 @@ __global__ __launch_bounds__(256) void gemm_tn_dma_kernel(const uint16_t* __rest
         asm volatile("" ::: "memory");
         if (ch + kTnDmaStages - 1 < nchunks) issue(ch + kTnDmaStages - 1);
         const uint32_t base = lds0 + (ch % kTnDmaStages) * 2 * kTnImg;
-        tn_u32x2 fa[2][2][2], fb[2][2][2];     // [step][tile][run]
+        u32x2 fa[2][2][2], fb[2][2][2];     // [step][tile][run]
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int run = 0; run < 2; ++run) {
-                    tn_read_tr<0>(fa[ks][t][run], base + aoff[ks][run][t]);
-                    tn_read_tr<0>(fb[ks][t][run], base + boff[ks][run][t]);
+                    lds_read_b64_tr_b16_asm<0>(fa[ks][t][run], base + aoff[ks][run][t]);
+                    lds_read_b64_tr_b16_asm<0>(fb[ks][t][run], base + boff[ks][run][t]);
                 }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {

@@ -14,6 +14,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP's uint4 (a union type) can block SROA
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // thread-local last-error text (set by ISPK_FAIL, read through ispk_last_error_string)
 char* ispk_err_buf();
@@ -74,6 +75,13 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+// two fp32 -> packed bf16x2 in ONE v_cvt_pk_bf16_f32 (round to nearest even)
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    f32x2 v;
+    v.x = lo; v.y = hi;
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+}
 
 // GELU(erf) for outputs that are rounded to bf16 anyway, two elements at a time so the polynomial runs on packed fp32
 // (v_pk_fma_f32 / v_pk_mul_f32).  erf by Abramowitz-Stegun 7.1.28: erf(z) = 1 - (1 + a1 z + .. + a6 z^6)^-16, z >= 0,
@@ -145,6 +153,22 @@ __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 
 constexpr int kWave = 64;
 
+__device__ __forceinline__ float wave_sum(float v) {   // every lane ends with the sum over the wave's 64 lanes
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// lane l <- lane l-1; lane 0 keeps `lane0_value` (bound_ctrl off: invalid source lanes keep `old`)
+__device__ __forceinline__ float dpp_shr1(float src, float lane0_value) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0_value),
+                                                                 __builtin_bit_cast(int, src), 0x138, 0xf, 0xf, false));
+}
+
+namespace {
+// 16 zero bytes: the source of LDS-DMA lanes whose index lies past the operand (a DMA cannot zero-fill)
+__device__ __attribute__((aligned(16))) const uint16_t g_zero16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+}  // namespace
+
 // ---- hand-scheduled LDS reads (guide §5.7): hipcc sinks every ds_read next to its consumer and keeps at most two in
 // flight, which makes short MFMA loops LDS-latency-bound.  These reads are opaque to its scheduler; the caller counts
 // them with lds_wait<N>() (LDS operations complete in order, so "at most N outstanding" retires everything older)
@@ -164,6 +188,12 @@ __device__ __forceinline__ void lds_read2_b64_asm(bf16x8& dst, uint32_t lds_byte
 template <int OFF>
 __device__ __forceinline__ void lds_read_b128_asm_acc(bf16x8& dst, uint32_t lds_byte_addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(dst) : "v"(lds_byte_addr), "n"(OFF) : "memory");
+}
+// the transposing read (guide T10): per 16-lane group a 4-row x 16-column block of 16-bit elements comes back with one column
+// per lane and its 4 consecutive rows packed in 8 bytes
+template <int OFF>
+__device__ __forceinline__ void lds_read_b64_tr_b16_asm(u32x2& dst, uint32_t lds_byte_addr) {
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_byte_addr), "n"(OFF) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void lds_wait() {

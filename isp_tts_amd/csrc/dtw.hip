@@ -49,12 +49,6 @@ __host__ __device__ constexpr int64_t bp_words(int rows, int M) {
 // whatever they hold never reaches a cell inside.
 __host__ __device__ constexpr int64_t skew_floats(int rows, int M) { return (int64_t)(M + kThreads - 1) * kThreads * rows_per_lane(rows); }
 
-__device__ __forceinline__ float dpp_shr1(float src, float lane0_value) {
-    // lane l <- lane l-1; lane 0 keeps `lane0_value` (bound_ctrl off: invalid source lanes keep `old`)
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0_value),
-                                                                 __builtin_bit_cast(int, src), 0x138, 0xf, 0xf, false));
-}
-
 struct DtwArgs {
     const float* skew;     // the costs in the skewed layout, skew_item floats per item
     int64_t skew_item;

@@ -2,7 +2,7 @@
 //     out = [mask] * ( x + gelu( LN(x) · W1ᵀ ) · W2ᵀ )        transformer.py:101-110, normalization.py:20-27, feedforward.py:33-40
 // ONE kernel; the [rows, inner] hidden activations never leave the CU.
 //
-// Why a second kernel (gemm.hip's ffn_bf16_kernel is the first): that one gives a wave 32 rows x ALL 384 output features,
+// Why a second kernel (ffn.hip's ffn_bf16_kernel is the first): that one gives a wave 32 rows x ALL 384 output features,
 // 192 accumulator + 96 operand registers = one wave per SIMD, and a wave's own VALU work (the GELU) does not overlap its
 // own MFMAs: the matrix pipe was busy 35 % of the time.  Here a workgroup of 128 rows runs EIGHT waves, two per SIMD, so
 // one wave's GELU / LDS traffic / waits run beside the other's MFMAs - and every weight fragment read from LDS still
@@ -211,7 +211,9 @@ __device__ __forceinline__ void vm_wait_tied(u32x4& a, u32x4& b) {
     asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
 }
 
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {
+// NOT common.h's pack_bf16x2: two scalar conversions joined by shift and OR.  hipcc schedules the pair differently from the
+// single vector conversion, and this kernel's waits are hand-counted against the instruction stream it gets from this form.
+__device__ __forceinline__ uint32_t pack_bf16_cvt2(float lo, float hi) {
     return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
@@ -401,8 +403,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
 #pragma unroll
         for (int gq = 0; gq < 2; ++gq) {
             uint2 pk;
-            pk.x = pack_bf16(g[4 * gq], g[4 * gq + 1]);
-            pk.y = pack_bf16(g[4 * gq + 2], g[4 * gq + 3]);
+            pk.x = pack_bf16_cvt2(g[4 * gq], g[4 * gq + 1]);
+            pk.y = pack_bf16_cvt2(g[4 * gq + 2], g[4 * gq + 3]);
             *reinterpret_cast<uint2*>(pt + 16 * ((2 * half + gq) ^ psw)) = pk;
         }
     };
@@ -558,8 +560,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[e] = fmaf((acc2[nt][4 * gq + e] - mean) * rstd, g4[e], b4[e]);
                 uint2 pk;
-                pk.x = pack_bf16(y[0], y[1]);
-                pk.y = pack_bf16(y[2], y[3]);
+                pk.x = pack_bf16_cvt2(y[0], y[1]);
+                pk.y = pack_bf16_cvt2(y[2], y[3]);
                 *reinterpret_cast<uint2*>(smem + kXtOff + rl * 768 + 16 * ((f0 >> 3) ^ (rl & 15)) + 8 * h) = pk;
             }
         if constexpr (split_mode) {
@@ -618,8 +620,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = fmaf((v[i][j][e] - mean) * rstd, g4[j][e], b4[j][e]);
                     uint2 pk;
-                    pk.x = pack_bf16(y[0], y[1]);
-                    pk.y = pack_bf16(y[2], y[3]);
+                    pk.x = pack_bf16_cvt2(y[0], y[1]);
+                    pk.y = pack_bf16_cvt2(y[2], y[3]);
                     const int c16 = (l31 + 32 * j) >> 1;     // 16-byte chunk of the row; this lane owns its half (l31 & 1)
                     *reinterpret_cast<uint2*>(smem + kXtOff + rl * 768 + 16 * (c16 ^ (rl & 15)) + 8 * (l31 & 1)) = pk;
                 }
@@ -869,8 +871,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = fmaf((y[j][e] - mean) * rstd, g4[e], b4[e]);
                     uint2 pk;
-                    pk.x = pack_bf16(o[0], o[1]);
-                    pk.y = pack_bf16(o[2], o[3]);
+                    pk.x = pack_bf16_cvt2(o[0], o[1]);
+                    pk.y = pack_bf16_cvt2(o[2], o[3]);
                     *reinterpret_cast<uint2*>(smem + kX2Off + rb * 768 + 16 * ((c >> 3) ^ (rb & 15)) + 8 * (l31 & 1)) = pk;
                 }
             }
@@ -924,8 +926,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
 #pragma unroll
                 for (int gq = 0; gq < 4; ++gq) {
                     uint2 pk;
-                    pk.x = pack_bf16(aq[t][4 * gq], aq[t][4 * gq + 1]);
-                    pk.y = pack_bf16(aq[t][4 * gq + 2], aq[t][4 * gq + 3]);
+                    pk.x = pack_bf16_cvt2(aq[t][4 * gq], aq[t][4 * gq + 1]);
+                    pk.y = pack_bf16_cvt2(aq[t][4 * gq + 2], aq[t][4 * gq + 3]);
                     *reinterpret_cast<uint2*>(orow + 2 * (32 * t + 8 * gq)) = pk;
                 }
         }
@@ -1023,8 +1025,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
                             for (int e = 0; e < 4; ++e) o[e] = ((y[j][e] - mean) * rstd * g4[e] + b4[e]) * om;
                             if (p.ln_bf16) {
                                 uint2 pk;
-                                pk.x = pack_bf16(o[0], o[1]);
-                                pk.y = pack_bf16(o[2], o[3]);
+                                pk.x = pack_bf16_cvt2(o[0], o[1]);
+                                pk.y = pack_bf16_cvt2(o[2], o[3]);
                                 *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p.ln_out) + (int64_t)r * p.ld_ln + c) = pk;
                             } else {
                                 *reinterpret_cast<f32x4*>(static_cast<float*>(p.ln_out) + (int64_t)r * p.ld_ln + c) = f32x4{o[0], o[1], o[2], o[3]};

@@ -2,7 +2,7 @@
 //     out = [mask] * ( x + gelu( LN(x) · W1ᵀ ) · W2ᵀ )        transformer.py:101-110, normalization.py:20-27, feedforward.py:33-40
 // ONE kernel, the [rows, inner] hidden activations never leave the register file.
 //
-// What the first two generations measured: the four-wave kernel of round 1 (gemm.hip, one wave per
+// What the first two generations measured: the four-wave kernel of round 1 (ffn.hip, one wave per
 // SIMD) staged its weights through registers and ds_write (LDS-write-bound) and ran its GELU on packed fp32 (slow beside
 // MFMAs): 114 us.  The eight-wave kernel of round 2 (ffn2.hip, two waves per SIMD, weights by LDS-DMA) splits both products
 // between the two waves of a SIMD: the partial sums and the activations cross LDS, all eight waves meet at a barrier per
@@ -77,13 +77,6 @@ struct Ffn3Params {
     unsigned long long* stamps = nullptr;   // experiments build, ABL == 3: per wave [prologue, fill, main loop, epilogue, total]
 };
 
-typedef __bf16 bf16x2_v __attribute__((ext_vector_type(2)));
-typedef float f32x2_v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {      // ONE v_cvt_pk_bf16_f32 for the pair
-    f32x2_v v;
-    v.x = lo; v.y = hi;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_v));
-}
 
 __device__ __forceinline__ float sgpr_const(float c) {     // coefficients in SGPRs: as literals every FMA is a two-dword instruction
     asm volatile("" : "+s"(c));
@@ -198,8 +191,8 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(Ffn3Params p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) y[e] = fmaf((v[i][j][e] - mean) * rstd, g4[j][e], b4[j][e]);
                 uint2 pk;
-                pk.x = pack2_bf16(y[0], y[1]);
-                pk.y = pack2_bf16(y[2], y[3]);
+                pk.x = pack_bf16x2(y[0], y[1]);
+                pk.y = pack_bf16x2(y[2], y[3]);
                 const int c16 = (l31 + 32 * j) >> 1;     // 16-byte chunk of the row; this lane owns its half (l31 & 1)
                 *reinterpret_cast<uint2*>(smem + kXtOff + rl * 768 + 16 * (c16 ^ (rl & 15)) + 8 * (l31 & 1)) = pk;
             }
@@ -261,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void ffn3_bf16_kernel(Ffn3Params p) {
         else if (lv == 4) gq[i] = ghv[i] + gq[i];
         else {
             const int k = n - 80;                                        // pair k: values 2k, 2k + 1 -> P fragment k >> 2, word k & 3
-            pf[k >> 2].u[k & 3] = pack2_bf16(gq[2 * k], gq[2 * k + 1]);
+            pf[k >> 2].u[k & 3] = pack_bf16x2(gq[2 * k], gq[2 * k + 1]);
         }
     };
     constexpr int kOpsB = 5 * 16 + 8;

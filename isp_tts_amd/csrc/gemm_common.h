@@ -1,4 +1,4 @@
-// Shared pieces of the Linear kernels (gemm.hip, split.hip): the launch parameter block and the epilogues.
+// Shared pieces of the Linear kernels (gemm.hip, ffn.hip, split.hip): the launch parameter block and the epilogues.
 #pragma once
 #include "common.h"
 #include "dropout.h"
@@ -20,7 +20,9 @@ struct GemmParams {
     uint32_t flags;
     int cpb;
     int64_t bstride;
-    // fused LayerNorm of the OUTPUT rows (wide bf16 kernel only, ispk_gemm_bf16_ln)
+    // LayerNorm operands.  ispk_gemm_bf16_lnin (panel kernel, ln_flags = 0x100): gamma / beta / eps of the LayerNorm applied to the
+    // fp32 INPUT rows, ln_out = their given (mean, rstd) or nullptr.  ispk_ffn_bf16_prenorm (ln_flags = 4): ln_out receives the
+    // (mean, rstd) of the OUTPUT rows, computed with ln_eps.
     const float* ln_gamma = nullptr;
     const float* ln_beta = nullptr;
     void* ln_out = nullptr;
@@ -31,12 +33,6 @@ struct GemmParams {
     const float* lx_gamma = nullptr;
     const float* lx_beta = nullptr;
     float lx_eps = 1e-5f;
-    // ... and the attention output projection in front of it (ispk_attn_out_ffn_bf16): x1 = pj_x + mask * (pj_o · pj_wᵀ)
-    const uint16_t* pj_o = nullptr;
-    int64_t pj_ldo = 0;
-    const uint16_t* pj_w = nullptr;
-    const float* pj_x = nullptr;
-    int64_t pj_ldx = 0;
     // split-f16 operands (split.hip): element offset of the lo plane from the hi plane for A, W and a split output C
     int64_t a_plane = 0, w_plane = 0, c_plane = 0;
     // batched fp32 product (ispk_gemm_f32_batched): element strides of A, W and C from one batch item (blockIdx.z) to the next
@@ -151,14 +147,6 @@ template <int EP> __device__ __forceinline__ bool ep_resid(const GemmParams& p) 
 }
 inline int ep_key(const GemmParams& p) {
     return (int)(p.flags & 0xffffu) | (p.bias ? kEpBias : 0) | (p.resid ? kEpResid : 0);
-}
-
-// two fp32 -> packed bf16x2 in ONE v_cvt_pk_bf16_f32 (round to nearest even)
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    f32x2 v;
-    v.x = lo; v.y = hi;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
 }
 
 template <int EP = kEpDyn>
@@ -385,9 +373,6 @@ inline bool rows_epilogue_ok(const GemmParams& p) {
         return !p.resid && p.N % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0;
     return true;  // fp32 out: vec_epilogue_ok() already guarantees 16-byte alignment of C / resid rows
 }
-
-// 16 zero bytes: the source of LDS-DMA lanes whose k index lies beyond K (a DMA cannot zero-fill)
-__device__ __attribute__((aligned(16))) const uint16_t g_zero16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 template <int N>
 __device__ __forceinline__ void vm_wait() {

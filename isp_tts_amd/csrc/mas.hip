@@ -33,13 +33,6 @@ namespace {
 // (latency-bound); with 32 it is bound by the dependent VALU chain instead.
 template <int NC> constexpr int rows_ahead() { return NC <= 2 ? 32 : (NC <= 4 ? 16 : 8); }
 
-__device__ __forceinline__ float dpp_shr1(float src, float lane0_value) {
-    // lane l <- lane l-1 ; lane 0 keeps `lane0_value` (bound_ctrl off: invalid source lanes keep `old`)
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0_value), __builtin_bit_cast(int, src), 0x138,
-                                           0xf, 0xf, false));
-}
-
 __device__ __forceinline__ float dpp_ror1(float src) {
     // lane l <- lane l-1, lane 0 <- lane 63 (wave_ror:1): carries a chunk's last column to the next chunk's lane 0
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, src), 0x13C, 0xf, 0xf, false));

@@ -9,12 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <typename OutT>
 __device__ __forceinline__ void store_out(OutT* p, float v);
 template <>

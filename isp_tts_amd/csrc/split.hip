@@ -24,7 +24,6 @@ namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t su32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f16x8 as_f16x8(const bf16x8& v) { return __builtin_bit_cast(f16x8, v); }
 __device__ __forceinline__ void keep_alive(const bf16x8& v) { asm volatile("" ::"v"(v)); }
@@ -491,11 +490,6 @@ constexpr int kSaKeys = 64;                         // keys per staged tile
 constexpr int kSaPlane = kSaKeys * 128;             // bytes of one fp16 plane of one tile
 constexpr int kSaBuf = 4 * kSaPlane;                // K hi, K lo, V hi, V lo
 
-template <int OFF>
-__device__ __forceinline__ void sa_read_tr16_b64(su32x2& dst, uint32_t lds_byte_addr) {
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_byte_addr), "n"(OFF) : "memory");
-}
-
 template <int MAXT, int NS, bool SPLIT_OUT>   // NS = ceil(2048 / threads): staged float4 per thread and tile
 __global__ __launch_bounds__(MAXT) void attn_split_f16_kernel(const float* __restrict__ q, int64_t ldq,
                                                               const float* __restrict__ k, const float* __restrict__ v,
@@ -639,13 +633,13 @@ __global__ __launch_bounds__(MAXT) void attn_split_f16_kernel(const float* __res
                 __builtin_amdgcn_sched_barrier(0);
             }
             // V fragments of the first k-step of the second product: requested now, they land during the softmax
-            su32x2 vh[2][2], vl[2][2];   // [dim tile][run]
+            u32x2 vh[2][2], vl[2][2];   // [dim tile][run]
             auto rdv = [&](auto sc) {
                 constexpr int st = decltype(sc)::value;
                 static_for<0, 4>([&](auto ic) {
                     constexpr int i4 = decltype(ic)::value, dt = i4 >> 1, run = i4 & 1;
-                    sa_read_tr16_b64<(16 * st + 8 * run) * 128>(vh[dt][run], blk + (voff0 ^ (uint32_t)(dt << 6)));
-                    sa_read_tr16_b64<(16 * st + 8 * run) * 128 + kSaPlane>(vl[dt][run], blk + (voff0 ^ (uint32_t)(dt << 6)));
+                    lds_read_b64_tr_b16_asm<(16 * st + 8 * run) * 128>(vh[dt][run], blk + (voff0 ^ (uint32_t)(dt << 6)));
+                    lds_read_b64_tr_b16_asm<(16 * st + 8 * run) * 128 + kSaPlane>(vl[dt][run], blk + (voff0 ^ (uint32_t)(dt << 6)));
                 });
             };
             rdv(std::integral_constant<int, 0>{});

@@ -462,10 +462,7 @@ __global__ __launch_bounds__(512) void ctc_alpha_beta_kernel(const float* __rest
 // exp / log on v_exp_f32 / v_log_f32: the log-sum-exp of a step is m + log(sum) with sum in [1, 3], so a step's error is an
 // absolute ~1e-7 however large the accumulated log-probability is.  The frame's three inputs (two class logits of the lane,
 // the row normaliser) are fetched eight frames ahead.
-__device__ __forceinline__ float ctc_shr1(float src) {      // lane l <- lane l - 1; lane 0 <- -inf
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -INFINITY), __builtin_bit_cast(int, src), 0x138,
-                                                                 0xf, 0xf, false));
-}
+__device__ __forceinline__ float ctc_shr1(float src) { return dpp_shr1(src, -INFINITY); }   // lane l <- lane l - 1; lane 0 <- -inf
 __device__ __forceinline__ float ctc_shl1(float src) {      // lane l <- lane l + 1; lane 63 <- -inf
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -INFINITY), __builtin_bit_cast(int, src), 0x130,
                                                                  0xf, 0xf, false));

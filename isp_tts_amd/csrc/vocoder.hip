@@ -102,11 +102,6 @@ __global__ void __launch_bounds__(256) vocoder_unfold_kernel(const void* __restr
 constexpr int kDwFrames = 8;                      // frames per wave
 constexpr int kDwWaves = 4;
 
-__device__ __forceinline__ float wave_sum(float x) {
-    for (int o = kWave / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
 template <int NC, bool kOutBf16>
 __global__ void __launch_bounds__(256) dwconv7_ln_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                          const float* __restrict__ bias, const float* __restrict__ gamma,

@@ -319,7 +319,7 @@ def layernorm(x: Tensor, gamma: Optional[Tensor], beta: Optional[Tensor], ada_sc
 
 # ------------------------------------------------------------------------------------------------- GEMM
 def _splitk_layout_ok(c2: Tensor, bias: Optional[Tensor], r2: Optional[Tensor], flags: int) -> bool:
-    """The pointer / leading-dimension half of vec_epilogue_ok (csrc/gemm.hip:541), which ispk_gemm_bf16_splitk requires on
+    """The pointer / leading-dimension half of vec_epilogue_ok (csrc/gemm.hip), which ispk_gemm_bf16_splitk requires on
     top of its plan (the plan sees only M, N, K and flags).  Views that fail it (an offset `out=`, a bias slice off 16 bytes,
     an odd row stride) go to ispk_gemm_bf16, whose other kernels take any layout."""
     c_align = 8 if flags & EP_OUT_BF16 else 16

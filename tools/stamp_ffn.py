@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""In-kernel phase stamps of the fused FFN (ISPK_FFN_STAMP): per-wave cycle sums of phase A / phase B / barrier."""
+"""In-kernel phase stamps of the four-wave fused FFN (csrc/ffn.hip, ISPK_FFN_STAMP; experiments build): per-wave cycle sums of
+phase A / phase B / barrier."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isp_tts_amd import runtime, synth
