@@ -20,9 +20,9 @@
 // their VALU work at the same time and leave the matrix pipe idle).
 // Weights stream through LDS by LDS-DMA (global_load_lds_dwordx4, no staging registers): per iteration one 48-KB group
 // {W1 chunk it+1, W2 chunk it-1} into the buffer the previous iteration released, 6 DMA instructions per wave, a whole
-// iteration to land.  Both images are lane-linear as the DMA writes them; bank conflicts are removed by XOR-swizzling the
-// LDS images are what the DMA's per-lane SOURCE addresses make them (the destination is lane-linear): the W1 chunk gets
-// rows of 768 + 16 bytes (the pad slots re-fetch a neighbouring piece) - conflict-free fragment reads AND one address
+// iteration to land.  The LDS images are what the DMA's per-lane SOURCE addresses make them (the destination is lane-linear),
+// and that is where the bank conflicts are removed: the W1 chunk gets rows of 768 + 16 bytes (the pad slots re-fetch a
+// neighbouring piece) - conflict-free fragment reads AND one address
 // register for all twelve of them (base + immediate; an XOR swizzle would need an address per k-step); W2 and P rows
 // (64 B) are XOR-swizzled, 16-byte chunk ^ ((row >> 2) & 3): two addresses.  tools/lds_conflicts.py checks every
 // fragment read: 4 LDS cycles, conflict-free.
@@ -35,7 +35,7 @@
 // workgroup, raw partial products, ispk_ffn_combine_ln_f32 adds them); 50 with the attention block's OUTPUT PROJECTION as the
 // prologue - x1 = x + mask * (o Woᵀ) is formed in product 2's accumulators and never reaches memory (transformer.py:91,
 // attention.py:172); 51 = 50 + the NEXT layer's attention_norm and q/kv projection as the epilogue (transformer.py:79-80,
-// attention.py:63-64); 21 = 20 with the projection prologue.  Everything else is an ablation / stamp variant of the experiments build.
+// attention.py:63-64); 21 = 20 with the projection prologue.  The experiments build adds the probes kProbe* below.
 #include "common.h"
 
 namespace {
@@ -48,7 +48,6 @@ constexpr int kW1Src = kHC * kD * 2;             // 24,576: W1 chunk [32 hidden]
 constexpr int kW2Bytes = kD * kHC * 2;           // 24,576: W2 chunk [384 features][32 hidden] bf16 (24 DMA instructions)
 constexpr int kWbuf = kW1Bytes + kW2Bytes;       // 50,176 per buffer, two buffers
 constexpr int kDmaPerWave = 7;                   // 49 instructions per group over 8 waves: wave w issues q = w, w + 8, ...
-constexpr int kDmaMax = 10;                      // (uneven distributions: up to this many per wave)
 constexpr int kPOff = 2 * kWbuf;                 // P tiles  [2][4 row groups][32 rows][64 B]
 constexpr int kXcOff = kPOff + 2 * 4 * 2048;     // exchange [2][8 waves][2 planes][64 lanes][16 B]
 constexpr int kLds = kXcOff + 2 * 8 * 2048;      // 149,504 B
@@ -60,6 +59,12 @@ constexpr int kSplitMode = 20;   // template argument of the split-inner instanc
 constexpr int kProjMode = 50;    // ... of the instance whose prologue is the attention block's output projection (ispk_attn_out_ffn_bf16)
 constexpr int kSplitProjMode = 21;   // ... of the split-inner instance with the projection prologue (ispk_attn_out_ffn_split_bf16)
 constexpr int kProjQkvMode = 51; // ... and whose epilogue is also the NEXT layer's attention_norm + q/kv projection (ispk_attn_out_ffn_qkv_bf16)
+// Probes (experiments build only, tools/bench_ffn.py): they measure this kernel, they do not propose another one
+constexpr int kProbeNoDma = 1;       // weight DMA only for the first two groups (the products then run on stale buffers: WRONG results, compute-bound timing)
+constexpr int kProbeDmaOnly = 2;     // DMA and barriers only, no products / finish (streaming-bound timing)
+constexpr int kProbeStamps = 3;      // cycle stamps: per wave, cycles in [prologue, barrier waits, DMA issue, finish, product 1, product 2, epilogue, total]
+constexpr int kProbeNoFinish = 10;   // no finish stage (no GELU / exchange reads)
+constexpr int kProbeNoReads = 11;    // matrix stages without operand reads
 constexpr int kNq = 512;         // q/kv features of that mode: 6 heads x 64 + 128
 constexpr int kQChunk = kNq * 16 * 2;            // one k-step of the q/kv weight: [512 features][16] bf16 = 16 KB (ispk_chunk_k16_bf16)
 constexpr int kX2Off = 32 * 388 * 4;             // that epilogue: fp32 tile of 32 rows at 0, then the bf16 tile of LN_next(out) [128][768 B]
@@ -82,7 +87,7 @@ struct Ffn2Params {
     float stats_eps;
     int chunk_count = 0;          // split mode (blockIdx.y = split): chunks per split; 0 = the whole inner dimension
     int64_t part_stride = 0;      // split mode: floats between the splits' partial outputs
-    unsigned long long* stamps = nullptr;   // experiments build, ABL == 3: per-wave phase cycle sums [grid * 8][8]
+    unsigned long long* stamps = nullptr;   // experiments build, kProbeStamps: per-wave phase cycle sums [grid * 8][8]
     const uint16_t* o = nullptr;  // projection mode: attention output rows [rows][384] bf16 ...
     int64_t ld_o = 0;
     const uint16_t* WoC = nullptr;   // ... and to_out's weight as twelve chunks [384 / 32][384][32] (ispk_ffn_chunk_w2_bf16)
@@ -147,59 +152,6 @@ __device__ __forceinline__ void gelu8_bf16_grade(float (&v)[8]) {
     for (int i = 0; i < 8; ++i) v[i] = fmaf(0.5f, v[i], q[i]);
 }
 
-// The same, with a hook after every level (experiment ABL 40: the wave's weight-DMA instructions go out between the levels)
-template <typename Hook>
-__device__ __forceinline__ void gelu8_bf16_grade_hooked(float (&v)[8], Hook&& hook) {
-    const float kRs2 = opaque(0.70710678118654752440f), a4 = opaque(0.078108f), a3 = opaque(0.000972f),
-                a2 = opaque(0.230389f), a1 = opaque(0.278393f);
-    float z[8], q[8];
-#define ISPK_LVL(n_, expr_)                          \
-    _Pragma("unroll") for (int i = 0; i < 8; ++i) { expr_; } \
-    __builtin_amdgcn_sched_barrier(0);               \
-    hook(std::integral_constant<int, n_>{});         \
-    __builtin_amdgcn_sched_barrier(0);
-    ISPK_LVL(0, z[i] = fabsf(v[i]) * kRs2)
-    ISPK_LVL(1, q[i] = fmaf(z[i], a4, a3))
-    ISPK_LVL(2, q[i] = fmaf(q[i], z[i], a2))
-    ISPK_LVL(3, q[i] = fmaf(q[i], z[i], a1))
-    ISPK_LVL(4, q[i] = fmaf(q[i], z[i], 1.0f))
-    ISPK_LVL(5, q[i] = q[i] * q[i])
-    ISPK_LVL(6, q[i] = q[i] * q[i])
-    ISPK_LVL(7, q[i] = __builtin_amdgcn_rcpf(q[i]))
-    ISPK_LVL(8, z[i] = 0.5f * fabsf(v[i]))
-    ISPK_LVL(9, q[i] = fmaf(-z[i], q[i], z[i]))
-#undef ISPK_LVL
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = fmaf(0.5f, v[i], q[i]);
-}
-
-// Variant: the tanh form, gelu(x) ~ x / (1 + exp(-2 u)), u = sqrt(2/pi) (x + 0.044715 x^3): 7 instructions per value, two
-// of them transcendental; max |error| vs the erf form about 5e-4 (at |x| ~ 2).
-__device__ __forceinline__ void gelu8_tanh_form(float (&v)[8]) {
-    const float c1 = opaque(-2.0f * 0.7978845608028654f * 1.4426950408889634f), c3 = opaque(-2.0f * 0.7978845608028654f * 0.044715f * 1.4426950408889634f);
-    float t[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = v[i] * v[i];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = fmaf(t[i], c3, c1);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = t[i] * v[i];
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = __builtin_amdgcn_exp2f(t[i]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = t[i] + 1.0f;
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = __builtin_amdgcn_rcpf(t[i]);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = v[i] * t[i];
-}
-
 // A global load the compiler's wait insertion does not see, and the counted wait that covers it (the loaded registers are
 // operands of the wait: no use of them can be scheduled in front of it)
 template <int OFF>
@@ -217,20 +169,17 @@ __device__ __forceinline__ uint32_t pack_bf16_cvt2(float lo, float hi) {
     return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
 }
 
-// ABL (experiments build only, tools/bench_ffn.py): 1 = weight DMA only for the first two groups (the products then run on
-// stale buffers: WRONG results, compute-bound timing); 2 = DMA and barriers only, no products / finish (streaming-bound
-// timing); 3 = s_memtime stamps: per wave, cycles in [prologue, barrier waits, DMA issue, finish, product 1, product 2,
-// epilogue, total]
-template <int ABL>
+// MODE: one of the five product modes above or, in the experiments build, one of the probes
+template <int MODE>
 __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // experiment switches (ABL 6 .. 9, 12): MFMA stages WITHOUT raised priority; tanh-form GELU; the DMA group issued by half 0 only
-    // (matrix stages at raised priority: adopted - 102.8 -> 101.7 us, same results; ABL 6 = the kernel without it)
-    constexpr bool kPrio = ABL != 6 && ABL != 16 && ABL != 17, kStaticPrio = ABL == 16 || ABL == 17, kTanh = ABL == 7 || ABL == 9, kDmaHalf0 = ABL == 8 || ABL == 9 || ABL == 12;
+    constexpr bool split_mode = MODE == kSplitMode || MODE == kSplitProjMode;      // (own instances: distinct kernel names in profiles)
+    constexpr bool qkv_mode = MODE == kProjQkvMode;
+    constexpr bool proj_mode = MODE == kProjMode || qkv_mode || MODE == kSplitProjMode;
     [[maybe_unused]] unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     [[maybe_unused]] unsigned long long t_prev = 0, t_first = 0;
     auto stamp = [&](int slot) __attribute__((always_inline)) {
-        if constexpr (ABL == 3 || ABL == 34) {
+        if constexpr (MODE == kProbeStamps) {
             __builtin_amdgcn_sched_barrier(0);
             const unsigned long long t = __builtin_readcyclecounter();
             __builtin_amdgcn_sched_barrier(0);
@@ -247,7 +196,6 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     // split mode (small batches, ispk_ffn_bf16_prenorm2_split): workgroup (row block, split) walks only its `chunk_count`
     // chunks of the inner dimension and leaves a raw fp32 partial product; both weight images are chunk-contiguous
     // (kHC rows of W1 = kHC * kD * 2 bytes = one W2 chunk), so a split is a pointer offset
-    constexpr bool split_mode = ABL == kSplitMode || ABL == kSplitProjMode;      // (own instances: distinct kernel names in profiles)
     const int nchunks = split_mode ? p.chunk_count : p.inner / kHC;
     const int64_t wskip = split_mode ? (int64_t)blockIdx.y * p.chunk_count * (kHC * kD * 2) : 0;
     const char* W1b = reinterpret_cast<const char*>(p.W1) + wskip;
@@ -256,25 +204,15 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     // ---- this lane's part of the wave's DMA instructions (q = wave + 8 j of the group's 49): byte offset inside the chunk
     // in memory.  q < 25: the padded W1 image - 16-byte slot t = 64 q + lane is (row t / 49, piece t % 49), piece 48 and rows
     // past 31 are padding; q >= 25: the W2 image, slot -> (row, piece ^ ((row >> 2) & 3)).
-    // Distribution of the 49 instructions over the waves.  Even: q = wave + 8 j (6 each, wave 0 a seventh).  Uneven (kH0 per
-    // half-0 wave, the rest to half 1): the two halves run the stages in different orders and half 1 - the younger wave of
-    // each SIMD, which loses every issue arbitration - is the one the barrier waits for; a DMA instruction costs its issuer
-    // 70 - 115 cycles, so half 0 takes more of them.
-    constexpr int kH0 = (ABL == 13 || ABL == 17 || ABL == 30 || ABL == 34) ? 8 : (ABL == 14 || ABL == 32) ? 9 : (ABL == 15 || ABL == 33) ? 10 : 0;        // 0 = even
-    constexpr int kH1 = kH0 ? (48 - 4 * kH0) / 4 : 0;                              // 8 -> 4, 9 -> 3, 10 -> 2  (+ q = 48: wave 0)
-    constexpr int kPerWave = kH0 ? kH0 + 1 : kDmaPerWave;
+    // The 49 instructions are dealt evenly: q = wave + 8 j (6 each, wave 0 a seventh).  (Uneven deals that give half 0 more
+    // of them, 8/4 to 10/2, measured the same: DESIGN §4.1.)
     auto q_of = [&](int j) __attribute__((always_inline)) -> int {                 // instruction j of this wave; -1 = none
-        if constexpr (kH0 == 0) {
-            const int q = wave + 8 * j;
-            return q < kW1Dma + 24 ? q : -1;
-        } else {
-            if (half == 0) return j < kH0 ? wave + 4 * j : (j == kH0 && wave == 0 ? 48 : -1);
-            return j < kH1 ? 4 * kH0 + (wave - 4) + 4 * j : -1;
-        }
+        const int q = wave + 8 * j;
+        return q < kW1Dma + 24 ? q : -1;
     };
-    uint32_t soff[kPerWave];
+    uint32_t soff[kDmaPerWave];
 #pragma unroll
-    for (int j = 0; j < kPerWave; ++j) {
+    for (int j = 0; j < kDmaPerWave; ++j) {
         const int qq = q_of(j);
         const uint32_t q = qq < 0 ? 0u : (uint32_t)qq;
         if (q < (uint32_t)kW1Dma) {
@@ -294,8 +232,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     // are fetched again into a buffer nobody reads (cheaper than a dozen scalar branches per iteration).
     // One DMA instruction occupies the CU's address path for 16 cycles; eight waves issuing their six or seven right
     // behind the barrier queue up for 49 x 16 cycles (stamped: 440 - 700 cycles per wave and iteration).  Issuing them one
-    // at a time from inside the matrix stages (dma_one<J>, experiment ABL 5) moved that wait into the stages and changed
-    // nothing in total, so the group goes out at the barrier.
+    // at a time from inside the matrix stages moved that wait into the stages and changed nothing in total, so the group
+    // goes out at the barrier.
     int64_t dma_o1 = 0, dma_o2 = 0;     // byte offsets of the chunks being fetched this iteration
     char* dma_base = smem;
     auto dma_begin = [&](int c1, int c2, int buf) __attribute__((always_inline)) {
@@ -305,18 +243,15 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     };
     auto dma_one = [&](auto jc) __attribute__((always_inline)) {
         constexpr int j = decltype(jc)::value;
-        if constexpr (j < kPerWave) {
-            const int q = q_of(j);                    // wave-uniform
-            if (q < 0) return;
-            if constexpr (ABL == 36) { if (q >= kW1Dma && dma_o1 > kW1Src) return; }      // experiment: half the bytes
-            const char* src = (q < kW1Dma ? W1b + dma_o1 : W2b + dma_o2) + soff[j];
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dma_base + q * 1024), 16, 0, 0);
-        }
+        const int q = q_of(j);                    // wave-uniform
+        if (q < 0) return;
+        const char* src = (q < kW1Dma ? W1b + dma_o1 : W2b + dma_o2) + soff[j];
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(dma_base + q * 1024), 16, 0, 0);
     };
     auto issue = [&](int c1, int c2, int buf) __attribute__((always_inline)) {     // a whole group at once
         dma_begin(c1, c2, buf);
-        static_for<0, kPerWave>([&](auto jc) { dma_one(jc); });
+        static_for<0, kDmaPerWave>([&](auto jc) { dma_one(jc); });
     };
     bf16x8 xf[12];   // B operands of product 1: LN(x)[row rg*32 + l31][this half's 192 features], k-step ks = 16 features
     f32x16 acc2[6];
@@ -335,33 +270,32 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     const uint32_t w2a1 = lds0 + kW1Bytes + (192 * half + l31) * 64 + 16 * ((2 + h) ^ psw);  //                        (k-step 1)
     const uint32_t pa0 = lds0 + kPOff + rg * 2048 + l31 * 64 + 16 * ((0 + h) ^ psw);         // + 8192 parity
     const uint32_t pa1 = lds0 + kPOff + rg * 2048 + l31 * 64 + 16 * ((2 + h) ^ psw);
-    constexpr int kRing = 4;   // operand fragments in flight per matrix stage (6: 246 VGPRs, measured 2 % slower)
+    constexpr int kRing = 4;   // operand fragments in flight per matrix stage (a ring of 6: 246 VGPRs, measured 2 % slower)
     bf16x8 r1[kRing];          // product 1 ring: W1 fragments
     bf16x8 r2[kRing], pb[2];   // product 2 ring: W2 fragments; the two P fragments
 
     auto prefetch1 = [&](int it) __attribute__((always_inline)) {     // first 4 W1 fragments of chunk `it`
         const uint32_t a = w1a + (it & 1) * kWbuf;
-        if constexpr (ABL != 11)
+        if constexpr (MODE != kProbeNoReads)
             static_for<0, kRing>([&](auto kc) { lds_read_b128_asm<32 * decltype(kc)::value>(r1[decltype(kc)::value], a); });
     };
-    auto product1 = [&](int it, bool dma) __attribute__((always_inline)) {   // S = W1[chunk it][:, this half of K] · xfᵀ ; send 8, keep 8
+    auto product1 = [&](int it) __attribute__((always_inline)) {   // S = W1[chunk it][:, this half of K] · xfᵀ ; send 8, keep 8
         const uint32_t a = w1a + (it & 1) * kWbuf;
         f32x16 S;
 #pragma unroll
         for (int r = 0; r < 16; ++r) S[r] = 0.f;
-        if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
+        // matrix stages run at raised priority (102.8 -> 101.7 us, same results; one static priority per half instead of the
+        // per-stage flips measured no better: DESIGN §4.1)
+        __builtin_amdgcn_s_setprio(1);
         static_for<0, 12>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
-            if constexpr (ABL != 11) lds_wait<(11 - ks) < kRing - 1 ? (11 - ks) : kRing - 1>();   // fragment ks is in; younger reads may be in flight
+            if constexpr (MODE != kProbeNoReads) lds_wait<(11 - ks) < kRing - 1 ? (11 - ks) : kRing - 1>();   // fragment ks is in; younger reads may be in flight
             __builtin_amdgcn_sched_barrier(0);
             S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(r1[ks % kRing], xf[ks], S, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (ks + kRing < 12 && ABL != 11) lds_read_b128_asm<32 * (ks + kRing)>(r1[ks % kRing], a);
-            if constexpr ((ks & 3) == 1) {
-                if (dma) dma_one(std::integral_constant<int, ks / 4>{});           // DMA instructions 0, 1, 2
-            }
+            if constexpr (ks + kRing < 12 && MODE != kProbeNoReads) lds_read_b128_asm<32 * (ks + kRing)>(r1[ks % kRing], a);
         });
-        if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         // S[r] = partial H[hidden (r & 3) + 8 (r >> 2) + 4 h][row l31]; half 0 finishes r < 8, half 1 finishes r >= 8
         f32x4* xc = reinterpret_cast<f32x4*>(smem + kXcOff + ((it & 1) * 8 + wave) * 2048 + lane * 16);   // two 1-KB planes
         f32x4 s0, s1v;
@@ -379,8 +313,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
         xc[0] = s0;
         xc[64] = s1v;
     };
-    constexpr bool kDmaInFinish = ABL == 40;
-    auto finish = [&](int c, bool dma_here = false) __attribute__((always_inline)) {         // chunk c: own + partner's partial sums -> GELU -> bf16 -> P tile
+    auto finish = [&](int c) __attribute__((always_inline)) {         // chunk c: own + partner's partial sums -> GELU -> bf16 -> P tile
         const f32x4* pc = reinterpret_cast<const f32x4*>(smem + kXcOff + ((c & 1) * 8 + (wave ^ 4)) * 2048 + lane * 16);
         const f32x4 a0 = pc[0], a1 = pc[64];
         float g[8];
@@ -389,16 +322,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             g[i] = keep[i] + a0[i];
             g[4 + i] = keep[4 + i] + a1[i];
         }
-        if constexpr (kDmaInFinish) {
-            // this wave's DMA instructions of the iteration's group between the GELU's levels: ~60 cycles apart instead of a burst
-            // of 49 from eight waves at the barrier, which queues on the CU's one address path (stamped: 70 - 115 cycles each)
-            gelu8_bf16_grade_hooked(g, [&](auto lc) {
-                constexpr int lv = decltype(lc)::value;
-                if constexpr (lv < kPerWave) {
-                    if (dma_here) dma_one(std::integral_constant<int, lv>{});
-                }
-            });
-        } else if constexpr (kTanh) gelu8_tanh_form(g); else gelu8_bf16_grade(g);
+        gelu8_bf16_grade(g);
         char* pt = smem + kPOff + ((c & 1) * 4 + rg) * 2048 + l31 * 64 + 8 * h;
 #pragma unroll
         for (int gq = 0; gq < 2; ++gq) {
@@ -416,38 +340,30 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     };
     auto prefetch2 = [&](int it) __attribute__((always_inline)) {     // the P fragments and the first 4 W2 fragments
         const uint32_t b0 = w2a0 + (it & 1) * kWbuf, b1 = w2a1 + (it & 1) * kWbuf;
-        if constexpr (ABL != 11) {
+        if constexpr (MODE != kProbeNoReads) {
             lds_read_b128_asm<0>(pb[0], pa0 + (it & 1) * 8192);
             lds_read_b128_asm<0>(pb[1], pa1 + (it & 1) * 8192);
             static_for<0, kRing>([&](auto jc) { w2read(jc, b0, b1); });
         }
     };
-    auto product2_at = [&](uint32_t b0, uint32_t b1, bool dma) __attribute__((always_inline)) {   // (b0 / b1: the W2 image's k-step 0 / 1 addresses)
-        if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
+    auto product2_at = [&](uint32_t b0, uint32_t b1) __attribute__((always_inline)) {   // (b0 / b1: the W2 image's k-step 0 / 1 addresses)
+        __builtin_amdgcn_s_setprio(1);
         static_for<0, 12>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
-            if constexpr (ABL != 11) lds_wait<(11 - j) < kRing - 1 ? (11 - j) : kRing - 1>();
+            if constexpr (MODE != kProbeNoReads) lds_wait<(11 - j) < kRing - 1 ? (11 - j) : kRing - 1>();
             __builtin_amdgcn_sched_barrier(0);
             acc2[j >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(r2[j % kRing], pb[j & 1], acc2[j >> 1], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (j + kRing < 12 && ABL != 11) w2read(std::integral_constant<int, j + kRing>{}, b0, b1);
-            if constexpr ((j & 3) == 1) {
-                if (dma) dma_one(std::integral_constant<int, 3 + j / 4>{});        // DMA instructions 3, 4, 5
-            }
-            if constexpr (j == 10) {
-                if (dma) dma_one(std::integral_constant<int, 6>{});                // (wave 0 only)
-            }
+            if constexpr (j + kRing < 12 && MODE != kProbeNoReads) w2read(std::integral_constant<int, j + kRing>{}, b0, b1);
         });
-        if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
-    auto product2 = [&](int it, bool dma) __attribute__((always_inline)) {   // acc2 += W2[this half's 192 features][chunk it - 2] · Pᵀ
-        product2_at(w2a0 + (it & 1) * kWbuf, w2a1 + (it & 1) * kWbuf, dma);
+    auto product2 = [&](int it) __attribute__((always_inline)) {   // acc2 += W2[this half's 192 features][chunk it - 2] · Pᵀ
+        product2_at(w2a0 + (it & 1) * kWbuf, w2a1 + (it & 1) * kWbuf);
     };
 
     // ---- prologue (a lambda: projection mode runs it INSIDE the two branches that select the main loop's stage order - with the
     // accumulators live across that branch hipcc has to agree on one register assignment for both loop copies and spills 76 VGPRs)
-    constexpr bool qkv_mode = ABL == kProjQkvMode;
-    constexpr bool proj_mode = ABL == kProjMode || qkv_mode || ABL == kSplitProjMode;
     auto prologue = [&]() __attribute__((always_inline)) {
     if constexpr (proj_mode) {
         // Projection mode: this row block's residual rows start in the accumulators of product 2 and the attention block's
@@ -496,7 +412,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             gload_b128_asm<64 * c>(af[c % 3][0], orow);
             gload_b128_asm<64 * c + 32>(af[c % 3][1], orow);
         };
-        static_for<0, kPerWave>([&](auto jc) { dma_w1_0(jc); });      // (its W1 area is not touched before the main loop)
+        static_for<0, kDmaPerWave>([&](auto jc) { dma_w1_0(jc); });      // (its W1 area is not touched before the main loop)
         {
             const float* xr = p.x + (int64_t)rr * p.ldx + 192 * half + 4 * h;
 #pragma unroll
@@ -522,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             pb[1] = __builtin_bit_cast(bf16x8, af[c % 3][1] & row_on);
             const uint32_t b0 = w2a0 - kW1Bytes + kPjBuf[c % 3], b1 = w2a1 - kW1Bytes + kPjBuf[c % 3];
             static_for<0, kRing>([&](auto jc) { w2read(jc, b0, b1); });
-            product2_at(b0, b1, false);
+            product2_at(b0, b1);
         });
         __syncthreads();     // (everyone is done with the last chunks: the sums below and the tile go over their buffers)
         // LayerNorm of x1 from the accumulators; the partner wave's sums come through buffer 0's W2 area
@@ -646,7 +562,8 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
     // precedes product 1, which overwrites the partial sums it consumes): whenever one wave of a SIMD is in its VALU stage
     // the other is in a matrix stage.  The whole loop exists twice, once per order, selected ONCE: a per-iteration choice
     // (a branch or a rotation loop around the stages) turns the 96 accumulators into loop-carried phi copies - twice the
-    // registers, spills, and 96 moves per iteration.
+    // registers, spills, and 96 moves per iteration.  (A two-slot schedule - per iteration two barrier-separated slots, in each
+    // one wave of a SIMD runs both products while its partner does its vector work - measured the same: DESIGN §4.1.)
     auto main_loop = [&](auto order) __attribute__((always_inline)) {
         constexpr int kOrder = decltype(order)::value;
 #pragma unroll 1
@@ -656,146 +573,45 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             stamp(1);
             // group it+1 = {W1 chunk it+1, W2 chunk it-1} (indices clamped at the pipeline's ends) into the buffer iteration
             // it-1 released; nothing in the last iteration (the epilogue reuses the buffers right after the loop)
-            bool dma = it <= nchunks && (ABL != 1 || it < 2);
+            const bool dma = it <= nchunks && (MODE != kProbeNoDma || it < 2);
             dma_begin(it + 1 < nchunks ? it + 1 : nchunks - 1, it < 1 ? 0 : (it <= nchunks ? it - 1 : nchunks - 1), (it + 1) & 1);
-            const bool p1 = ABL != 2 && it < nchunks, fi = ABL != 2 && ABL != 10 && it >= 1 && it <= nchunks, p2 = ABL != 2 && it >= 2;
-            // a stage that does not run this iteration (pipeline fill / drain) cannot carry its share of the DMA group
-            if constexpr (kDmaHalf0) {   // experiment: half 0 (which waits at the barrier anyway) issues the whole group
-                if (dma && half == 0) {
-                    static_for<0, 13>([&](auto jc) {
-                        constexpr int j = decltype(jc)::value;
-                        const int q = wave + 4 * j;
-                        if (q < kW1Dma + 24) {
-                            const uint32_t t = 64u * (q < kW1Dma ? q : q - kW1Dma) + lane;
-                            uint32_t so;
-                            if (q < kW1Dma) {
-                                uint32_t r = t / 49u, c = t - r * 49u;
-                                r = r < 32u ? r : 31u;
-                                c = c < 48u ? c : 47u;
-                                so = r * 768u + 16u * c;
-                            } else {
-                                const uint32_t r = t >> 2, c = t & 3u;
-                                so = r * 64u + 16u * (c ^ ((r >> 2) & 3u));
-                            }
-                            const char* src = (q < kW1Dma ? W1b + dma_o1 : W2b + dma_o2) + so;
-                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                             (__attribute__((address_space(3))) void*)(smem + ((it + 1) & 1) * kWbuf + q * 1024), 16, 0, 0);
-                        }
-                    });
-                }
-                dma = false;
-            }
-            bool dma_fin = false;
-            if constexpr (kDmaInFinish) {
-                if (dma && fi) { dma_fin = true; dma = false; }      // (pipeline fill: no finish stage yet - the group goes out at the barrier)
-            }
-            if (ABL != 5) {        // the whole group right behind the barrier (ABL == 5, experiment: one instruction at a time
-                                   // from inside the matrix stages - measured no faster, and hipcc then drops the vmcnt(0)
-                                   // in front of the barrier: racy without the explicit wait below)
-                if (dma) static_for<0, kPerWave>([&](auto jc) { dma_one(jc); });
-                dma = false;
-            }
-            if (dma && !p1) static_for<0, 3>([&](auto jc) { dma_one(jc); });
-            if (dma && !p2) static_for<3, kPerWave>([&](auto jc) { dma_one(jc); });
+            const bool p1 = MODE != kProbeDmaOnly && it < nchunks,
+                       fi = MODE != kProbeDmaOnly && MODE != kProbeNoFinish && it >= 1 && it <= nchunks,
+                       p2 = MODE != kProbeDmaOnly && it >= 2;
+            if (dma) static_for<0, kDmaPerWave>([&](auto jc) { dma_one(jc); });     // the whole group right behind the barrier
             stamp(2);
             if constexpr (kOrder == 0) {
                 if (p1) prefetch1(it);
-                if (fi) finish(it - 1, dma_fin);
+                if (fi) finish(it - 1);
                 stamp(3);
-                if (p1) product1(it, dma);
+                if (p1) product1(it);
                 stamp(4);
                 if (p2) {
                     prefetch2(it);
-                    product2(it, dma);
+                    product2(it);
                 }
                 stamp(5);
             } else {
                 if (p2) {
                     prefetch2(it);
-                    product2(it, dma);
+                    product2(it);
                 }
                 stamp(5);
                 if (p1) prefetch1(it);
-                if (fi) finish(it - 1, dma_fin);
+                if (fi) finish(it - 1);
                 stamp(3);
-                if (p1) product1(it, dma);
+                if (p1) product1(it);
                 stamp(4);
             }
         }
     };
-    // ---- TWO-SLOT schedule (experiment ABL 30 - 33).  The loop above pairs three stages per wave (one vector, two matrix), so one
-    // pairing per iteration is matrix beside matrix and two are a 900-cycle vector stage beside a 384-cycle matrix stage: the
-    // matrix pipe idles under the vector stages.  Here an iteration is two slots, a workgroup barrier in front of each; in a
-    // slot one wave of every SIMD runs BOTH products of its chunk back to back (24 MFMAs) while its partner runs its vector
-    // work (finish of the previous chunk + its share of the DMA group), then they swap:
-    //     slot A(k):  half 1: product 1 (chunk k), product 2 (chunk k-2)      half 0: DMA part of group k+1, finish (chunk k-1)
-    //     slot B(k):  half 0: product 1 (chunk k), product 2 (chunk k-2)      half 1: DMA part of group k+1, finish (chunk k-1)
-    // Hand-offs as before (exchange planes and P tiles by chunk parity, weight buffers by iteration parity), each one slot
-    // boundary or more apart.  Half 1 finishes chunk k-1 AFTER it has started chunk k: its own eight partial sums of k-1 are
-    // carried in a second register set.  Half 0's DMA share has two slots to land, half 1's one: half 1 gets the smaller share.
-    constexpr bool kSlot2 = ABL >= 30 && ABL <= 35;     // (35: two-slot WITHOUT weight DMA after the first groups: compute-bound timing, wrong results)
-    if constexpr (kSlot2) {
-        auto dma_mine = [&]() __attribute__((always_inline)) { static_for<0, kPerWave>([&](auto jc) { dma_one(jc); }); };
-        if (half == 0) {
-#pragma unroll 1
-            for (int k = 0; k <= nchunks + 1; ++k) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's share of group k (issued in slot A(k-1))
-                __syncthreads();                                        // ---- slot A(k)
-                stamp(1);
-                dma_begin(k + 1 < nchunks ? k + 1 : nchunks - 1, k < 1 ? 0 : (k <= nchunks ? k - 1 : nchunks - 1), (k + 1) & 1);
-                if (k <= nchunks && (ABL != 35 || k < 2)) dma_mine();
-                stamp(2);
-                if (k >= 1 && k <= nchunks) finish(k - 1);
-                stamp(3);
-                __syncthreads();                                        // ---- slot B(k)
-                stamp(1);
-                if (k < nchunks) { prefetch1(k); product1(k, false); }
-                stamp(4);
-                if (k >= 2) { prefetch2(k); product2(k, false); }
-                stamp(5);
-            }
-        } else {
-            float keep_prev[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) keep_prev[i] = 0.f;
-#pragma unroll 1
-            for (int k = 0; k <= nchunks + 1; ++k) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's share of group k (issued in slot B(k-1))
-                __syncthreads();                                        // ---- slot A(k)
-                stamp(1);
-                if (k < nchunks) { prefetch1(k); product1(k, false); }     // (writes keep[])
-                stamp(4);
-                if (k >= 2) { prefetch2(k); product2(k, false); }
-                stamp(5);
-                __syncthreads();                                        // ---- slot B(k)
-                stamp(1);
-                dma_begin(k + 1 < nchunks ? k + 1 : nchunks - 1, k < 1 ? 0 : (k <= nchunks ? k - 1 : nchunks - 1), (k + 1) & 1);
-                if (k <= nchunks && (ABL != 35 || k < 2)) dma_mine();
-                stamp(2);
-                // finish(k - 1) on the partial sums of chunk k-1: swap them in for the duration of the stage
-                float keep_now[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { keep_now[i] = keep[i]; keep[i] = keep_prev[i]; }
-                if (k >= 1 && k <= nchunks) finish(k - 1);
-                stamp(3);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) keep_prev[i] = keep_now[i];
-            }
-        }
-    } else
-    if constexpr (kStaticPrio) {     // experiment: the younger half of every SIMD at raised priority for the whole loop, no per-stage flips
-        if (half == 1) __builtin_amdgcn_s_setprio(1);
+    if (half == 0) {
+        if constexpr (proj_mode) prologue();
+        main_loop(std::integral_constant<int, 0>{});
+    } else {
+        if constexpr (proj_mode) prologue();
+        main_loop(std::integral_constant<int, 1>{});
     }
-    if constexpr (!kSlot2) {
-        if (half == 0) {
-            if constexpr (proj_mode) prologue();
-            main_loop(std::integral_constant<int, 0>{});
-        } else {
-            if constexpr (proj_mode) prologue();
-            main_loop(std::integral_constant<int, 1>{});
-        }
-    }
-    if constexpr (kStaticPrio) __builtin_amdgcn_s_setprio(0);
 
     // ---- epilogue of the q/kv mode: 32 rows per pass through the fp32 tile (mask, coalesced stores, row statistics as below) and
     // from the same registers the NEXT layer's attention_norm of the finished rows, bf16, into a second tile - then that
@@ -906,7 +722,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             const uint32_t a = wa + buf * kQChunk;
             lds_read_b128_asm<0>(bq, xb + 16 * ((2 * c + h) ^ (l31 & 15)));
             static_for<0, kRing>([&](auto tc) { lds_read_b128_asm<1024 * decltype(tc)::value>(r2[decltype(tc)::value], a); });
-            if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
             static_for<0, 8>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 lds_wait<(7 - t) < kRing - 1 ? (7 - t) : kRing - 1>();
@@ -915,7 +731,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (t + kRing < 8) lds_read_b128_asm<1024 * (t + kRing)>(r2[t % kRing], a);
             });
-            if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             buf = buf == 2 ? 0 : buf + 1;
         }
         __syncthreads();     // both tiles and the ring are dead: the staging tile goes over them
@@ -994,11 +810,11 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
                 y[j] = a;
                 s += (a[0] + a[1]) + (a[2] + a[3]);
             }
-            if (live && (ABL != kProjMode || p.out)) {
+            if (live && (MODE != kProjMode || p.out)) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) *reinterpret_cast<f32x4*>(outp + (int64_t)r * p.ldo + 4 * (l31 + 32 * j)) = y[j];
             }
-            if constexpr (ABL == kProjMode) {
+            if constexpr (MODE == kProjMode) {
                 if (p.ln_out) {      // the stack's final LayerNorm (transformer.py:205-206) from the same registers
                     float sum = s;
 #pragma unroll
@@ -1056,7 +872,7 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             }
         }
     }
-    if constexpr (ABL == 3 || ABL == 34) {
+    if constexpr (MODE == kProbeStamps) {
         stamp(6);
         ts[7] = t_prev - t_first;
         if (lane == 0 && p.stamps) {
@@ -1179,27 +995,70 @@ __global__ __launch_bounds__(256) void ffn_combine_ln_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the eight-wave entry points
+// What differs between their argument checks (the rest is ffn2_check)
+struct Ffn2Entry {
+    const char* name;                  // for the messages
+    int min_inner;
+    uint32_t flags_ok;                 // permitted flags
+    bool proj;                         // takes the projection prologue's operands (attn_out, Wo_chunks)
+    bool out_optional = false;
+    int32_t no_mask = ISPK_E_NULL;     // the answer to a mask flag without a mask
+};
+
+// The checks, in one order for every entry point: null pointers; dim; rows / inner shape; permitted flags; mask flag without a
+// mask; strides and 16-byte alignment.  An entry point's further operands come in as the three `more_*` conditions, which the
+// caller evaluates (they only look at argument values); split entries pass their parts as p.out with ldo = 384.
+static int32_t ffn2_check(const Ffn2Entry& e, const Ffn2Params& p, int32_t dim, bool more_present = true, bool more_shape = true,
+                          bool more_aligned = true) {
+    ISPK_REQUIRE(p.x && p.gamma && p.beta && p.W1 && p.W2c && (!e.proj || (p.o && p.WoC)) && (e.out_optional || p.out) && more_present,
+                 ISPK_E_NULL, "%s: null pointer", e.name);
+    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "%s: dim %d (built for 384)", e.name, dim);
+    ISPK_REQUIRE(p.rows >= 0 && p.inner >= e.min_inner && p.inner % 32 == 0 && more_shape, ISPK_E_SHAPE,
+                 "%s: bad shape rows=%d inner=%d (inner: a multiple of 32, at least %d; split: the chunks of 32 divide evenly among "
+                 "the splits, >= 2 each, and part_stride >= rows * 384)", e.name, p.rows, p.inner, e.min_inner);
+    ISPK_REQUIRE((p.flags & ~e.flags_ok) == 0, ISPK_E_UNSUPPORTED, "%s: unsupported flags", e.name);
+    ISPK_REQUIRE(!(((p.flags & (ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) || p.ln_mask) && !p.mask), e.no_mask,
+                 "%s: mask flag without mask", e.name);
+    ISPK_REQUIRE(p.ldx % 4 == 0 && p.ldx >= dim && ispk_aligned(p.x, 16) && ispk_aligned(p.W1, 16) && ispk_aligned(p.W2c, 16) &&
+                     ispk_aligned(p.gamma, 16) && ispk_aligned(p.beta, 16) &&
+                     (!e.proj || (p.ld_o % 8 == 0 && p.ld_o >= dim && ispk_aligned(p.o, 16) && ispk_aligned(p.WoC, 16))) &&
+                     (!p.out || (p.ldo % 4 == 0 && p.ldo >= dim && ispk_aligned(p.out, 16))) &&
+                     (!p.stats || ispk_aligned(p.stats, 8)) && more_aligned,
+                 ISPK_E_ALIGN, "%s: 16-byte alignment / strides that are multiples of 4 (fp32) and 8 (bf16) required", e.name);
+    return 0;
+}
+
+// Reserve the LDS (once per instance), launch, status.  (Not ISPK_RESERVE_LDS: its message prefix has to be a string literal.)
+template <int MODE>
+static int32_t ffn2_launch(const Ffn2Params& p, dim3 grid, hipStream_t stream, const char* what) {
+    static std::atomic<bool> reserved{false};
+    if (!reserved.load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn2_bf16_kernel<MODE>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+        if (e != hipSuccess) ISPK_FAIL((int32_t)e, "%s: cannot reserve %d B of LDS: %s", what, kLds, hipGetErrorString(e));
+        reserved.store(true, std::memory_order_release);
+    }
+    hipLaunchKernelGGL(ffn2_bf16_kernel<MODE>, grid, dim3(512), kLds, stream, p);
+    return ispk_launch_status();
+}
+
+static bool ffn2_splits_ok(int32_t splits, int32_t rows, int32_t inner, int64_t part_stride) {
+    return splits >= 1 && (inner / 32) % splits == 0 && (inner / 32) / splits >= 2 && part_stride >= (int64_t)rows * kD;
+}
+
 extern "C" int32_t ispk_ffn_bf16_prenorm2_split(const float* x, int64_t ldx, const float* norm_gamma, const float* norm_beta,
                                                 float norm_eps, const uint16_t* W1, const uint16_t* W2_chunks, float* parts,
                                                 int64_t part_stride, int32_t splits, int32_t rows, int32_t dim, int32_t inner,
                                                 ispk_stream_t stream) {
-    ISPK_REQUIRE(x && norm_gamma && norm_beta && W1 && W2_chunks && parts, ISPK_E_NULL, "ffn_prenorm2_split: null pointer");
-    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "ffn_prenorm2_split: dim %d (built for 384)", dim);
-    ISPK_REQUIRE(rows >= 0 && inner >= 32 && inner % 32 == 0 && splits >= 1 && (inner / 32) % splits == 0 &&
-                     (inner / 32) / splits >= 2 && part_stride >= (int64_t)rows * kD,
-                 ISPK_E_SHAPE, "ffn_prenorm2_split: bad shape rows=%d inner=%d splits=%d (chunks of 32 must divide evenly, >= 2 each)",
-                 rows, inner, splits);
-    ISPK_REQUIRE(ldx % 4 == 0 && ldx >= dim && part_stride % 4 == 0 && ispk_aligned(x, 16) && ispk_aligned(parts, 16) &&
-                     ispk_aligned(W1, 16) && ispk_aligned(W2_chunks, 16) && ispk_aligned(norm_gamma, 16) &&
-                     ispk_aligned(norm_beta, 16), ISPK_E_ALIGN, "ffn_prenorm2_split: 16-byte alignment required");
-    if (rows == 0) return 0;
     Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, nullptr, parts, kD, rows, inner, 0u, nullptr, 0.f};
+    if (int32_t rc = ffn2_check({"ffn_prenorm2_split", 32, 0u, false}, p, dim, true, ffn2_splits_ok(splits, rows, inner, part_stride),
+                                part_stride % 4 == 0))
+        return rc;
+    if (rows == 0) return 0;
     p.chunk_count = (inner / 32) / splits;
     p.part_stride = part_stride;
-    ISPK_RESERVE_LDS((&ffn2_bf16_kernel<kSplitMode>), kLds, "ffn_prenorm2_split");
-    hipLaunchKernelGGL(ffn2_bf16_kernel<kSplitMode>, dim3((rows + 127) / 128, splits), dim3(512), kLds,
-                       reinterpret_cast<hipStream_t>(stream), p);
-    return ispk_launch_status();
+    return ffn2_launch<kSplitMode>(p, dim3((rows + 127) / 128, splits), reinterpret_cast<hipStream_t>(stream), "ffn_prenorm2_split");
 }
 
 // Small batches, with the attention block's output projection as the prologue of EVERY split (each needs LN(x1); split 0's partial
@@ -1209,30 +1068,18 @@ extern "C" int32_t ispk_attn_out_ffn_split_bf16(const float* x, int64_t ldx, con
                                                 float norm_eps, const uint16_t* W1, const uint16_t* W2_chunks,
                                                 const uint8_t* mask, uint32_t flags, float* parts, int64_t part_stride,
                                                 int32_t splits, int32_t rows, int32_t dim, int32_t inner, ispk_stream_t stream) {
-    ISPK_REQUIRE(x && attn_out && Wo_chunks && norm_gamma && norm_beta && W1 && W2_chunks && parts, ISPK_E_NULL,
-                 "attn_out_ffn_split: null pointer");
-    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "attn_out_ffn_split: dim %d (built for 384 = heads * 64)", dim);
-    ISPK_REQUIRE(rows >= 0 && inner >= 32 && inner % 32 == 0 && splits >= 1 && (inner / 32) % splits == 0 &&
-                     (inner / 32) / splits >= 2 && part_stride >= (int64_t)rows * kD,
-                 ISPK_E_SHAPE, "attn_out_ffn_split: bad shape rows=%d inner=%d splits=%d (chunks of 32 must divide evenly, >= 2 each)",
-                 rows, inner, splits);
-    ISPK_REQUIRE((flags & ~ISPK_EP_MASK_ACC) == 0 && !((flags & ISPK_EP_MASK_ACC) && !mask), ISPK_E_UNSUPPORTED,
-                 "attn_out_ffn_split: flags other than MASK_ACC (with a mask) are the combine pass's business");
-    ISPK_REQUIRE(ldx % 4 == 0 && ldx >= dim && ld_attn % 8 == 0 && ld_attn >= dim && part_stride % 4 == 0 && ispk_aligned(x, 16) &&
-                     ispk_aligned(attn_out, 16) && ispk_aligned(Wo_chunks, 16) && ispk_aligned(parts, 16) && ispk_aligned(W1, 16) &&
-                     ispk_aligned(W2_chunks, 16) && ispk_aligned(norm_gamma, 16) && ispk_aligned(norm_beta, 16),
-                 ISPK_E_ALIGN, "attn_out_ffn_split: 16-byte alignment required");
-    if (rows == 0) return 0;
     Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, mask, parts, kD, rows, inner, flags, nullptr, 0.f};
-    p.chunk_count = (inner / 32) / splits;
-    p.part_stride = part_stride;
     p.o = attn_out;
     p.ld_o = ld_attn;
     p.WoC = Wo_chunks;
-    ISPK_RESERVE_LDS((&ffn2_bf16_kernel<kSplitProjMode>), kLds, "attn_out_ffn_split");
-    hipLaunchKernelGGL(ffn2_bf16_kernel<kSplitProjMode>, dim3((rows + 127) / 128, splits), dim3(512), kLds,
-                       reinterpret_cast<hipStream_t>(stream), p);
-    return ispk_launch_status();
+    // (MASK_OUT is the combine pass's business; and here a mask flag without a mask is UNSUPPORTED, not NULL)
+    if (int32_t rc = ffn2_check({"attn_out_ffn_split", 32, ISPK_EP_MASK_ACC, true, false, ISPK_E_UNSUPPORTED}, p, dim, true,
+                                ffn2_splits_ok(splits, rows, inner, part_stride), part_stride % 4 == 0))
+        return rc;
+    if (rows == 0) return 0;
+    p.chunk_count = (inner / 32) / splits;
+    p.part_stride = part_stride;
+    return ffn2_launch<kSplitProjMode>(p, dim3((rows + 127) / 128, splits), reinterpret_cast<hipStream_t>(stream), "attn_out_ffn_split");
 }
 
 extern "C" int32_t ispk_ffn_combine_ln_f32(const float* x, int64_t ldx, const float* parts, int64_t part_stride, int32_t splits,
@@ -1268,17 +1115,11 @@ static int32_t attn_out_ffn_launch(const float* x, int64_t ldx, const uint16_t* 
                                    int32_t rows, int32_t dim, int32_t inner, uint32_t flags, float* row_stats, float stats_eps,
                                    const float* next_gamma, const float* next_beta, float next_eps, const uint16_t* Wqkv_chunks,
                                    uint16_t* qkv, int64_t ld_qkv, bool with_qkv, ispk_stream_t stream) {
-    ISPK_REQUIRE(x && attn_out && Wo_chunks && norm_gamma && norm_beta && W1 && W2_chunks && out, ISPK_E_NULL,
-                 "attn_out_ffn: null pointer");
-    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "attn_out_ffn: dim %d (built for 384 = heads * 64)", dim);
-    ISPK_REQUIRE(rows >= 0 && inner >= 64 && inner % 32 == 0, ISPK_E_SHAPE, "attn_out_ffn: bad shape rows=%d inner=%d", rows, inner);
-    ISPK_REQUIRE((flags & ~(ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) == 0, ISPK_E_UNSUPPORTED, "attn_out_ffn: unsupported flags");
-    ISPK_REQUIRE(!((flags & (ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) && !mask), ISPK_E_NULL, "attn_out_ffn: mask flag without mask");
-    ISPK_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ld_attn % 8 == 0 && ldx >= dim && ldo >= dim && ld_attn >= dim &&
-                     ispk_aligned(x, 16) && ispk_aligned(out, 16) && ispk_aligned(attn_out, 16) && ispk_aligned(Wo_chunks, 16) &&
-                     ispk_aligned(W1, 16) && ispk_aligned(W2_chunks, 16) && ispk_aligned(norm_gamma, 16) &&
-                     ispk_aligned(norm_beta, 16) && (!row_stats || ispk_aligned(row_stats, 8)),
-                 ISPK_E_ALIGN, "attn_out_ffn: 16-byte alignment / strides that are multiples of 4 (fp32) and 8 (bf16) required");
+    Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, mask, out, ldo, rows, inner, flags, row_stats, stats_eps};
+    p.o = attn_out;
+    p.ld_o = ld_attn;
+    p.WoC = Wo_chunks;
+    if (int32_t rc = ffn2_check({"attn_out_ffn", 64, ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC, true}, p, dim)) return rc;
     if (with_qkv) {
         ISPK_REQUIRE(next_gamma && next_beta && Wqkv_chunks && qkv, ISPK_E_NULL, "attn_out_ffn_qkv: null pointer");
         ISPK_REQUIRE(ld_qkv >= kNq && ld_qkv % 8 == 0 && ispk_aligned(qkv, 16) && ispk_aligned(Wqkv_chunks, 16) &&
@@ -1286,26 +1127,16 @@ static int32_t attn_out_ffn_launch(const float* x, int64_t ldx, const uint16_t* 
                      ISPK_E_ALIGN, "attn_out_ffn_qkv: q/kv rows of 512 bf16, 16-byte aligned, row stride a multiple of 8");
     }
     if (rows == 0) return 0;
-    Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, mask, out, ldo, rows, inner, flags, row_stats, stats_eps};
-    p.o = attn_out;
-    p.ld_o = ld_attn;
-    p.WoC = Wo_chunks;
     const dim3 grid((rows + 127) / 128);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (with_qkv) {
-        p.gamma2 = next_gamma;
-        p.beta2 = next_beta;
-        p.eps2 = next_eps;
-        p.WqC = Wqkv_chunks;
-        p.qkv = qkv;
-        p.ld_qkv = ld_qkv;
-        ISPK_RESERVE_LDS((&ffn2_bf16_kernel<kProjQkvMode>), kLds, "attn_out_ffn_qkv");
-        hipLaunchKernelGGL(ffn2_bf16_kernel<kProjQkvMode>, grid, dim3(512), kLds, s, p);
-    } else {
-        ISPK_RESERVE_LDS((&ffn2_bf16_kernel<kProjMode>), kLds, "attn_out_ffn");
-        hipLaunchKernelGGL(ffn2_bf16_kernel<kProjMode>, grid, dim3(512), kLds, s, p);
-    }
-    return ispk_launch_status();
+    if (!with_qkv) return ffn2_launch<kProjMode>(p, grid, s, "attn_out_ffn");
+    p.gamma2 = next_gamma;
+    p.beta2 = next_beta;
+    p.eps2 = next_eps;
+    p.WqC = Wqkv_chunks;
+    p.qkv = qkv;
+    p.ld_qkv = ld_qkv;
+    return ffn2_launch<kProjQkvMode>(p, grid, s, "attn_out_ffn_qkv");
 }
 
 extern "C" int32_t ispk_attn_out_ffn_bf16(const float* x, int64_t ldx, const uint16_t* attn_out, int64_t ld_attn,
@@ -1325,20 +1156,6 @@ extern "C" int32_t ispk_attn_out_ffn_norm_bf16(const float* x, int64_t ldx, cons
                                                float* out, int64_t ldo, int32_t rows, int32_t dim, int32_t inner, uint32_t flags,
                                                const float* final_gamma, const float* final_beta, float final_eps, int32_t ln_mask,
                                                void* ln_out, int64_t ld_ln, int32_t ln_bf16, ispk_stream_t stream) {
-    ISPK_REQUIRE(x && attn_out && Wo_chunks && norm_gamma && norm_beta && W1 && W2_chunks && final_gamma && final_beta && ln_out,
-                 ISPK_E_NULL, "attn_out_ffn_norm: null pointer");
-    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "attn_out_ffn_norm: dim %d (built for 384 = heads * 64)", dim);
-    ISPK_REQUIRE(rows >= 0 && inner >= 64 && inner % 32 == 0, ISPK_E_SHAPE, "attn_out_ffn_norm: bad shape rows=%d inner=%d", rows, inner);
-    ISPK_REQUIRE((flags & ~(ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) == 0, ISPK_E_UNSUPPORTED, "attn_out_ffn_norm: unsupported flags");
-    ISPK_REQUIRE(!(((flags & (ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) || ln_mask) && !mask), ISPK_E_NULL,
-                 "attn_out_ffn_norm: mask flag without mask");
-    ISPK_REQUIRE(ldx % 4 == 0 && ld_attn % 8 == 0 && ldx >= dim && ld_attn >= dim && ld_ln >= dim && ld_ln % 4 == 0 &&
-                     (!out || (ldo % 4 == 0 && ldo >= dim && ispk_aligned(out, 16))) && ispk_aligned(x, 16) &&
-                     ispk_aligned(attn_out, 16) && ispk_aligned(Wo_chunks, 16) && ispk_aligned(W1, 16) && ispk_aligned(W2_chunks, 16) &&
-                     ispk_aligned(norm_gamma, 16) && ispk_aligned(norm_beta, 16) && ispk_aligned(final_gamma, 16) &&
-                     ispk_aligned(final_beta, 16) && ispk_aligned(ln_out, ln_bf16 ? 8 : 16),
-                 ISPK_E_ALIGN, "attn_out_ffn_norm: 16-byte alignment / strides that are multiples of 4 (fp32) and 8 (bf16) required");
-    if (rows == 0) return 0;
     Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, mask, out, ldo, rows, inner, flags, nullptr, 0.f};
     p.o = attn_out;
     p.ld_o = ld_attn;
@@ -1350,9 +1167,13 @@ extern "C" int32_t ispk_attn_out_ffn_norm_bf16(const float* x, int64_t ldx, cons
     p.ld_ln = ld_ln;
     p.ln_bf16 = ln_bf16;
     p.ln_mask = ln_mask;
-    ISPK_RESERVE_LDS((&ffn2_bf16_kernel<kProjMode>), kLds, "attn_out_ffn_norm");
-    hipLaunchKernelGGL(ffn2_bf16_kernel<kProjMode>, dim3((rows + 127) / 128), dim3(512), kLds, reinterpret_cast<hipStream_t>(stream), p);
-    return ispk_launch_status();
+    if (int32_t rc = ffn2_check({"attn_out_ffn_norm", 64, ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC, true, /*out_optional=*/true}, p, dim,
+                                final_gamma && final_beta && ln_out, true,
+                                ld_ln >= dim && ld_ln % 4 == 0 && ispk_aligned(final_gamma, 16) && ispk_aligned(final_beta, 16) &&
+                                    ispk_aligned(ln_out, ln_bf16 ? 8 : 16)))
+        return rc;
+    if (rows == 0) return 0;
+    return ffn2_launch<kProjMode>(p, dim3((rows + 127) / 128), reinterpret_cast<hipStream_t>(stream), "attn_out_ffn_norm");
 }
 
 extern "C" int32_t ispk_attn_out_ffn_qkv_bf16(const float* x, int64_t ldx, const uint16_t* attn_out, int64_t ld_attn,
@@ -1370,97 +1191,22 @@ extern "C" int32_t ispk_ffn_bf16_prenorm2(const float* x, int64_t ldx, const flo
                                           float norm_eps, const uint16_t* W1, const uint16_t* W2_chunks, const uint8_t* mask,
                                           float* out, int64_t ldo, int32_t rows, int32_t dim, int32_t inner, uint32_t flags,
                                           float* row_stats, float stats_eps, ispk_stream_t stream) {
-    ISPK_REQUIRE(x && norm_gamma && norm_beta && W1 && W2_chunks && out, ISPK_E_NULL, "ffn_prenorm2: null pointer");
-    ISPK_REQUIRE(dim == kD, ISPK_E_UNSUPPORTED, "ffn_prenorm2: dim %d (built for 384)", dim);
-    ISPK_REQUIRE(rows >= 0 && inner >= 32 && inner % 32 == 0, ISPK_E_SHAPE, "ffn_prenorm2: bad shape rows=%d inner=%d", rows,
-                 inner);
-    ISPK_REQUIRE((flags & ~(ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) == 0, ISPK_E_UNSUPPORTED, "ffn_prenorm2: unsupported flags");
-    ISPK_REQUIRE(!((flags & (ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC)) && !mask), ISPK_E_NULL, "ffn_prenorm2: mask flag without mask");
-    ISPK_REQUIRE(ldx % 4 == 0 && ldo % 4 == 0 && ldx >= dim && ldo >= dim && ispk_aligned(x, 16) && ispk_aligned(out, 16) &&
-                     ispk_aligned(W1, 16) && ispk_aligned(W2_chunks, 16) && ispk_aligned(norm_gamma, 16) &&
-                     ispk_aligned(norm_beta, 16) && (!row_stats || ispk_aligned(row_stats, 8)),
-                 ISPK_E_ALIGN, "ffn_prenorm2: 16-byte alignment / strides that are multiples of 4 required");
-    if (rows == 0) return 0;
     Ffn2Params p{x, ldx, norm_gamma, norm_beta, norm_eps, W1, W2_chunks, mask, out, ldo, rows, inner, flags, row_stats, stats_eps};
+    if (int32_t rc = ffn2_check({"ffn_prenorm2", 32, ISPK_EP_MASK_OUT | ISPK_EP_MASK_ACC, false}, p, dim)) return rc;
+    if (rows == 0) return 0;
     const dim3 grid((rows + 127) / 128);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 #ifdef ISPK_EXPERIMENTS
-    if (const char* e = ispk_knob("ISPK_FFN2_ABLATE")) {
-        if (atoi(e) == 1) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<1>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<1>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 2) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<2>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<2>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 6) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<6>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<6>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 7) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<7>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<7>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 8) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<8>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<8>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 9) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<9>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<9>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 10) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<10>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<10>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 11) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<11>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<11>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 12) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<12>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<12>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-#define ISPK_FFN2_AB(N_)                                                                    \
-        if (atoi(e) == N_) {                                                                \
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<N_>), kLds, "ffn_prenorm2");               \
-            hipLaunchKernelGGL(ffn2_bf16_kernel<N_>, grid, dim3(512), kLds, s, p);          \
-            return ispk_launch_status();                                                    \
-        }
-        ISPK_FFN2_AB(13) ISPK_FFN2_AB(14) ISPK_FFN2_AB(15) ISPK_FFN2_AB(16) ISPK_FFN2_AB(17) ISPK_FFN2_AB(30) ISPK_FFN2_AB(31) ISPK_FFN2_AB(32) ISPK_FFN2_AB(33) ISPK_FFN2_AB(35) ISPK_FFN2_AB(36) ISPK_FFN2_AB(40)
-#undef ISPK_FFN2_AB
-        if (atoi(e) == 5) {
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<5>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<5>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 3) {
-            const char* sp = ispk_knob("ISPK_FFN2_STAMP");
-            p.stamps = sp ? reinterpret_cast<unsigned long long*>(strtoull(sp, nullptr, 16)) : nullptr;
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<3>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<3>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
-        }
-        if (atoi(e) == 34) {
-            const char* sp = ispk_knob("ISPK_FFN2_STAMP");
-            p.stamps = sp ? reinterpret_cast<unsigned long long*>(strtoull(sp, nullptr, 16)) : nullptr;
-            ISPK_RESERVE_LDS((&ffn2_bf16_kernel<34>), kLds, "ffn_prenorm2");
-            hipLaunchKernelGGL(ffn2_bf16_kernel<34>, grid, dim3(512), kLds, s, p);
-            return ispk_launch_status();
+    if (const char* e = ispk_knob("ISPK_FFN2_ABLATE")) {      // the probes (tools/bench_ffn.py)
+        if (const char* sp = ispk_knob("ISPK_FFN2_STAMP")) p.stamps = reinterpret_cast<unsigned long long*>(strtoull(sp, nullptr, 16));
+        switch (atoi(e)) {
+            case kProbeNoDma: return ffn2_launch<kProbeNoDma>(p, grid, s, "ffn_prenorm2");
+            case kProbeDmaOnly: return ffn2_launch<kProbeDmaOnly>(p, grid, s, "ffn_prenorm2");
+            case kProbeStamps: return ffn2_launch<kProbeStamps>(p, grid, s, "ffn_prenorm2");
+            case kProbeNoFinish: return ffn2_launch<kProbeNoFinish>(p, grid, s, "ffn_prenorm2");
+            case kProbeNoReads: return ffn2_launch<kProbeNoReads>(p, grid, s, "ffn_prenorm2");
         }
     }
 #endif
-    ISPK_RESERVE_LDS((&ffn2_bf16_kernel<0>), kLds, "ffn_prenorm2");
-    hipLaunchKernelGGL(ffn2_bf16_kernel<0>, grid, dim3(512), kLds, s, p);
-    return ispk_launch_status();
+    return ffn2_launch<0>(p, grid, s, "ffn_prenorm2");
 }
