@@ -417,6 +417,18 @@ int32_t ispk_flow_finish_f32(const float* pred_raw, const float* flow, const flo
  *                           reference adds before any re-masking); id_stride 1 = one id per utterance (the collator's
  *                           [B, 1] field), 0 = one id for the batch (the notebook's `torch.tensor([speaker])`).  Ids outside
  *                           [0, speakers) are clamped (the host-side F.embedding would raise).
+ * ispk_add_speaker_out_f32  the same sum into a second buffer: out[b][l][:] = x[b][l][:] + table[id_b][:], x untouched (x != out),
+ *                           same id clamp, bit for bit the in-place result.  The teacher-forced forward (model.py:138-146 with
+ *                           `speaker_encoder` read as `speaker_embedding`) adds AFTER the aligner took the encoder output, and
+ *                           the aligner's backward keeps that tensor.
+ * ispk_speaker_grad_f32     the table's gradient under that broadcast: d_table[s][:] = sum over the utterances b with id_b == s
+ *                           (ids clamped as above) of the sum over the rows l < text_len[b] (NULL: every row; values outside
+ *                           [0, L] are clamped) of d_x[b][l][:], in an order fixed by the shapes.  The reference's gradient is
+ *                           exactly zero on padded rows, so leaving them out is the same sum - and rows at or past text_len[b]
+ *                           are never read.  One owner per value, fixed order, no atomics: the same bits every run.  Rows of
+ *                           speakers absent from the batch are written as zeros; `accumulate` != 0 adds the sums to d_table's
+ *                           content instead (absent rows then keep theirs).  d_x fp32 [B][L][D] contiguous, L <= 512, D a
+ *                           multiple of 4; d_table [speakers] rows at stride ld_table; workspace >= B * ceil(L / 16) * D floats.
  * ispk_time_embedding_f32   modules/transformer/embeddings.py:131-157 with `with_steps` (temporal_adaptor.py:87-89):
  *                           f = [t, sin(t * freq_scale * inv_freq), cos(..)] (1 + 2*half_dim values),
  *                           out[n][:] = W1 silu(W0 f + b0) + b1; w0 [emb_dim][1 + 2*half_dim], w1 [emb_dim][emb_dim];
@@ -438,6 +450,11 @@ int32_t ispk_embed_tokens_f32(const int64_t* text, const float* table, int64_t l
                               ispk_stream_t stream);
 int32_t ispk_add_speaker_f32(float* x, const float* table, int64_t ld_table, int32_t speakers, const int64_t* speaker,
                              int32_t id_stride, int32_t B, int32_t L, int32_t D, ispk_stream_t stream);
+int32_t ispk_add_speaker_out_f32(const float* x, float* out, const float* table, int64_t ld_table, int32_t speakers,
+                                 const int64_t* speaker, int32_t id_stride, int32_t B, int32_t L, int32_t D, ispk_stream_t stream);
+int32_t ispk_speaker_grad_f32(const float* d_x, const int64_t* speaker, int32_t id_stride, const int64_t* text_len,
+                              float* workspace, int64_t workspace_floats, float* d_table, int64_t ld_table, int32_t speakers,
+                              int32_t B, int32_t L, int32_t D, int32_t accumulate, ispk_stream_t stream);
 int32_t ispk_time_embedding_f32(const float* t, int32_t n, const float* inv_freq, const float* freq_scale, int32_t half_dim,
                                 const float* w0, const float* b0, const float* w1, const float* b1, int32_t emb_dim,
                                 float* out, ispk_stream_t stream);

@@ -35,7 +35,8 @@ class AcousticModelOutput(NamedTuple):
 
 class AcousticModel(nn.Module, Constructor):
     def __init__(self, encoding_map: dict, mel_dim: int, text_dim: int = 384, encoder=None, decoder=None,
-                 temporal_adaptor=None, aligner=None, num_speakers: Optional[int] = 0, pitch_mean=None, pitch_std=None):
+                 temporal_adaptor=None, aligner=None, num_speakers: Optional[int] = 0, pitch_mean=None, pitch_std=None,
+                 speaker_in_forward: bool = False):
         super().__init__()
         self.encoding_map = dict(encoding_map)
         self.mel_dim, self.text_dim = mel_dim, text_dim
@@ -48,6 +49,10 @@ class AcousticModel(nn.Module, Constructor):
         if (num_speakers or 0) > 0:
             self.speaker_embedding = nn.Embedding(num_speakers, enc_dim)
             nn.init.xavier_uniform_(self.speaker_embedding.weight)
+        # `forward` of a multi-speaker model: off = the reference's AttributeError (see `forward`), on = model.py:145-146 with
+        # `speaker_encoder` read as `speaker_embedding`.  A plain attribute (not in the state_dict or the reference's config):
+        # it may be set after `from_pretrained`.
+        self.speaker_in_forward = bool(speaker_in_forward)
         self.train_amp: Optional[bool] = None     # forward under grad: bf16 AMP (None = follow torch.autocast's state)
         self.temporal_adaptor = FlowTemporalAdaptor.init(temporal_adaptor, encoder_dim=enc_dim)
         self.decoder = Transformer.init(decoder, emb_dim=enc_dim)
@@ -108,24 +113,32 @@ class AcousticModel(nn.Module, Constructor):
         (experiments/trainer.py:544) - the outputs carry autograd nodes whose backward is HIP kernels
         (`train.acoustic_train_outputs`): `criterion(inputs=, outputs=)` then `optimizer.step(loss)` train the model as they
         train the reference.  Under `torch.no_grad()` / with every parameter frozen: the inference kernels (no tape)."""
-        if self.speaker_embedding is not None:
+        if self.speaker_embedding is None:
+            speaker = None                       # model.py:145: a single-speaker model ignores the ids
+        elif not self.speaker_in_forward:
             # model.py:145-146: the reference's forward reads `self.speaker_encoder`, which no AcousticModel has - a
-            # multi-speaker model cannot be run through `forward` there either (only through `infer`); same error here
+            # multi-speaker model cannot be run through `forward` there either (only through `infer`); same error here unless
+            # `speaker_in_forward` is on: then the line reads `self.speaker_embedding`, what its authors meant
             raise AttributeError(f"'{type(self).__name__}' object has no attribute 'speaker_encoder'")
+        elif speaker is None:
+            raise ValueError("speaker_in_forward is on and the model has a speaker table: forward() needs `speaker` "
+                             "([B, 1] int64 ids, or a single id for the whole batch)")
         if torch.is_grad_enabled() and text.is_cuda and any(p.requires_grad for p in self.parameters()):
             from ..train.model import acoustic_train_outputs
             amp = self.train_amp if self.train_amp is not None else torch.is_autocast_enabled("cuda")
             train_aligner = any(p.requires_grad for p in self.aligner.parameters())
             with torch.autocast("cuda", enabled=False):      # (the kernels choose their own operand types: `amp`)
                 return acoustic_train_outputs(self, text, text_len, mel, mel_len, pitch, energy, flow_noise, flow_time, amp=amp,
-                                              train_aligner=train_aligner)
+                                              train_aligner=train_aligner, speaker=speaker)
         with torch.no_grad():
-            return self._forward_values(text, text_len, mel, mel_len, pitch, energy, flow_noise=flow_noise, flow_time=flow_time)
+            return self._forward_values(text, text_len, mel, mel_len, pitch, energy, flow_noise=flow_noise, flow_time=flow_time,
+                                        speaker=speaker)
 
     def _forward_values(self, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Optional[Tensor] = None,
                         energy: Optional[Tensor] = None, *, flow_noise: Optional[Tensor] = None,
-                        flow_time: Optional[Tensor] = None) -> AcousticModelOutput:
-        """The forward without a tape (inference kernels, `set_compute_dtype`'s precision)."""
+                        flow_time: Optional[Tensor] = None, speaker: Optional[Tensor] = None) -> AcousticModelOutput:
+        """The forward without a tape (inference kernels, `set_compute_dtype`'s precision).  `speaker`: ids whose table rows are
+        added to the encoder output once the aligner has taken it (`forward` decides whether they are given)."""
         # The aligner's mel-side projections (33,000 frames: large, HBM-bound launches) do not depend on the text encoder
         # (6,400 tokens: small, latency-bound launches), so they run beside it on a second stream; under HIP-graph
         # capture the fork / join become graph edges.
@@ -152,6 +165,10 @@ class AcousticModel(nn.Module, Constructor):
         hard = not self.temporal_adaptor.soft_duration
         aligner_output = self.aligner(mel=mel, enc_text=enc_out.transpose(1, 2).detach(), mel_len=mel_len,
                                       text_len=text_len, q_proj=q_proj, mas_stream=None if hard else branch)
+        if speaker is not None:
+            # model.py:145-146.  Out of place, so nothing has to be proved about the order: the aligner's launches read the
+            # un-added tensor, whichever stream they are on
+            enc_out = runtime.add_speaker(enc_out, self.speaker_embedding.weight, speaker)
         adaptor_output = self.temporal_adaptor(
             enc_out=enc_out, enc_mask=enc_mask, max_dec_len=mel.size(2),
             duration_target=aligner_output.attn_hard_duration, alignment=aligner_output.attn_soft,
@@ -294,6 +311,24 @@ class AcousticModel(nn.Module, Constructor):
         for name, param in self.named_parameters():
             param.requires_grad = any(name.startswith(layer) for layer in exception_list)
         return self
+
+    def extend_speakers(self, count: int) -> int:
+        """Grows `speaker_embedding` by `count` rows for new voices -> the first new id.  Old rows are kept bit for bit, every new
+        row is the mean of the old ones (a neutral voice to adapt from).  Call it before the optimizer is built: the table is
+        a new parameter.  With `freeze(["speaker_embedding"])` only the table trains - the usual new-voice fine-tune."""
+        if self.speaker_embedding is None:
+            raise ValueError("extend_speakers: the model has no speaker table (num_speakers = 0)")
+        if count < 1:
+            raise ValueError(f"extend_speakers: count = {count}")
+        old = self.speaker_embedding.weight
+        first = old.shape[0]
+        table = nn.Embedding(first + count, old.shape[1], device=old.device, dtype=old.dtype)
+        with torch.no_grad():
+            table.weight[:first] = old
+            table.weight[first:] = old.double().mean(dim=0).to(old.dtype)
+        table.weight.requires_grad_(old.requires_grad)
+        self.speaker_embedding = table
+        return first
 
     def prepare_inputs(self, inputs: dict) -> dict:
         """model.py:244-259 (collator field names -> forward kwargs)."""

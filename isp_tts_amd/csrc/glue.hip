@@ -33,13 +33,17 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __rest
 // over the text axis.  In place, every row of the utterance (padded ones too: the reference adds before any re-masking).
 // One wave per row; speaker ids at stride `id_stride` (0: one id for the whole batch).  Ids outside [0, speakers) are
 // clamped (the host-side F.embedding would raise).
+__device__ __forceinline__ int64_t speaker_row(const int64_t* __restrict__ speaker, int b, int id_stride, int speakers) {
+    const int64_t id = speaker[(int64_t)b * id_stride];
+    return id < 0 ? 0 : (id >= speakers ? speakers - 1 : id);
+}
+
 __global__ __launch_bounds__(256) void add_speaker_kernel(float* __restrict__ x, const float* __restrict__ table, int64_t ld_table,
                                                           int speakers, const int64_t* __restrict__ speaker, int id_stride,
                                                           int rows, int L, int D) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
-    int64_t id = speaker[(int64_t)(row / L) * id_stride];
-    id = id < 0 ? 0 : (id >= speakers ? speakers - 1 : id);
+    const int64_t id = speaker_row(speaker, row / L, id_stride, speakers);
     const f32x4* src = reinterpret_cast<const f32x4*>(table + id * ld_table);
     f32x4* dst = reinterpret_cast<f32x4*>(x + (int64_t)row * D);
     for (int c = lane; c < D / 4; c += 64) {
@@ -47,6 +51,108 @@ __global__ __launch_bounds__(256) void add_speaker_kernel(float* __restrict__ x,
         const f32x4 e = src[c];
         v[0] += e[0]; v[1] += e[1]; v[2] += e[2]; v[3] += e[3];
         dst[c] = v;
+    }
+}
+
+// The same sum into a second buffer, for the teacher-forced forward (model.py:138-146 with `speaker_encoder` read as
+// `speaker_embedding`): the aligner takes the un-added encoder output - and keeps it for its backward - so x must survive.
+__global__ __launch_bounds__(256) void add_speaker_out_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                              const float* __restrict__ table, int64_t ld_table, int speakers,
+                                                              const int64_t* __restrict__ speaker, int id_stride, int rows,
+                                                              int L, int D) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int64_t id = speaker_row(speaker, row / L, id_stride, speakers);
+    const f32x4* src = reinterpret_cast<const f32x4*>(table + id * ld_table);
+    const f32x4* in = reinterpret_cast<const f32x4*>(x + (int64_t)row * D);
+    f32x4* dst = reinterpret_cast<f32x4*>(out + (int64_t)row * D);
+    for (int c = lane; c < D / 4; c += 64) {
+        f32x4 v = in[c];
+        const f32x4 e = src[c];
+        v[0] += e[0]; v[1] += e[1]; v[2] += e[2]; v[3] += e[3];
+        dst[c] = v;
+    }
+}
+
+// Its backward for the table: d_table[s][:] = sum over the utterances b with id_b == s, in batch order, of the sum over the
+// rows l < text_len[b], in row order, of d_x[b][l][:] (nn.Embedding's backward under the broadcast; the reference's gradient is
+// exactly zero on padded rows, so leaving them out changes nothing - and what other backward kernels leave there is never read).
+// Two stages, one owner per value, no atomics:
+//   1. a workgroup owns kSgRows rows of one utterance x 256 columns; wave w adds rows w, w + 4, ... of the chunk, wave 0 then
+//      adds the four waves' sums in wave order -> part[b][chunk][:].  Chunks at or past text_len[b] are neither read nor written.
+//   2. a workgroup owns one table row x 256 columns: wave w adds, for the utterances b = w, w + 4, ... of that speaker in batch
+//      order, their chunks in row order; wave 0 then adds the four waves' sums in wave order.
+constexpr int kSgRows = 16;
+__device__ __forceinline__ int speaker_grad_len(const int64_t* __restrict__ text_len, int b, int L) {
+    if (!text_len) return L;
+    const int64_t n = text_len[b];
+    return n < 0 ? 0 : (n > L ? L : (int)n);
+}
+
+__global__ __launch_bounds__(256) void speaker_grad_stage1_kernel(const float* __restrict__ d_x, const int64_t* __restrict__ text_len,
+                                                                  float* __restrict__ part, int L, int D, int chunks) {
+    __shared__ f32x4 sums[3][64];
+    const int b = blockIdx.z, chunk = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = speaker_grad_len(text_len, b, L), r0 = chunk * kSgRows;
+    if (r0 >= n) return;                                            // (uniform over the workgroup: before any barrier)
+    const int r1 = r0 + kSgRows < n ? r0 + kSgRows : n, c = blockIdx.x * 64 + lane;
+    const bool live = c < D / 4;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (live)
+        for (int r = r0 + wave; r < r1; r += 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(d_x + ((int64_t)b * L + r) * D + 4 * c);
+            s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
+        }
+    if (wave > 0) sums[wave - 1][lane] = s;
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            const f32x4 v = sums[w][lane];
+            s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3];
+        }
+        *reinterpret_cast<f32x4*>(part + ((int64_t)b * chunks + chunk) * D + 4 * c) = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void speaker_grad_stage2_kernel(const float* __restrict__ part, const int64_t* __restrict__ speaker,
+                                                                  int id_stride, const int64_t* __restrict__ text_len,
+                                                                  float* __restrict__ d_table, int64_t ld_table, int speakers,
+                                                                  int B, int L, int D, int chunks, int accumulate) {
+    __shared__ f32x4 sums[3][64];
+    const int s = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = blockIdx.y * 64 + lane;
+    const bool live = c < D / 4;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    // wave w takes the utterances w, w + 4, ... (the tests on b are wave-uniform); an utterance's chunks are fetched eight at a
+    // time, independent loads, and added in row order: with few speakers a row's sum is a chain of B / 4 round trips, not B * chunks
+    for (int b = wave; b < B; b += 4) {
+        if (speaker_row(speaker, b, id_stride, speakers) != s) continue;
+        const int nk = (speaker_grad_len(text_len, b, L) + kSgRows - 1) / kSgRows;
+        const float* src = part + (int64_t)b * chunks * D + 4 * c;
+        for (int k0 = 0; k0 < nk && live; k0 += 8) {
+            f32x4 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (k0 + u < nk) v[u] = *reinterpret_cast<const f32x4*>(src + (int64_t)(k0 + u) * D);
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (k0 + u < nk) { acc[0] += v[u][0]; acc[1] += v[u][1]; acc[2] += v[u][2]; acc[3] += v[u][3]; }
+        }
+    }
+    if (wave > 0) sums[wave - 1][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            const f32x4 v = sums[w][lane];
+            acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
+        }
+        f32x4* dst = reinterpret_cast<f32x4*>(d_table + (int64_t)s * ld_table + 4 * c);
+        if (accumulate) {
+            const f32x4 old = *dst;
+            acc[0] += old[0]; acc[1] += old[1]; acc[2] += old[2]; acc[3] += old[3];
+        }
+        *dst = acc;
     }
 }
 
@@ -328,6 +434,46 @@ extern "C" int32_t ispk_add_speaker_f32(float* x, const float* table, int64_t ld
     const int rows = B * L;
     hipLaunchKernelGGL(add_speaker_kernel, dim3((rows + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, table,
                        ld_table, speakers, speaker, id_stride, rows, L, D);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_add_speaker_out_f32(const float* x, float* out, const float* table, int64_t ld_table, int32_t speakers,
+                                            const int64_t* speaker, int32_t id_stride, int32_t B, int32_t L, int32_t D,
+                                            ispk_stream_t stream) {
+    ISPK_REQUIRE(x && out && table && speaker, ISPK_E_NULL, "add_speaker_out: null pointer");
+    ISPK_REQUIRE(B >= 0 && L >= 1 && D >= 4 && speakers >= 1 && (id_stride == 0 || id_stride == 1), ISPK_E_SHAPE,
+                 "add_speaker_out: bad shape B=%d L=%d D=%d speakers=%d id_stride=%d", B, L, D, speakers, id_stride);
+    ISPK_REQUIRE(D % 4 == 0 && ld_table % 4 == 0 && ld_table >= D && ispk_aligned(table, 16) && ispk_aligned(x, 16) &&
+                     ispk_aligned(out, 16),
+                 ISPK_E_ALIGN, "add_speaker_out: D / ld_table must be multiples of 4 and table / x / out 16-byte aligned");
+    ISPK_REQUIRE(x != out, ISPK_E_UNSUPPORTED, "add_speaker_out: x and out are the same buffer (ispk_add_speaker_f32 works in place)");
+    if (B == 0) return 0;
+    const int rows = B * L;
+    hipLaunchKernelGGL(add_speaker_out_kernel, dim3((rows + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, out,
+                       table, ld_table, speakers, speaker, id_stride, rows, L, D);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_speaker_grad_f32(const float* d_x, const int64_t* speaker, int32_t id_stride, const int64_t* text_len,
+                                         float* workspace, int64_t workspace_floats, float* d_table, int64_t ld_table,
+                                         int32_t speakers, int32_t B, int32_t L, int32_t D, int32_t accumulate,
+                                         ispk_stream_t stream) {
+    ISPK_REQUIRE(d_x && speaker && workspace && d_table, ISPK_E_NULL, "speaker_grad: null pointer");
+    ISPK_REQUIRE(B >= 0 && B <= 65535 && L >= 1 && L <= 512 && D >= 4 && speakers >= 1 && (id_stride == 0 || id_stride == 1),
+                 ISPK_E_SHAPE, "speaker_grad: bad shape B=%d L=%d (<= 512) D=%d speakers=%d id_stride=%d", B, L, D, speakers,
+                 id_stride);
+    ISPK_REQUIRE(D % 4 == 0 && ld_table % 4 == 0 && ld_table >= D && ispk_aligned(d_table, 16) && ispk_aligned(d_x, 16) &&
+                     ispk_aligned(workspace, 16),
+                 ISPK_E_ALIGN, "speaker_grad: D / ld_table must be multiples of 4 and d_x / d_table / workspace 16-byte aligned");
+    const int chunks = (L + kSgRows - 1) / kSgRows;
+    ISPK_REQUIRE(workspace_floats >= (int64_t)B * chunks * D, ISPK_E_SHAPE, "speaker_grad: workspace needs %lld floats (B * ceil(L / %d) * D)",
+                 (long long)B * chunks * D, kSgRows);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (B > 0)
+        hipLaunchKernelGGL(speaker_grad_stage1_kernel, dim3((D / 4 + 63) / 64, chunks, B), dim3(256), 0, s, d_x, text_len, workspace,
+                           L, D, chunks);
+    hipLaunchKernelGGL(speaker_grad_stage2_kernel, dim3(speakers, (D / 4 + 63) / 64), dim3(256), 0, s, workspace, speaker, id_stride, text_len, d_table,
+                       ld_table, speakers, B, L, D, chunks, accumulate);
     return ispk_launch_status();
 }
 

@@ -60,7 +60,9 @@ class GraphedCall:
 class GraphedForward(GraphedCall):
     def __init__(self, model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor,
                  energy: Tensor, flow_noise: Optional[Tensor] = None, flow_time: Optional[Tensor] = None,
-                 warmup: int = 2):
+                 warmup: int = 2, *, speaker: Optional[Tensor] = None):
+        """`speaker` (a multi-speaker model with `speaker_in_forward` on): one more static input - the replay reads the ids
+        from device memory, `__call__(speaker=...)` copies new ones in."""
         self.model = model
         self.static = {"text": text.clone(), "text_len": text_len.clone(), "mel": mel.clone(), "mel_len": mel_len.clone(),
                        "pitch": pitch.clone(), "energy": energy.clone()}
@@ -69,13 +71,15 @@ class GraphedForward(GraphedCall):
         self.static["flow_noise"] = (flow_noise.clone() if flow_noise is not None
                                      else torch.randn(b, l, 3, device=dev))
         self.static["flow_time"] = flow_time.clone() if flow_time is not None else torch.rand(b, device=dev)
+        if speaker is not None:
+            self.static["speaker"] = speaker.clone()
         super().__init__(self._run, warmup)
 
     def _run(self):
         s = self.static
         with torch.no_grad():      # (a replayed forward has no tape; with gradients enabled `model(...)` is the training forward)
             return self.model(s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"], s["energy"],
-                              flow_noise=s["flow_noise"], flow_time=s["flow_time"])
+                              speaker=s.get("speaker"), flow_noise=s["flow_noise"], flow_time=s["flow_time"])
 
     def __call__(self, **inputs: Tensor):
         for k, v in inputs.items():
@@ -102,6 +106,9 @@ class SegmentedForward:
                                       "regulator, decoder) is launched without waiting for the side piece, and with hard "
                                       "durations both its targets and its regulator read the MAS durations that piece computes; "
                                       "use GraphedForward")
+        if model.speaker_embedding is not None and model.speaker_in_forward:
+            raise NotImplementedError("SegmentedForward does not add the speaker rows (its three pieces hand the encoder output "
+                                      "on as one tensor); use GraphedForward(..., speaker=ids)")
         b, l = text.shape
         dev = text.device
         s = self.static = {"text": text.clone(), "text_len": text_len.clone(), "mel": mel.clone(), "mel_len": mel_len.clone(),

@@ -25,6 +25,8 @@ from torch import Tensor
 
 FIELDS = (("text_vector", torch.int64), ("text_vector_len", torch.int64), ("mel", torch.float32), ("mel_len", torch.int64),
           ("pitch", torch.float32), ("energy", torch.float32))
+# staged only when the submitted batch has it: `speaker` int64 [B, 1], the collator's field for multi-speaker data (collator.py:59)
+OPTIONAL_FIELDS = (("speaker", torch.int64),)
 
 
 def _numel(shape) -> int:
@@ -59,9 +61,10 @@ class BatchIngest:
         self.on_gpu = self.device.type == "cuda"
         self.slots = slots
         caps = {"text_vector": max_batch * max_text, "text_vector_len": max_batch, "mel": max_batch * mel_dim * max_mel,
-                "mel_len": max_batch, "pitch": max_batch * max_mel, "energy": max_batch * max_mel}
-        self.host = [{k: torch.empty(caps[k], dtype=dt, pin_memory=self.on_gpu) for k, dt in FIELDS} for _ in range(slots)]
-        self.dev = [{k: torch.empty(caps[k], dtype=dt, device=self.device) for k, dt in FIELDS} for _ in range(slots)]
+                "mel_len": max_batch, "pitch": max_batch * max_mel, "energy": max_batch * max_mel, "speaker": max_batch}
+        every = FIELDS + OPTIONAL_FIELDS
+        self.host = [{k: torch.empty(caps[k], dtype=dt, pin_memory=self.on_gpu) for k, dt in every} for _ in range(slots)]
+        self.dev = [{k: torch.empty(caps[k], dtype=dt, device=self.device) for k, dt in every} for _ in range(slots)]
         self.copy_stream = torch.cuda.Stream(device=self.device) if self.on_gpu else None
         self.copied = [torch.cuda.Event() if self.on_gpu else None for _ in range(slots)]
         self.consumed = [torch.cuda.Event() if self.on_gpu else None for _ in range(slots)]
@@ -72,7 +75,8 @@ class BatchIngest:
         self.handed_out = [False] * slots   # get() returned this slot's device views and done() has not been called for it
 
     def submit(self, batch: dict) -> None:
-        """Stages one collated batch (the reference collator's dict; `pitch` / `energy` required, as in the recipes)."""
+        """Stages one collated batch (the reference collator's dict; `pitch` / `energy` required, as in the recipes; `speaker`
+        when the batch has one)."""
         assert self.pending < self.slots, "every slot holds a batch that has not been taken with get() yet"
         k = self.head
         # contract: get() -> queue the compute that reads the views -> done(); only then may the slot be staged again (the
@@ -85,7 +89,7 @@ class BatchIngest:
             # running has finished, and the next batch's staging + launch would then start on an idle GPU
             self.copied[k].synchronize()
         shapes = {}
-        for name, dt in FIELDS:
+        for name, dt in FIELDS + tuple(f for f in OPTIONAL_FIELDS if batch.get(f[0]) is not None):
             t = batch[name]
             assert t.dtype == dt and t.device.type == "cpu", f"{name}: expected a CPU {dt} tensor"
             n = t.numel()
@@ -96,12 +100,12 @@ class BatchIngest:
         if self.on_gpu:
             with torch.cuda.stream(self.copy_stream):
                 self.copy_stream.wait_event(self.consumed[k])      # the compute that read this slot's device buffers (no-op at first)
-                for name, _ in FIELDS:
+                for name in shapes:
                     n = _numel(shapes[name])
                     self.dev[k][name][:n].copy_(self.host[k][name][:n], non_blocking=True)
                 self.copied[k].record(self.copy_stream)
         else:
-            for name, _ in FIELDS:
+            for name in shapes:
                 n = _numel(shapes[name])
                 self.dev[k][name][:n].copy_(self.host[k][name][:n])
         self.head = (k + 1) % self.slots
@@ -113,7 +117,7 @@ class BatchIngest:
         k = self.tail
         if self.on_gpu:
             torch.cuda.current_stream().wait_event(self.copied[k])
-        out = {name: self.dev[k][name][: _numel(self.shapes[k][name])].view(self.shapes[k][name]) for name, _ in FIELDS}
+        out = {name: self.dev[k][name][: _numel(shape)].view(shape) for name, shape in self.shapes[k].items()}
         self.tail = (k + 1) % self.slots
         self.pending -= 1
         self._last = k
@@ -129,6 +133,10 @@ class BatchIngest:
 
 
 def model_inputs(batch: dict) -> dict:
-    """The reference's `AcousticModel.prepare_inputs` (model.py:244-259): collator field names -> forward kwargs."""
-    return {"text": batch["text_vector"], "text_len": batch["text_vector_len"], "mel": batch["mel"],
-            "mel_len": batch["mel_len"], "pitch": batch["pitch"], "energy": batch["energy"]}
+    """The reference's `AcousticModel.prepare_inputs` (model.py:244-259): collator field names -> forward kwargs; `speaker`
+    only when the batch has one."""
+    out = {"text": batch["text_vector"], "text_len": batch["text_vector_len"], "mel": batch["mel"],
+           "mel_len": batch["mel_len"], "pitch": batch["pitch"], "energy": batch["energy"]}
+    if batch.get("speaker") is not None:
+        out["speaker"] = batch["speaker"]
+    return out

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ispk_hard_average_f32": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_embed_tokens_f32": [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_add_speaker_f32": [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _P],
+    "ispk_add_speaker_out_f32": [_P, _P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _P],
+    "ispk_speaker_grad_f32": [_P, _P, _I32, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_time_embedding_f32": [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P],
     "ispk_length_regulate_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_length_regulate_split_bf16": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
@@ -1035,6 +1037,18 @@ def embed_tokens(text: Tensor, table: Tensor, text_len: Optional[Tensor] = None,
     return emb, mask
 
 
+def _speaker_ids(speaker: Tensor, B: int):
+    """-> (contiguous int64 ids, id_stride): `speaker` int64 [B, 1] (the collator's field, collator.py:59) = one id per utterance,
+    or one element = one id for the whole batch (the notebook's `torch.tensor([id])`)."""
+    assert speaker.dtype == torch.int64
+    if speaker.numel() == 1:
+        return speaker.contiguous(), 0
+    if speaker.ndim == 2 and tuple(speaker.shape) == (B, 1):
+        return speaker.contiguous(), 1
+    raise ValueError(f"speaker of shape {tuple(speaker.shape)} does not broadcast against enc_out [B={B}, L, D] "
+                     "(the reference takes [B, 1] ids or a single id)")
+
+
 def add_speaker_(x: Tensor, table: Tensor, speaker: Tensor) -> Tensor:
     """ispk_add_speaker_f32: x [B, L, D] += table[speaker] in place, broadcast over L the way the reference's
     `enc_out + self.speaker_embedding(speaker)` broadcasts (model.py:205-207): `speaker` int64 [B, 1] (the collator's field,
@@ -1042,18 +1056,49 @@ def add_speaker_(x: Tensor, table: Tensor, speaker: Tensor) -> Tensor:
     _dev(x, table, speaker)
     assert x.dtype == torch.float32 and x.ndim == 3 and x.is_contiguous() and table.dtype == torch.float32 and table.stride(1) == 1
     B, L, D = x.shape
-    assert table.shape[1] == D and speaker.dtype == torch.int64
-    if speaker.numel() == 1:
-        stride = 0
-    elif speaker.ndim == 2 and tuple(speaker.shape) == (B, 1):
-        stride = 1
-    else:
-        raise ValueError(f"speaker of shape {tuple(speaker.shape)} does not broadcast against enc_out [B={B}, L, D] "
-                         "(the reference takes [B, 1] ids or a single id)")
-    speaker = speaker.contiguous()
+    assert table.shape[1] == D
+    speaker, stride = _speaker_ids(speaker, B)
     _launch("add_speaker_kernel", 0.0, 8.0 * B * L * D, lib().ispk_add_speaker_f32, x.data_ptr(), table.data_ptr(), table.stride(0),
             table.shape[0], speaker.data_ptr(), stride, B, L, D, _stream())
     return x
+
+
+def add_speaker(x: Tensor, table: Tensor, speaker: Tensor) -> Tensor:
+    """ispk_add_speaker_out_f32: -> x [B, L, D] + table[speaker] in a new tensor, bit for bit what `add_speaker_` leaves in
+    place; x is untouched (the teacher-forced forward: the aligner reads - and its backward keeps - the un-added tensor)."""
+    _dev(x, table, speaker)
+    assert x.dtype == torch.float32 and x.ndim == 3 and x.is_contiguous() and table.dtype == torch.float32 and table.stride(1) == 1
+    B, L, D = x.shape
+    assert table.shape[1] == D
+    speaker, stride = _speaker_ids(speaker, B)
+    out = torch.empty_like(x)
+    _launch("add_speaker_out_kernel", 0.0, 8.0 * B * L * D, lib().ispk_add_speaker_out_f32, x.data_ptr(), out.data_ptr(),
+            table.data_ptr(), table.stride(0), table.shape[0], speaker.data_ptr(), stride, B, L, D, _stream())
+    return out
+
+
+def speaker_grad(d_x: Tensor, speaker: Tensor, speakers: int, text_len: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                 accumulate: bool = False) -> Tensor:
+    """ispk_speaker_grad_f32: d_x fp32 [B, L, D] -> d_table [speakers, D], row s the sum of d_x[b, :text_len[b]] over the
+    utterances of speaker s (fixed order, no atomics); rows of absent speakers are zero.  `out` (contiguous [speakers, D]) is
+    written, or - `accumulate` - added to."""
+    _dev(d_x, speaker, text_len, out)
+    assert d_x.dtype == torch.float32 and d_x.ndim == 3
+    d_x = d_x.contiguous()
+    B, L, D = d_x.shape
+    speaker, stride = _speaker_ids(speaker, B)
+    if text_len is not None:
+        text_len = text_len.to(torch.int64).contiguous()
+        assert text_len.numel() == B
+    if out is None:
+        assert not accumulate
+        out = torch.empty((speakers, D), dtype=torch.float32, device=d_x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (speakers, D) and out.stride(1) == 1
+    ws = workspace(d_x.device, B * -(-L // 16) * D)
+    _launch("speaker_grad_kernels", 1.0 * B * L * D, 4.0 * B * L * D + 4.0 * speakers * D, lib().ispk_speaker_grad_f32, d_x.data_ptr(),
+            speaker.data_ptr(), stride, _ptr(text_len), ws.data_ptr(), ws.numel(), out.data_ptr(), out.stride(0), speakers, B, L, D,
+            1 if accumulate else 0, _stream())
+    return out
 
 
 def time_embedding(t: Tensor, inv_freq: Tensor, freq_scale: Tensor, w0: Tensor, b0: Tensor, w1: Tensor, b1: Tensor) -> Tensor:

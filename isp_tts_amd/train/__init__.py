@@ -29,9 +29,9 @@ from .loss import AcousticModelLoss, AttentionBinarizationLoss, AttentionCTCLoss
 from .model import acoustic_train_forward, acoustic_train_outputs
 from .predictor import flow_predictor_loss
 from .optim import FlatAdamW, FlatParameters, group_weight_decayable_params
-from .stack import (EmbedTokensFunction, HardRegulateFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction, TransformerStackFunction, acoustic_mel_train_forward, mel_decoder_train_forward, transformer_train_forward)
+from .stack import (AddSpeakerFunction, EmbedTokensFunction, HardRegulateFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction, TransformerStackFunction, acoustic_mel_train_forward, mel_decoder_train_forward, transformer_train_forward)
 
 from .graph import GraphedTrainStep
 
-__all__ = ["AcousticModelLoss", "GraphedTrainStep", "EmbedTokensFunction", "MaskedLinearResidualFunction", "acoustic_mel_train_forward", "acoustic_train_forward", "acoustic_train_outputs", "flow_predictor_loss", "AttentionBinarizationLoss", "AttentionCTCLoss", "FlatAdamW", "FlatParameters", "HardRegulateFunction", "LengthRegulateFunction", "MelLoss", "ToMelFunction", "TransformerStackFunction",
+__all__ = ["AcousticModelLoss", "AddSpeakerFunction", "GraphedTrainStep", "EmbedTokensFunction", "MaskedLinearResidualFunction", "acoustic_mel_train_forward", "acoustic_train_forward", "acoustic_train_outputs", "flow_predictor_loss", "AttentionBinarizationLoss", "AttentionCTCLoss", "FlatAdamW", "FlatParameters", "HardRegulateFunction", "LengthRegulateFunction", "MelLoss", "ToMelFunction", "TransformerStackFunction",
            "group_weight_decayable_params", "mel_decoder_train_forward", "transformer_train_forward"]

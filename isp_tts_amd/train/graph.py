@@ -24,6 +24,8 @@ from .optim import FlatAdamW
 class GraphedTrainStep:
     """step = GraphedTrainStep(model, opt, batch); total, losses, norm = step(**next_batch).
     `batch`: text, text_len, mel, mel_len, pitch, energy (+ flow_x0, flow_t) on the device, at the shapes every later batch has.
+    With a `speaker` field (int64 [B, 1] ids; a multi-speaker model with `speaker_in_forward` on) the ids are one more static
+    input: copied per call, read by the replay from device memory.
     The `warmup` steps before the capture are REAL steps on `batch`.  Single rank, no gradient accumulation.
     `evaluator` (e.g. acoustic.AcousticModelEvaluator, the reference's `metrics = self.evaluator(inputs, outputs)` of
     experiments/trainer.py:557-559): the captured step also runs it on the step's forward outputs, before the backward;
@@ -52,6 +54,8 @@ class GraphedTrainStep:
             features.device_tables(dev)                     # (its tables reach the device before, not inside, the capture)
             self.features = features.empty_outputs(*batch["audio"].shape, dev)
         self.static = {k: batch[k].clone() for k in keys}
+        if batch.get("speaker") is not None:
+            self.static["speaker"] = batch["speaker"].clone()
         b, l = batch["text"].shape
         self.static["flow_x0"] = batch["flow_x0"].clone() if "flow_x0" in batch else torch.randn(b, l, 3, device=dev)
         self.static["flow_t"] = batch["flow_t"].clone() if "flow_t" in batch else torch.rand(b, device=dev)
@@ -117,15 +121,15 @@ class GraphedTrainStep:
         if self.evaluator is None:
             _, total, losses = acoustic_train_forward(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"],
                                                       s["energy"], flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
-                                                      train_aligner=self.train_aligner)
+                                                      train_aligner=self.train_aligner, speaker=s.get("speaker"))
         else:
             out = acoustic_train_outputs(self.model, s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"], s["energy"],
                                          flow_noise=s["flow_x0"], flow_time=s["flow_t"], amp=self.amp,
-                                         train_aligner=self.train_aligner)
+                                         train_aligner=self.train_aligner, speaker=s.get("speaker"))
             total, losses = acoustic_train_losses(out, s["text_len"], s["mel"], s["mel_len"], self.train_aligner)
             self.outputs = _detached(out)
             with torch.no_grad():
-                self.metrics = self.evaluator({k: s[k] for k in self.KEYS}, self.outputs)
+                self.metrics = self.evaluator({k: s[k] for k in self.KEYS + (("speaker",) if "speaker" in s else ())}, self.outputs)
         # (the finiteness check of an eager step is a host read of the norm; the AdamW factors come from the device record)
         norm = self.opt.step(total, args_dev=self.args_dev, check_finite=False)
         return total, losses, norm

@@ -19,13 +19,13 @@ from .. import runtime
 from .loss import AttentionBinarizationLoss, AttentionCTCLoss, MelLoss, sum_losses
 from .aligner import conv_attention_train
 from .predictor import flow_predictor_loss
-from .stack import (EmbedTokensFunction, HardRegulateFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction,
+from .stack import (AddSpeakerFunction, EmbedTokensFunction, HardRegulateFunction, LengthRegulateFunction, MaskedLinearResidualFunction, ToMelFunction,
                     fork, transformer_train_forward)
 
 
 def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor, energy: Tensor,
                            flow_noise: Optional[Tensor] = None, flow_time: Optional[Tensor] = None, amp: bool = False,
-                           train_aligner: bool = True):
+                           train_aligner: bool = True, speaker: Optional[Tensor] = None):
     """`AcousticModel.forward` (model.py:116-174) as a chain of autograd nodes whose forward AND backward are HIP kernels ->
     the reference's `AcousticModelOutput`: `mel`, `adaptor_output.losses["flow_loss"]`, `aligner_output.attn_logits` and
     `aligner_output.attn_soft` carry the graph, so that the reference's loop body - `outputs = model(**inputs)`;
@@ -33,7 +33,9 @@ def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, m
     back-propagates through these kernels.  This is what `AcousticModel.forward` returns when gradients are enabled.
     `train_aligner=False`: the aligner front-end is frozen (its outputs are values).
     With hard durations (`temporal_adaptor.soft_duration` off) the targets are the hard averages over the MAS durations and the
-    regulator repeats rows by them: attn_soft has ONE consumer, the binarisation loss, and the mel loss does not reach the aligner."""
+    regulator repeats rows by them: attn_soft has ONE consumer, the binarisation loss, and the mel loss does not reach the aligner.
+    `speaker` (a multi-speaker model with `speaker_in_forward` on): the speaker rows are added after the aligner took the encoder
+    output (model.py:138-146), so the predictor's condition and the embedding residual carry them and the aligner's keys do not."""
     from ..acoustic.alignment import AlignerOutput
     from ..acoustic.model import AcousticModelOutput
     from ..acoustic.temporal_adaptor import TemporalAdaptorOutput
@@ -57,6 +59,8 @@ def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, m
             targets = runtime.hard_average(pitch, energy, dur, text_len)                           # [log1p duration, pitch, energy]
         else:
             targets = runtime.soft_average(attn_soft.detach(), pitch, energy, dur, text_len)
+    if speaker is not None:
+        enc_out = AddSpeakerFunction.apply(enc_out, model.speaker_embedding.weight, speaker, text_len)
     # The averaged pitch / energy enter the embedding stack DETACHED (temporal_adaptor.py:284, :292 `pitch_target.detach()`,
     # `energy_target.detach()`), like the predictor's targets (:112): the mel loss reaches attn_soft - and through it the
     # aligner - only by way of the length regulator (:300).
@@ -90,12 +94,13 @@ def acoustic_train_outputs(model, text: Tensor, text_len: Tensor, mel: Tensor, m
 
 def acoustic_train_forward(model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor, energy: Tensor,
                            flow_noise: Optional[Tensor] = None, flow_time: Optional[Tensor] = None, amp: bool = False,
-                           train_aligner: bool = True):
+                           train_aligner: bool = True, speaker: Optional[Tensor] = None):
     """-> (mel_out [B, 80, M], loss, losses): `acoustic_train_outputs` under the reference's total loss.  `train_aligner`: the
     aligner front-end is a differentiable node too (train/aligner.py) and loss = mel + flow + CTC + binarisation, the
     reference's total (loss.py:140-182); otherwise the aligner is frozen, loss = mel + flow and the two attention terms are
     values."""
-    out = acoustic_train_outputs(model, text, text_len, mel, mel_len, pitch, energy, flow_noise, flow_time, amp, train_aligner)
+    out = acoustic_train_outputs(model, text, text_len, mel, mel_len, pitch, energy, flow_noise, flow_time, amp, train_aligner,
+                                 speaker)
     total, losses = acoustic_train_losses(out, text_len, mel, mel_len, train_aligner)
     return out.mel, total, losses
 

@@ -338,6 +338,34 @@ class EmbedTokensFunction(torch.autograd.Function):
         return None, dt, None
 
 
+class AddSpeakerFunction(torch.autograd.Function):
+    """out = enc_out + table[speaker], broadcast over the text axis (model.py:145-146 with `speaker_encoder` read as
+    `speaker_embedding`; forward = `runtime.add_speaker`, out of place: the aligner reads - and keeps for its backward - the
+    un-added tensor).  Backward: d enc_out = d out, unchanged; d table[s] = the sum of d out's rows l < text_len[b] over the
+    utterances of speaker s (`runtime.speaker_grad`: fixed order, one owner per value, no atomics), written straight into the
+    optimizer arena when the table's .grad is one of its buffers.  No launch when the table is frozen."""
+
+    @staticmethod
+    def forward(ctx, enc_out: Tensor, table: Tensor, speaker: Tensor, text_len: Optional[Tensor]):
+        ctx.save_for_backward(speaker, text_len)
+        ctx.table = table
+        return runtime.add_speaker(enc_out.float().contiguous(), table.detach(), speaker)
+
+    @staticmethod
+    def backward(ctx, d_out: Tensor):
+        speaker, text_len = ctx.saved_tensors
+        table, dt = ctx.table, None
+        if table.requires_grad:
+            d_out = d_out.float().contiguous()
+            g = table.grad
+            if g is not None and getattr(g, "_ispk_grad_arena", False):
+                runtime.speaker_grad(d_out, speaker, table.shape[0], text_len, out=g, accumulate=getattr(g, "_ispk_dirty", False))
+                g._ispk_dirty = True
+            else:
+                dt = runtime.speaker_grad(d_out, speaker, table.shape[0], text_len)
+        return d_out, dt, None, None
+
+
 def acoustic_mel_train_forward(model, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Tensor, energy: Tensor,
                                amp: bool = False) -> Tensor:
     """The teacher-forced forward of `AcousticModel` (model.py:116-174) as a differentiable chain for the MEL loss:

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the hot kernels at the BASELINE config-3 shapes (B=64: 32768 decoder rows, 6400 encoder rows).
 HIP-event timing, interleaved rounds, median.  Usage: python tools/bench_kernels.py [f32|bf16] [--rows 32768]
-`python tools/bench_kernels.py adaptor`: the temporal adaptor's regulators and averagers instead, hard durations beside soft,
-at B=64, L=100, M=512, D=384, each with its traffic floor at the 6.3 TB/s a float4 copy reaches on the MI355X."""
+`python tools/bench_kernels.py adaptor`: the temporal adaptor's regulators and averagers instead, hard durations beside soft, and
+the speaker-embedding add with its table gradient, at B=64, L=100, M=512, D=384, each with its traffic floor at the 6.3 TB/s a float4 copy reaches on the MI355X."""
 import os
 import sys
 
@@ -52,6 +52,12 @@ def adaptor_cases():
     dur_d, dur_f, tl_d = dur.to(dev), dur.float().to(dev), tl.to(dev)
     pitch, energy = inp["pitch"].to(dev), inp["energy"].to(dev)
     rows = 4 * B * D * (M + L)
+    S = 1307                                             # the published multi-speaker checkpoint's table
+    table = synth._normal("b/adaptor/speakers", (S, D), 0.3).to(dev)
+    d_table = torch.empty_like(table)
+    ids = (torch.arange(B).view(B, 1) * 20 % S).to(dev)
+    ids4 = ids % 4
+    d_x = d_out[:, :L].contiguous()
     return [
         ("hard regulate (int64 durations)", lambda: runtime.hard_regulate(x, dur_d, M, max_len=M), rows),
         ("hard regulate (fp32 durations)", lambda: runtime.hard_regulate(x, dur_f, M), rows),
@@ -64,6 +70,10 @@ def adaptor_cases():
         ("soft average", lambda: runtime.soft_average(attn, pitch, energy, dur_d, tl_d), 4 * B * M * L + 8 * B * M + 20 * B * L),
         ("infer features, rounded", lambda: runtime.infer_features(pred, None, None, None, round_duration=True), 24 * B * L),
         ("infer features", lambda: runtime.infer_features(pred, None, None, None), 24 * B * L),
+        ("add speaker, out of place", lambda: runtime.add_speaker(x, table, ids), 8 * B * L * D),
+        ("add speaker, in place", lambda: runtime.add_speaker_(x, table, ids), 8 * B * L * D),
+        (f"speaker table gradient, S={S}", lambda: runtime.speaker_grad(d_x, ids, S, tl_d, out=d_table), 4 * B * L * D + 4 * S * D),
+        ("speaker table gradient, S=4", lambda: runtime.speaker_grad(d_x, ids4, 4, tl_d, out=d_table[:4]), 4 * B * L * D),
     ]
 
 
