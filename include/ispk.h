@@ -1007,6 +1007,44 @@ int32_t ispk_copy2d_f32(const float* src, int64_t ld_src, float* dst, int64_t ld
 int32_t ispk_permute021_f32(const float* src, float* dst, int32_t A, int32_t B, int32_t C, ispk_stream_t stream);
 int32_t ispk_conv_weight_flip_f32(const float* w, float* wf, int32_t O, int32_t C, int32_t K, ispk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * HiFi-GAN generator (csrc/hifigan.hip; isp_tts_amd/hifigan.py).  Activations are fp32 rows [B * T][C] with unit column
+ * stride (row b*T + t = sample t of utterance b); weights are images [k][C_out][C_in] (tap-major, C_in contiguous), fp32 for
+ * the _f32 entries (exact-fp32 MFMA) and bf16 for the _bf16 entries (activations rounded to bf16 on their way into LDS, fp32
+ * accumulation, fp32 rows in and out).  The valid length of utterance b is len[b] * len_mul input rows (len NULL: T; a value
+ * outside [0, T] counts as 0): input rows at or past it, and halo rows outside [0, length), read as zeros (a select: NaN in
+ * the padding does not propagate), output rows at or past the output length are written as zeros.  C_in and C_out are
+ * multiples of 32 up to 512 (anything else: E_UNSUP).  x, w and out 16-byte aligned, ldx and ldo multiples of 4.
+ *
+ * ispk_hifigan_tile_rows      time positions per workgroup of the two convolution kernels (128): the tests' tile edges.
+ * ispk_hifigan_conv_*         v = bias + Conv1d(C_in, C_out, k, dilation, padding (k-1) dilation / 2)(leaky_relu(x, slope))
+ *                             [+ resid];  out = scale * v, or with accumulate != 0 out = fma(scale, v, out).  slope 1 = no
+ *                             activation.  k odd, 1 .. 11; dilation 1 .. 12.  resid may be out (same rows), not x.
+ * ispk_hifigan_upsample_*     out [B * T * stride][C_out] = bias + ConvTranspose1d(C_in, C_out, k, stride,
+ *                             padding (k - stride) / 2)(leaky_relu(x, slope)); w[j][o][c] = weight[c][o][j].  Any k >= stride
+ *                             with k - stride even (stride <= 64, k <= 128); output length stride * input length.
+ * ispk_hifigan_post_f32       audio[b][s] = tanh(bias[0] + sum_j sum_c w[j][c] leaky_relu(x[b*T + s + j - 3][c], slope)), the
+ *                             7-tap C -> 1 output convolution in fp32, for s < len[b] * len_mul, 0 from there to S (S >= T,
+ *                             ld_audio >= S); audio_len[b] = len[b] * len_mul (may be NULL).  w fp32 [7][C]. */
+int32_t ispk_hifigan_tile_rows(void);
+int32_t ispk_hifigan_conv_f32(const float* x, int64_t ldx, const float* w, const float* bias, const float* resid, int64_t ldr,
+                              float* out, int64_t ldo, const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C_in,
+                              int32_t C_out, int32_t k, int32_t dilation, float slope, float scale, int32_t accumulate,
+                              ispk_stream_t stream);
+int32_t ispk_hifigan_conv_bf16(const float* x, int64_t ldx, const uint16_t* w, const float* bias, const float* resid,
+                               int64_t ldr, float* out, int64_t ldo, const int64_t* len, int32_t len_mul, int32_t B, int32_t T,
+                               int32_t C_in, int32_t C_out, int32_t k, int32_t dilation, float slope, float scale,
+                               int32_t accumulate, ispk_stream_t stream);
+int32_t ispk_hifigan_upsample_f32(const float* x, int64_t ldx, const float* w, const float* bias, float* out, int64_t ldo,
+                                  const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C_in, int32_t C_out,
+                                  int32_t k, int32_t stride, float slope, ispk_stream_t stream);
+int32_t ispk_hifigan_upsample_bf16(const float* x, int64_t ldx, const uint16_t* w, const float* bias, float* out, int64_t ldo,
+                                   const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C_in, int32_t C_out,
+                                   int32_t k, int32_t stride, float slope, ispk_stream_t stream);
+int32_t ispk_hifigan_post_f32(const float* x, int64_t ldx, const float* w, const float* bias, const int64_t* len,
+                              int32_t len_mul, float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B, int32_t T,
+                              int32_t S, int32_t C, float slope, ispk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

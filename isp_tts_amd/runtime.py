@@ -150,6 +150,14 @@ SIGNATURES = {
     "ispk_vocoder_unfold": [_P, _I32, _I64, _I64, _I64, _P, _P, _I32, _I64, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_dwconv7_ln_f32": [_P, _I64, _P, _P, _P, _P, _F32, _P, _P, _I32, _I64, _I32, _I32, _I32, _P],
     "ispk_istft_head_f32": [_P, _I64, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _P],
+    "ispk_hifigan_tile_rows": [],
+    "ispk_hifigan_conv_f32": [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _F32,
+                              _I32, _P],
+    "ispk_hifigan_conv_bf16": [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _F32,
+                               _I32, _P],
+    "ispk_hifigan_upsample_f32": [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _P],
+    "ispk_hifigan_upsample_bf16": [_P, _I64, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F32, _P],
+    "ispk_hifigan_post_f32": [_P, _I64, _P, _P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _F32, _P],
 }
 
 _lib = None
@@ -2365,4 +2373,100 @@ def istft_head(h: Tensor, T: int, mel_len: Optional[Tensor], tables: Tensor, aud
     _launch("istft_head_kernel", R * 1.25 * (5.0 * 512 * 9 + 20.0 * 513), float(R * 1026 * 4 + B * S * 4),
             lib().ispk_istft_head_f32, h.data_ptr(), h.stride(0), ml, tables.data_ptr(), tables.numel(), audio.data_ptr(),
             audio.stride(0), _ptr(audio_len), B, T, S, _stream())
+    return audio
+
+
+# ------------------------------------------------------------------------------------------------- HiFi-GAN vocoder
+HIFIGAN_TILE_ROWS = 128       # ispk_hifigan_tile_rows(): time positions per workgroup of the convolution kernels
+HIFIGAN_MAX_CHANNELS = 512    # C_in, C_out: multiples of 32 up to this
+HIFIGAN_MAX_KERNEL, HIFIGAN_MAX_DILATION = 11, 12
+
+
+def _hifigan_rows(x: Tensor, name: str) -> None:
+    assert x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1, f"{name}: fp32 rows [R, C] with unit column stride"
+
+
+def hifigan_conv(x: Tensor, T: int, weight: Tensor, bias: Optional[Tensor], k: int, dilation: int = 1, slope: float = 1.0,
+                 resid: Optional[Tensor] = None, out: Optional[Tensor] = None, accumulate: bool = False, scale: float = 1.0,
+                 lengths: Optional[Tensor] = None, len_mul: int = 1) -> Tensor:
+    """ispk_hifigan_conv_{f32,bf16} by weight.dtype: x fp32 [B*T, C_in] rows -> out fp32 [B*T, C_out] =
+    [out +] scale * (bias + Conv1d(k, dilation, "same")(leaky_relu(x, slope)) [+ resid]); weight image [k, C_out, C_in].
+    lengths int64 [B]: utterance b has lengths[b] * len_mul valid rows, the rest read and are written as zeros."""
+    _dev(x, weight, bias, resid, out, lengths)
+    _hifigan_rows(x, "x")
+    R, C_in = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.ndim == 3 and weight.is_contiguous() and weight.shape[0] == k and weight.shape[2] == C_in
+    assert weight.dtype in (torch.float32, torch.bfloat16)
+    C_out = weight.shape[1]
+    assert not accumulate or out is not None, "accumulate needs out="
+    if out is None:
+        out = torch.empty((R, C_out), dtype=torch.float32, device=x.device)
+    _hifigan_rows(out, "out")
+    assert out.shape == (R, C_out)
+    if resid is not None:
+        _hifigan_rows(resid, "resid")
+        assert resid.shape == (R, C_out)
+    ln = _lengths_ptr(lengths, B)
+    if R == 0:
+        return out
+    bf = weight.dtype == torch.bfloat16
+    _launch(f"hifigan_conv_kernel<{'bf16' if bf else 'f32'},{_hifigan_bn(C_out)}>", 2.0 * R * C_out * C_in * k,
+            float(R * 4 * (C_in + C_out * (1 + (resid is not None) + bool(accumulate))) + weight.numel() * weight.element_size()),
+            lib().ispk_hifigan_conv_bf16 if bf else lib().ispk_hifigan_conv_f32, x.data_ptr(), x.stride(0), weight.data_ptr(),
+            _ptr(bias), _ptr(resid), resid.stride(0) if resid is not None else 0, out.data_ptr(), out.stride(0), ln, len_mul, B,
+            T, C_in, C_out, k, dilation, slope, scale, int(accumulate), _stream())
+    return out
+
+
+def _hifigan_bn(C_out: int) -> int:
+    return 128 if C_out % 128 == 0 else 64 if C_out % 64 == 0 else 32
+
+
+def hifigan_upsample(x: Tensor, T: int, weight: Tensor, bias: Optional[Tensor], k: int, stride: int, slope: float = 0.1,
+                     out: Optional[Tensor] = None, lengths: Optional[Tensor] = None, len_mul: int = 1) -> Tensor:
+    """ispk_hifigan_upsample_{f32,bf16} by weight.dtype: x fp32 [B*T, C_in] rows -> out fp32 [B*T*stride, C_out] = bias +
+    ConvTranspose1d(k, stride, padding (k - stride) / 2)(leaky_relu(x, slope)); weight image [k, C_out, C_in] (the module's
+    [C_in, C_out, k] permuted).  lengths[b] * len_mul valid INPUT rows; output rows past stride times that are zeros."""
+    _dev(x, weight, bias, out, lengths)
+    _hifigan_rows(x, "x")
+    R, C_in = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.ndim == 3 and weight.is_contiguous() and weight.shape[0] == k and weight.shape[2] == C_in
+    assert weight.dtype in (torch.float32, torch.bfloat16)
+    C_out = weight.shape[1]
+    if out is None:
+        out = torch.empty((R * stride, C_out), dtype=torch.float32, device=x.device)
+    _hifigan_rows(out, "out")
+    assert out.shape == (R * stride, C_out)
+    ln = _lengths_ptr(lengths, B)
+    if R == 0:
+        return out
+    bf = weight.dtype == torch.bfloat16
+    _launch(f"hifigan_conv_kernel<{'bf16' if bf else 'f32'},{_hifigan_bn(C_out)}>(T)", 2.0 * R * C_out * C_in * k,
+            float(R * 4 * (C_in + C_out * stride) + weight.numel() * weight.element_size()),
+            lib().ispk_hifigan_upsample_bf16 if bf else lib().ispk_hifigan_upsample_f32, x.data_ptr(), x.stride(0),
+            weight.data_ptr(), _ptr(bias), out.data_ptr(), out.stride(0), ln, len_mul, B, T, C_in, C_out, k, stride, slope,
+            _stream())
+    return out
+
+
+def hifigan_post(x: Tensor, T: int, weight: Tensor, bias: Tensor, audio: Tensor, audio_len: Optional[Tensor] = None,
+                 lengths: Optional[Tensor] = None, len_mul: int = 1, slope: float = 0.01) -> Tensor:
+    """ispk_hifigan_post_f32: x fp32 [B*T, C] rows -> audio fp32 [B, S >= T] = tanh(bias + conv7(leaky_relu(x, slope))), zeros
+    from lengths[b] * len_mul on; audio_len int64 [B] = lengths[b] * len_mul.  weight fp32 [7, C] contiguous, bias fp32 [1]."""
+    _dev(x, weight, bias, audio, audio_len, lengths)
+    _hifigan_rows(x, "x")
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and (audio.stride(1) == 1 or audio.shape[1] <= 1)
+    B, S = audio.shape
+    C = x.shape[1]
+    assert x.shape[0] == B * T and weight.shape == (7, C) and weight.is_contiguous() and weight.dtype == torch.float32
+    assert bias.dtype == torch.float32 and bias.numel() == 1
+    assert audio_len is None or (audio_len.dtype == torch.int64 and audio_len.shape == (B,) and audio_len.is_contiguous())
+    ln = _lengths_ptr(lengths, B)
+    if B == 0:
+        return audio
+    _launch("hifigan_post_kernel", 14.0 * B * T * C, float(B * T * C * 4 + B * S * 4), lib().ispk_hifigan_post_f32,
+            _ptr(x) if x.numel() else None, x.stride(0), weight.data_ptr(), bias.data_ptr(), ln, len_mul, audio.data_ptr(),
+            max(audio.stride(0), S), _ptr(audio_len), B, T, S, C, slope, _stream())
     return audio

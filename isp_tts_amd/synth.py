@@ -329,6 +329,61 @@ def make_vocoder_mel(B: int, n_mels: int, T: int, seed: int = SEED) -> torch.Ten
     return torch.from_numpy((x - 4.5 + np.linspace(1.5, -1.5, n_mels)[None, :, None]).astype(np.float32))
 
 
+# ---------------------------------------------------------------------------------------------------- HiFi-GAN generators
+# name -> generator configuration (hifigan.HifiGan's constructor arguments).  "odd": stage lengths that are no powers of two,
+# unequal taps per phase (k 7, stride 3) and the 25-row halo of k 11, dilation 5.
+HIFIGAN_DIMS = {
+    "v1": dict(n_mels=80, upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
+               resblock="1", resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3),
+    "v3": dict(n_mels=80, upsample_initial_channel=256, upsample_rates=(8, 8, 4), upsample_kernel_sizes=(16, 16, 8),
+               resblock="2", resblock_kernel_sizes=(3, 5, 7), resblock_dilation_sizes=((1, 2), (2, 6), (3, 12))),
+    "odd": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
+                resblock="1", resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3, 5),) * 2),
+}
+
+
+def make_hifigan_state_dict(dims=HIFIGAN_DIMS["v1"], seed: int = SEED, weight_norm: Optional[str] = None) -> dict[str, torch.Tensor]:
+    """Synthetic HiFi-GAN generator weights in the official state-dict layout, from keyed streams.  Convolution weights are
+    N(0, s^2 / (C_in k)) with s = 1.4 (first convolution of a type "1" unit), 0.5 (second), 0.7 (type "2"), up-convolutions
+    N(0, 1.4^2 / (C_in k / stride)), conv_post s = 0.1, biases N(0, 0.05^2): on make_vocoder_mel the output peaks at
+    0.16 - 0.9, inside tanh's curved part.  weight_norm None: plain `weight`; "g_v": `weight_g` + `weight_v`; "parametrized":
+    `parametrizations.weight.original0` + `original1`.  v is the plain weight times a per-slice factor in [0.5, 2] and g the
+    plain weight's norm, so g != ||v|| and g v / ||v|| is the plain weight."""
+    if weight_norm not in (None, "g_v", "parametrized"):
+        raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
+    C0, rates, up_k = dims["upsample_initial_channel"], dims["upsample_rates"], dims["upsample_kernel_sizes"]
+    sd: dict[str, torch.Tensor] = {}
+
+    def put(name: str, shape, fan: float, s: float):
+        w = _normal(f"hfg/{name}.w", shape, s / math.sqrt(fan), seed=seed)
+        if weight_norm is None:
+            sd[name + ".weight"] = w
+        else:
+            gk, vk = (".weight_g", ".weight_v") if weight_norm == "g_v" else (".parametrizations.weight.original0",
+                                                                             ".parametrizations.weight.original1")
+            ones = [1] * (len(shape) - 1)
+            f = torch.from_numpy(_rng(f"hfg/{name}.f", seed).uniform(0.5, 2.0, size=(shape[0], *ones)).astype(np.float32))
+            sd[name + gk] = w.double().flatten(1).norm(dim=1).reshape(shape[0], *ones).float()
+            sd[name + vk] = w * f
+        sd[name + ".bias"] = _normal(f"hfg/{name}.b", (shape[0] if not name.startswith("ups.") else shape[1],), 0.05, seed=seed)
+
+    put("conv_pre", (C0, dims["n_mels"], 7), dims["n_mels"] * 7, 1.0)
+    J = len(dims["resblock_kernel_sizes"])
+    for i, (u, k) in enumerate(zip(rates, up_k)):
+        C = C0 >> i
+        put(f"ups.{i}", (C, C // 2, k), C * k / u, 1.4)
+        for j, (r, D) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
+            n = i * J + j
+            for m in range(len(D)):
+                if str(dims["resblock"]) == "1":
+                    put(f"resblocks.{n}.convs1.{m}", (C // 2, C // 2, r), C // 2 * r, 1.4)
+                    put(f"resblocks.{n}.convs2.{m}", (C // 2, C // 2, r), C // 2 * r, 0.5)
+                else:
+                    put(f"resblocks.{n}.convs.{m}", (C // 2, C // 2, r), C // 2 * r, 0.7)
+    put("conv_post", (1, C0 >> len(rates), 7), (C0 >> len(rates)) * 7, 0.1)
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------------- dataset statistics
 # Batches for data.DatasetStats (tests/golden/dataset_stats.npz holds the reference's results on them): pitch in Hz as the
 # extractor delivers it with mean 0 / std 1 - the discrete values fl(fl(1 / tau) * 22050), tau in 27 .. 524, 0 on unvoiced

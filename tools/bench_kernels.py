@@ -2,7 +2,9 @@
 """Micro-benchmark of the hot kernels at the BASELINE config-3 shapes (B=64: 32768 decoder rows, 6400 encoder rows).
 HIP-event timing, interleaved rounds, median.  Usage: python tools/bench_kernels.py [f32|bf16] [--rows 32768]
 `python tools/bench_kernels.py adaptor`: the temporal adaptor's regulators and averagers instead, hard durations beside soft, and
-the speaker-embedding add with its table gradient, at B=64, L=100, M=512, D=384, each with its traffic floor at the 6.3 TB/s a float4 copy reaches on the MI355X."""
+the speaker-embedding add with its table gradient, at B=64, L=100, M=512, D=384, each with its traffic floor at the 6.3 TB/s a float4 copy reaches on the MI355X.
+`python tools/bench_kernels.py hifigan [bf16]`: the HiFi-GAN convolution kernels (csrc/hifigan.hip) at the V1 stage shapes of the
+B=64 x 512-frame batch."""
 import os
 import sys
 
@@ -82,6 +84,37 @@ if "adaptor" in sys.argv:
     for name, fn, nbytes in adaptor_cases():
         med, mn = time_it(fn)
         print(f"{name:36s} median {med:7.1f} us  min {mn:7.1f} us  {nbytes / 1e6:7.2f} MB  floor {nbytes / 6.3e6:6.2f} us  {nbytes / med / 1e3:7.1f} GB/s")
+    sys.exit(0)
+
+def hifigan_cases():
+    """One dilated convolution and the transposed convolution of every V1 stage, plus the output layer, at B=64 x 512 frames."""
+    B, T, C = 64, 512, 512
+    cases = []
+    for u, ku, (k, d) in zip((8, 8, 2, 2), (16, 16, 4, 4), ((7, 3), (7, 3), (11, 5), (11, 5))):
+        x = synth._normal(f"b/hfg/x{C}", (B * T, C)).to(dev)
+        wu = synth._normal(f"b/hfg/up{C}", (ku, C // 2, C), (C * ku / u) ** -0.5).to(dev).to(dt)
+        up = torch.empty((B * T * u, C // 2), device=dev)
+        cases.append((f"upsample {C}->{C // 2} k={ku} u={u} T={T}", lambda x=x, wu=wu, up=up, T=T, ku=ku, u=u:
+                      runtime.hifigan_upsample(x, T, wu, None, ku, u, out=up), 2 * B * T * C * (C // 2) * ku,
+                      4 * B * T * (C + u * C // 2)))
+        T, C = T * u, C // 2
+        wc = synth._normal(f"b/hfg/w{C}", (k, C, C), (C * k) ** -0.5).to(dev).to(dt)
+        y = torch.empty_like(up)
+        cases.append((f"conv {C} k={k} d={d} T={T} +resid", lambda up=up, wc=wc, y=y, T=T, k=k, d=d:
+                      runtime.hifigan_conv(up, T, wc, None, k, d, 0.1, resid=up, out=y), 2 * B * T * C * C * k, 12 * B * T * C))
+        del x
+    wp, bp = synth._normal("b/hfg/post", (7, C), 0.1).to(dev), torch.zeros(1, device=dev)
+    audio = torch.empty((B, T), device=dev)
+    cases.append((f"post {C}->1 T={T}", lambda: runtime.hifigan_post(y, T, wp, bp, audio), 14 * B * T * C, 4 * B * T * (C + 1)))
+    return cases
+
+
+if "hifigan" in sys.argv:
+    dt = torch.bfloat16 if "bf16" in sys.argv else torch.float32
+    print(f"HiFi-GAN V1 kernels, B=64 x 512 frames, {dt}")
+    for name, fn, flops, nbytes in hifigan_cases():
+        med, mn = time_it(fn, rounds=5, inner=3)
+        print(f"{name:40s} median {med:9.1f} us  min {mn:9.1f} us  {flops / med / 1e6:7.1f} TFLOP/s  {nbytes / med / 1e3:7.1f} GB/s")
     sys.exit(0)
 
 x384 = synth._normal("b/x", (R, 384)).to(dev).to(dt)
