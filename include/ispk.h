@@ -448,6 +448,12 @@ int32_t ispk_flow_finish_f32(const float* pred_raw, const float* flow, const flo
 int32_t ispk_embed_tokens_f32(const int64_t* text, const float* table, int64_t ld_table, int32_t vocab,
                               const int64_t* text_len, float* emb, uint8_t* mask, int32_t B, int32_t L, int32_t D,
                               ispk_stream_t stream);
+/* ispk_embed_tokens_f32 plus a second gather with the same (clamped) ids: qkv[b][l][:] = qkv_table[text[b][l]][:], bf16 rows of
+ * N elements (N % 8 == 0) - the text encoder's first attention_norm + [to_q; to_kv] projection, staged once per weight version
+ * over the vocab's rows, since its input is Embedding(text) alone. */
+int32_t ispk_embed_tokens_qkv(const int64_t* text, const float* table, int64_t ld_table, int32_t vocab, const int64_t* text_len,
+                              float* emb, uint8_t* mask, const uint16_t* qkv_table, int64_t ld_qkv_table, uint16_t* qkv,
+                              int32_t B, int32_t L, int32_t D, int32_t N, ispk_stream_t stream);
 int32_t ispk_add_speaker_f32(float* x, const float* table, int64_t ld_table, int32_t speakers, const int64_t* speaker,
                              int32_t id_stride, int32_t B, int32_t L, int32_t D, ispk_stream_t stream);
 int32_t ispk_add_speaker_out_f32(const float* x, float* out, const float* table, int64_t ld_table, int32_t speakers,
@@ -466,6 +472,16 @@ int32_t ispk_length_regulate_f32(const float* alignment, const float* dur_f32, c
 int32_t ispk_length_regulate_split_bf16(const float* alignment, const float* dur_f32, const int64_t* dur_i64, const int64_t* enc_len,
                                  const float* x, int64_t ldx, float* out, int64_t* dec_len, uint8_t* dec_mask, int32_t B,
                                  int32_t M, int32_t L, int32_t D, int32_t max_len, int32_t dur_cols, ispk_stream_t stream);
+/* ispk_length_regulate_split_bf16 with the consuming layer's attention_norm + [to_q; to_kv] projection as its epilogue (dim 384):
+ * out, dec_len and dec_mask as without it, bit for bit; qkv bf16 [B * M][512] (ld_qkv elements between rows, every row of every
+ * frame tile, rows past dec_len included) = bf16(LayerNorm(out row; norm_gamma, norm_beta, norm_eps), two-pass statistics) times
+ * Wqkv_chunks = ispk_chunk_k16_bf16([Wq; Wkv]): [384/16][512][16], fp32 accumulation - what ispk_gemm_bf16_lnin computes from
+ * `out` with its own statistics.  An utterance's frame tiles are mapped to one XCD (a speed choice: no result depends on it). */
+int32_t ispk_length_regulate_qkv_bf16(const float* alignment, const float* dur_f32, const int64_t* dur_i64, const int64_t* enc_len,
+                                      const float* x, int64_t ldx, float* out, int64_t* dec_len, uint8_t* dec_mask,
+                                      const float* norm_gamma, const float* norm_beta, float norm_eps, const uint16_t* Wqkv_chunks,
+                                      uint16_t* qkv, int64_t ld_qkv, int32_t B, int32_t M, int32_t L, int32_t D, int32_t max_len,
+                                      int32_t dur_cols, ispk_stream_t stream);
 /* ... and for the split-fp16 parity path: the same three products over fp16 terms (22 significant bits per operand: fp32-grade). */
 int32_t ispk_length_regulate_split_f16(const float* alignment, const float* dur_f32, const int64_t* dur_i64, const int64_t* enc_len,
                                 const float* x, int64_t ldx, float* out, int64_t* dec_len, uint8_t* dec_mask, int32_t B,

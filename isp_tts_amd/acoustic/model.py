@@ -20,6 +20,7 @@ from .. import runtime
 from ..staging import StagedWeights
 from ..modules.constructor import Constructor
 from ..modules.transformer import Transformer
+from ..modules.transformer.plan import Hand, Handed
 from ..utils import get_mask_from_lengths
 from .alignment import Aligner, AlignerOutput
 from .temporal_adaptor import FlowTemporalAdaptor, TemporalAdaptorOutput
@@ -57,6 +58,9 @@ class AcousticModel(nn.Module, Constructor):
         self.temporal_adaptor = FlowTemporalAdaptor.init(temporal_adaptor, encoder_dim=enc_dim)
         self.decoder = Transformer.init(decoder, emb_dim=enc_dim)
         self.to_mel = nn.Linear(self.decoder.dim, mel_dim)
+        # bf16 no-tape forward: the encoder's first attention_norm + q/kv projection as a per-token table, gathered beside the
+        # embedding rows (`_embed`).  Off: the LayerNorm and GEMM launches over the embedded rows.
+        self.token_qkv_table = True
         self.overlap_streams = True          # run the aligner's mel-side branch beside the text encoder (forward())
         self._side_streams: dict = {}
         self.register_buffer("pitch_mean", torch.tensor(float(pitch_mean or 0.)))
@@ -102,6 +106,44 @@ class AcousticModel(nn.Module, Constructor):
         if dec_out.dtype == torch.bfloat16:
             w = self._cache.get(torch.bfloat16, (w,), lambda: w.detach().to(torch.bfloat16).contiguous())
         return runtime.to_mel(dec_out, w, self.to_mel.bias, dec_mask)
+
+    def _embed(self, text: Tensor, text_len: Optional[Tensor], want_mask: bool = True):
+        """Embedding(text) and the key mask (model.py:131-134) -> (emb, mask, what is handed to the encoder's first layer).
+        That layer's attention_norm and [to_q; to_kv] read the embedded rows and nothing else, so their result is a function of
+        the token id and the weights: with `token_qkv_table` on, the bf16 path stages it once per weight version for every row of
+        the table - the layer's own LayerNorm and GEMM launches over `vocab` rows - and the lookup kernel gathers both rows.
+        Only where that layer takes handed q/kv rows: bf16, a plain LayerNorm, no input projection, rows as wide as the
+        attention kernel's buffer; elsewhere (fp32, split fp16) nothing is handed."""
+        table, enc = self.text_embedding.weight, self.encoder
+        first = enc.layers[0]
+        norm, att = first.attention_norm, first.attention
+        if not (self.token_qkv_table and text.is_cuda and att.compute_dtype == torch.bfloat16 and not first.adaptive_norm
+                and norm.weight is not None and norm.bias is not None and isinstance(enc.project_emb, nn.Identity)
+                and (att.heads * 64 + 128) % 8 == 0):
+            return (*runtime.embed_tokens(text, table, text_len, want_mask=want_mask), Handed())
+
+        def build():
+            with torch.no_grad():
+                rows = runtime.layernorm(table.detach().float().contiguous(), norm.weight, norm.bias, eps=norm.eps,
+                                         out_dtype=torch.bfloat16)
+                return runtime.gemm(rows, att._staged(torch.bfloat16)[0])
+        qkv_table = self._cache.get("token_qkv", (table, norm.weight, norm.bias, att.to_q.weight, att.to_kv.weight), build)
+        emb, mask, qkv = runtime.embed_tokens_qkv(text, table, qkv_table, text_len, want_mask=want_mask)
+        return emb, mask, Handed(Hand.QKV, qkv)
+
+    def _decoder_first(self):
+        """The decoder's first layer where it can take its q/kv rows from the length regulator's epilogue
+        (`LengthRegulator.hand_qkv`), else None: bf16, a plain LayerNorm, no input projection, 6 heads at dim 384."""
+        dec = self.decoder
+        first = dec.layers[0]
+        norm, att = first.attention_norm, first.attention
+        ok = (att.compute_dtype == torch.bfloat16 and not first.adaptive_norm and norm.weight is not None and norm.bias is not None
+              and isinstance(dec.project_emb, nn.Identity) and dec.dim == 384 and att.heads * 64 + 128 == 512)
+        return first if ok else None
+
+    def _decoder_handed(self) -> Handed:
+        qkv = self.temporal_adaptor.length_regulator.qkv
+        return Handed(Hand.QKV, qkv) if qkv is not None else Handed()
 
     def forward(self, text: Tensor, text_len: Tensor, mel: Tensor, mel_len: Tensor, pitch: Optional[Tensor] = None,
                 energy: Optional[Tensor] = None, speaker: Optional[Tensor] = None, sigma: float = 0., steps: int = 1, *,
@@ -151,8 +193,8 @@ class AcousticModel(nn.Module, Constructor):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 q_proj = self.aligner.attention.project_queries(mel, mel_len)
-        token_emb, enc_mask = runtime.embed_tokens(text, self.text_embedding.weight, text_len)   # model.py:131-134
-        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_len).out
+        token_emb, enc_mask, handed = self._embed(text, text_len)                               # model.py:131-134
+        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_len, handed=handed).out
         if q_proj is not None:
             main.wait_stream(side)
             q_proj.record_stream(main)
@@ -173,10 +215,12 @@ class AcousticModel(nn.Module, Constructor):
             enc_out=enc_out, enc_mask=enc_mask, max_dec_len=mel.size(2),
             duration_target=aligner_output.attn_hard_duration, alignment=aligner_output.attn_soft,
             pitch_target_dense=pitch, energy_target_dense=energy, noise=flow_noise, time_steps=flow_time,
-            enc_len=text_len, predictor_stream=branch, duration_sum=mel_len if branch is not None and not hard else None)
+            enc_len=text_len, predictor_stream=branch, duration_sum=mel_len if branch is not None and not hard else None,
+            qkv_for=self._decoder_first())
         dec_len = adaptor_output.dec_lengths
         dec_mask = adaptor_output.dec_mask              # arange(frames) < dec_len, from the length-regulation kernel
-        dec_out = self.decoder(adaptor_output.enc_out, mask=dec_mask, key_len=dec_len, out_dtype=self.compute_dtype).out
+        dec_out = self.decoder(adaptor_output.enc_out, mask=dec_mask, key_len=dec_len, out_dtype=self.compute_dtype,
+                               handed=self._decoder_handed()).out
         mel_out = self._to_mel(dec_out, dec_mask)
         if q_proj is not None:
             # join the MAS / flow-predictor branch (it ran beside the embedding stack and the decoder) before handing out its tensors
@@ -200,8 +244,8 @@ class AcousticModel(nn.Module, Constructor):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             q_proj = self.aligner.attention.project_queries(mel, mel_len)
-        token_emb, enc_mask = runtime.embed_tokens(text, self.text_embedding.weight, text_len)
-        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_len).out
+        token_emb, enc_mask, handed = self._embed(text, text_len)
+        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_len, handed=handed).out
         main.wait_stream(side)
         q_proj.record_stream(main)
         attn_soft, attn_logits = self.aligner.attention(mel, enc_out.transpose(1, 2).detach(), mel_len, text_len,
@@ -227,9 +271,11 @@ class AcousticModel(nn.Module, Constructor):
         ad = self.temporal_adaptor
         feats = st["feats"]
         x = ad.embedding(feats[..., 1:3], mask=st["enc_mask"][..., None], key_len=text_len, residual=st["enc_out"])
-        dec_in, dec_len = ad.length_regulator(x, mel_len.view(-1, 1), max_len=max_dec_len, alignment=st["attn_soft"])
+        dec_in, dec_len = ad.length_regulator(x, mel_len.view(-1, 1), max_len=max_dec_len, alignment=st["attn_soft"],
+                                              qkv_for=self._decoder_first())
         dec_mask = ad.length_regulator.dec_mask
-        dec_out = self.decoder(dec_in, mask=dec_mask, key_len=dec_len, out_dtype=self.compute_dtype).out
+        dec_out = self.decoder(dec_in, mask=dec_mask, key_len=dec_len, out_dtype=self.compute_dtype,
+                               handed=self._decoder_handed()).out
         return {"mel": self._to_mel(dec_out, dec_mask), "dec_in": dec_in, "dec_len": dec_len, "dec_mask": dec_mask}
 
     @staticmethod
@@ -252,9 +298,8 @@ class AcousticModel(nn.Module, Constructor):
               max_dec_len: Optional[int] = None):
         """model.py:177-238: masks only for batch > 1 (:191-201, :228)."""
         batch_infer = input_sequence.shape[0] > 1
-        token_emb, enc_mask = runtime.embed_tokens(input_sequence, self.text_embedding.weight,
-                                                   text_lengths if batch_infer else None, want_mask=batch_infer)
-        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_lengths if batch_infer else None).out
+        token_emb, enc_mask, handed = self._embed(input_sequence, text_lengths if batch_infer else None, want_mask=batch_infer)
+        enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_lengths if batch_infer else None, handed=handed).out
         if self.speaker_embedding is not None and speaker is not None:      # model.py:205-207
             enc_out = runtime.add_speaker_(enc_out, self.speaker_embedding.weight, speaker)
         if pitch_normalize:
@@ -265,10 +310,10 @@ class AcousticModel(nn.Module, Constructor):
             enc_out=enc_out, enc_mask=enc_mask, duration_target=duration_target, pitch_target=pitch_target,
             energy_target=energy_target, duration_factor=duration_factor, pitch_factor=pitch_factor,
             pitch_delta=pitch_delta, steps=steps, noise=flow_noise, max_dec_len=max_dec_len,
-            enc_len=text_lengths if batch_infer else None)
+            enc_len=text_lengths if batch_infer else None, qkv_for=self._decoder_first())
         dec_mask = adaptor_output.dec_mask if batch_infer else None
         dec_out = self.decoder(adaptor_output.enc_out, mask=dec_mask, key_len=adaptor_output.dec_lengths if batch_infer else None,
-                               out_dtype=self.compute_dtype).out
+                               out_dtype=self.compute_dtype, handed=self._decoder_handed()).out
         return self._to_mel(dec_out, dec_mask), adaptor_output
 
     # ---- checkpoint drop-in (tts/models/base.py:39-108 of the reference; trainer.py:361-372 writes the file) ----

@@ -203,9 +203,15 @@ class LengthRegulator(nn.Module):
     (float(duration) + .5).long() times by `ispk_hard_regulate_f32` - a row copy, the same bits on every compute path.  Without
     `frames` the output length is data, as in the reference: the longest decoder length is read back to the host."""
     split_bf16 = False
+    # bf16 path, soft branch: the kernel's epilogue also applies the attention_norm and the q/kv projection of the layer that
+    # consumes the rows (`qkv_for`; ispk_length_regulate_qkv_bf16) - the rows are in its accumulators.  The q/kv rows of the last
+    # call are kept in `self.qkv`, as the mask is in `self.dec_mask` (None: not produced).  Off: that layer's own launch.
+    hand_qkv = True
+    qkv: Optional[Tensor] = None
 
     def forward(self, x: Tensor, durations: Tensor, max_len: Optional[int] = None, alignment: Optional[Tensor] = None, *,
-                enc_len: Optional[Tensor] = None, frames: Optional[int] = None, hard: bool = False):
+                enc_len: Optional[Tensor] = None, frames: Optional[int] = None, hard: bool = False, qkv_for=None):
+        self.qkv = None
         if alignment is None and (hard or frames is None or durations.dtype == torch.int64):
             if frames is None:
                 frames = int((durations.float() + 0.5).long().sum(dim=1).max().item())
@@ -221,6 +227,12 @@ class LengthRegulator(nn.Module):
         if max_len is not None and alignment is not None:
             rows = min(rows, max_len)
             alignment = alignment[:, :rows]
+        if self.hand_qkv and qkv_for is not None and self.split_bf16 is True and x.is_cuda and x.shape[-1] == 384:
+            norm, att = qkv_for.attention_norm, qkv_for.attention
+            out, dec_lens, self.dec_mask, self.qkv = runtime.length_regulate(
+                x.float(), durations, alignment, rows, max_len=-1 if max_len is None else max_len, enc_len=enc_len,
+                split_bf16=True, next_qkv=(norm.weight, norm.bias, norm.eps, att._chunked_wqkv()))
+            return out, dec_lens
         out, dec_lens, self.dec_mask = runtime.length_regulate(x.float(), durations, alignment, rows,
                                                                max_len=-1 if max_len is None else max_len, enc_len=enc_len,
                                                                split_bf16=self.split_bf16)
@@ -284,7 +296,7 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
                 alignment: Optional[Tensor] = None, pitch_target_dense: Optional[Tensor] = None,
                 energy_target_dense: Optional[Tensor] = None, *, noise: Optional[Tensor] = None,
                 time_steps: Optional[Tensor] = None, enc_len: Optional[Tensor] = None,
-                predictor_stream=None, duration_sum: Optional[Tensor] = None) -> TemporalAdaptorOutput:
+                predictor_stream=None, duration_sum: Optional[Tensor] = None, qkv_for=None) -> TemporalAdaptorOutput:
         """temporal_adaptor.py:238-312 (teacher-forced: the decoder input uses the TARGET pitch/energy, :284,:292).
 
         What the DECODER waits for is short: pitch / energy targets (soft averages over attn_soft), the embedding stack,
@@ -300,7 +312,9 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
 
         With hard durations (`soft_duration` off) `alignment` is ignored (:250-251): the targets are the hard averages over the
         durations' segments and the regulator repeats rows by them, so the decoder path DOES wait for `duration_target` - it
-        must be complete on the current stream, and `duration_sum` has no use.  The flow predictor may still run beside it."""
+        must be complete on the current stream, and `duration_sum` has no use.  The flow predictor may still run beside it.
+
+        `qkv_for`: the layer that will consume the decoder input (the decoder's first) - see `LengthRegulator.hand_qkv`."""
         assert duration_target is not None and (alignment is not None or not self.soft_duration)
         assert pitch_target_dense is not None and energy_target_dense is not None
         hard = not self.soft_duration
@@ -334,7 +348,7 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
             enc_out_ = self.embedding(features, mask=m3, key_len=enc_len, residual=enc_out_)   # enc_out + embedding(...)
             # (hard durations: `frames` fixes the output length at max_dec_len, as the alignment's rows do - no host read-back)
             return self.length_regulator(enc_out_, len_src, max_len=max_dec_len, alignment=alignment,
-                                         frames=max_dec_len if hard else None)
+                                         frames=max_dec_len if hard else None, qkv_for=qkv_for)
 
         if not (side is not None and self.predictor_first):
             enc_out, dec_lens = decoder_input(enc_out)
@@ -367,7 +381,7 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
               duration_factor: float = 1.0, pitch_target: Optional[Tensor] = None, pitch_factor: float = 1.0,
               pitch_delta: float = 0., energy_target: Optional[Tensor] = None, energy_factor: float = 1.0,
               energy_delta: float = 0., steps: int = 4, *, noise: Optional[Tensor] = None,
-              max_dec_len: Optional[int] = None, enc_len: Optional[Tensor] = None) -> TemporalAdaptorOutput:
+              max_dec_len: Optional[int] = None, enc_len: Optional[Tensor] = None, qkv_for=None) -> TemporalAdaptorOutput:
         """temporal_adaptor.py:331-408.  Durations stay fractional with soft_duration (:355-356) and are rounded without it;
         the embedding transformer gets NO mask even when batched (:384).  `max_dec_len` (optional) fixes the decoder length
         without reading `dec_lens.max()` back to the host."""
@@ -394,7 +408,7 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
             max_dec_len = int((duration_pred.sum(dim=1) + 0.5).long().max().item())
         # :388-397: soft path (generate_soft_path) and length regulation in one kernel
         enc_out, dec_lens = self.length_regulator(enc_out, duration_pred, alignment=None, enc_len=enc_lens,
-                                                  frames=max_dec_len)
+                                                  frames=max_dec_len, qkv_for=qkv_for)
         return TemporalAdaptorOutput(enc_out=enc_out, log_duration=None, duration=duration_pred, dec_lengths=dec_lens,
                                      pitch=pitch.squeeze(-1), energy=energy.squeeze(-1), pitch_target=pitch_target,
                                      energy_target=energy_target, dec_mask=self.length_regulator.dec_mask)

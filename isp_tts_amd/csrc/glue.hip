@@ -28,6 +28,31 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int64_t* __rest
     }
 }
 
+// The same lookup with the first layer's q/kv rows gathered beside it (ispk_embed_tokens_qkv): the text encoder's first
+// attention_norm + [to_q; to_kv] projection reads nothing but Embedding(text), so its result is one of `vocab` distinct rows -
+// staged once per weight version as qkv_table bf16 [vocab][N] - and the LayerNorm and GEMM launches become this second gather.
+// Same id clamping, same mask; each lane moves 16-byte vectors of both rows.
+__global__ __launch_bounds__(256) void embed_tokens_qkv_kernel(const int64_t* __restrict__ text, const float* __restrict__ table,
+                                                               int64_t ld_table, int vocab, const int64_t* __restrict__ text_len,
+                                                               float* __restrict__ emb, uint8_t* __restrict__ mask,
+                                                               const uint16_t* __restrict__ qkv_table, int64_t ld_qkv_table,
+                                                               uint16_t* __restrict__ qkv, int rows, int L, int D, int N) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    int64_t id = text[row];
+    id = (id < 0 || id >= vocab) ? 0 : id;
+    const f32x4* src = reinterpret_cast<const f32x4*>(table + id * ld_table);
+    f32x4* dst = reinterpret_cast<f32x4*>(emb + (int64_t)row * D);
+    for (int c = lane; c < D / 4; c += 64) dst[c] = src[c];
+    const f32x4* qsrc = reinterpret_cast<const f32x4*>(qkv_table + id * ld_qkv_table);
+    f32x4* qdst = reinterpret_cast<f32x4*>(qkv + (int64_t)row * N);
+    for (int c = lane; c < N / 8; c += 64) qdst[c] = qsrc[c];
+    if (mask && lane == 0) {
+        const int b = row / L, l = row - b * L;
+        mask[row] = text_len ? (uint8_t)(l < text_len[b]) : (uint8_t)1;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ speaker embedding
 // models/acoustic/model.py:205-207 (`infer`): enc_out = enc_out + speaker_embedding(speaker) - nn.Embedding rows broadcast
 // over the text axis.  In place, every row of the utterance (padded ones too: the reference adds before any re-masking).
@@ -250,21 +275,49 @@ __device__ __forceinline__ f32x16 lr_mfma(const bf16x8& a, const bf16x8& b, cons
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
-template <int NT, int kSplit = 0>   // D = 128 * NT: a wave owns NT 32-feature tiles; kSplit: 0 exact fp32, 1 bf16 terms, 2 fp16 terms
-__global__ __launch_bounds__(256) void length_regulate_kernel(const float* __restrict__ align, const float* __restrict__ dur_f,
-                                                              const int64_t* __restrict__ dur_i,
-                                                              const int64_t* __restrict__ enc_len,
-                                                              const float* __restrict__ x, int64_t ldx,
-                                                              float* __restrict__ out, int64_t* __restrict__ dec_len,
-                                                              uint8_t* __restrict__ dec_mask, int M, int L, int max_len,
-                                                              int dur_cols) {
+// kQkv (ispk_length_regulate_qkv_bf16): the decoder's first attention_norm + [to_q; to_kv] projection as the epilogue.  The
+// finished rows are stored as without it; then their two-pass LayerNorm statistics come from the accumulators (a butterfly over
+// the 32 lanes of a row, the four waves' partial sums through LDS), the normalised rows pass through LDS as bf16 - a frame's 384
+// features live in four waves, the projection sums over them - and wave w multiplies the 64 frames by columns [128 w, 128 w + 128)
+// of the weight, read as MFMA fragments straight from the k-step chunk image (ispk_chunk_k16_bf16: a wave's fragment of one
+// step and column tile is 1 KiB contiguous), three steps ahead; the first three are requested before the statistics.  The q/kv
+// tile goes back through LDS so that a wave stores whole 1-KiB rows.
+struct LrQkv {
+    const float* gamma;       // attention_norm of the consuming layer
+    const float* beta;
+    float eps;
+    const uint16_t* w;        // [D / 16][512][16] bf16
+    uint16_t* qkv;            // bf16 [B * M][512] at ld elements between rows
+    int64_t ld;
+};
+constexpr int kLrQkvN = 512, kLrQkvLd = kLrQkvN + 8, kLrQkvDepth = 3;
+constexpr size_t kLrQkvLds = 16 + (size_t)kLrRows * kLrQkvLd * 2 + (4 * kLrRows + 2 * kLrRows) * sizeof(float);
+
+template <int NT, int kSplit, bool kQkv>   // D = 128 * NT: a wave owns NT 32-feature tiles; kSplit: 0 exact fp32, 1 bf16 terms, 2 fp16 terms
+__device__ __forceinline__ void length_regulate_body(const float* __restrict__ align, const float* __restrict__ dur_f,
+                                                     const int64_t* __restrict__ dur_i, const int64_t* __restrict__ enc_len,
+                                                     const float* __restrict__ x, int64_t ldx, float* __restrict__ out,
+                                                     int64_t* __restrict__ dec_len, uint8_t* __restrict__ dec_mask, int M, int L,
+                                                     int max_len, int dur_cols, const LrQkv& q) {
     constexpr int D = 128 * NT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int64_t& s_dec = *reinterpret_cast<int64_t*>(smem);                      // (all LDS in the dynamic region: a static
     float* As = reinterpret_cast<float*>(smem + 16);                         //  object would shift its 16-byte alignment)
     float* Xs = As + kLrRows * kLrAld;                                       // [16][D]   (As: [64][17] = 4352 B)
     float* cum = Xs + kLrChunk * D;                                          // [L + 1]   (soft path only): cum[t] = sum_{u<t}
-    const int b = blockIdx.y, y0 = blockIdx.x * kLrRows, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int b = blockIdx.y, bx = blockIdx.x;
+    if constexpr (kQkv) {
+        // XCD-aware (utterance, frame tile) mapping, as csrc/attention.hip's: workgroups are dealt to the 8 XCDs round-robin in
+        // linear order, so the frame tiles of one utterance - which all read its [L][D] rows - would land on 8 different L2s.
+        // Within each run of 8 * gridDim.x workgroups, utterance = 8 * run + (linear % 8), tile = (linear / 8) % gridDim.x.
+        const int gx = gridDim.x, lin = blockIdx.y * gx + blockIdx.x, run = lin / (8 * gx);
+        if ((run + 1) * 8 <= (int)gridDim.y) {            // (a ragged last run keeps the plain mapping)
+            const int r = lin - run * 8 * gx;
+            b = run * 8 + (r & 7);
+            bx = r >> 3;
+        }
+    }
+    const int y0 = bx * kLrRows, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool soft = align == nullptr;
 
     // ---- decoder length of this utterance (every workgroup of the utterance computes the same value; tile 0 stores it)
@@ -292,7 +345,7 @@ __global__ __launch_bounds__(256) void length_regulate_kernel(const float* __res
         if (max_len >= 0 && dl > max_len) dl = max_len;
         if (lane == 0) {
             s_dec = dl;
-            if (blockIdx.x == 0) dec_len[b] = dl;
+            if (bx == 0) dec_len[b] = dl;
         }
     }
     __syncthreads();
@@ -404,6 +457,152 @@ __global__ __launch_bounds__(256) void length_regulate_kernel(const float* __res
                 const int y = y0 + rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
                 if (y < M) ob[(int64_t)y * D + wave * (32 * NT) + ct * 32 + (lane & 31)] = acc[rt][ct][i];
             }
+
+    if constexpr (kQkv) {
+        static_assert(NT == 3 && kSplit == 1, "the q/kv epilogue is built for dim 384 on the bf16 path");
+        constexpr int kSteps = D / 16, kAld = D + 8, kRing = kLrQkvDepth + 1;
+        uint16_t* An = reinterpret_cast<uint16_t*>(smem + 16);               // [64][D + 8] bf16: the normalised rows
+        uint16_t* Qs = An;                                                   // [64][520] bf16: the q/kv tile (after the product)
+        float* red = reinterpret_cast<float*>(smem + 16 + kLrRows * kLrQkvLd * 2);     // [4 waves][64 rows]
+        float* stat = red + 4 * kLrRows;                                     // mean[64], rstd[64]
+        const int r = lane & 31, kh = lane >> 5;
+        // the weight fragments of this wave's 128 columns: lane (column r, half kh) of column tile ct, step s_
+        const uint16_t* wl = q.w + ((int64_t)(wave * 128 + r) * 16 + 8 * kh);
+        bf16x8 bq[kRing][4];
+        auto wload = [&](int s_, bf16x8 (&dst)[4]) {
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+                dst[ct] = *reinterpret_cast<const bf16x8*>(wl + ((int64_t)s_ * kLrQkvN + ct * 32) * 16);
+        };
+        // sum over the 32 lanes of a half-wave of 32 values each, in 31 exchanges: at distance h a lane keeps the half of its
+        // values that its bit h selects and adds the partner's; lane l ends with the sum of value l & 31 in v[0]
+        auto butterfly = [&](float (&v)[32]) {
+            static_for<0, 5>([&](auto st) {
+                constexpr int h = 16 >> decltype(st)::value;
+                const bool up = (lane & h) != 0;
+#pragma unroll
+                for (int k = 0; k < h; ++k) {
+                    const float keep = up ? v[k + h] : v[k], send = up ? v[k] : v[k + h];
+                    v[k] = keep + __shfl_xor(send, h, 64);
+                }
+            });
+        };
+        // value k = 16 rt + i of a lane is row 32 rt + (i & 3) + 8 (i >> 2) + 4 kh of the tile; the row whose sum lane l holds:
+        const int own = 32 * (r >> 4) + (r & 3) + 8 * ((r & 15) >> 2) + 4 * kh;
+        float v[32];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[16 * rt + i] = (acc[rt][0][i] + acc[rt][1][i]) + acc[rt][2][i];
+        butterfly(v);
+        __syncthreads();          // every wave is done with the token loop's LDS
+        red[wave * kLrRows + own] = v[0];
+        __syncthreads();
+        if (tid < kLrRows) stat[tid] = ((red[tid] + red[kLrRows + tid]) + (red[2 * kLrRows + tid] + red[3 * kLrRows + tid])) * (1.0f / D);
+        __syncthreads();
+        // (the 4 rows of registers 4 g .. 4 g + 3 are consecutive: one 16-byte read)
+        auto rows4 = [&](const float* p, int rt, int g) { return *reinterpret_cast<const f32x4*>(p + 32 * rt + 8 * g + 4 * kh); };
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 m = rows4(stat, rt, g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * g + e;
+                    const float d0 = acc[rt][0][i] - m[e], d1 = acc[rt][1][i] - m[e], d2 = acc[rt][2][i] - m[e];
+                    v[16 * rt + i] = (d0 * d0 + d1 * d1) + d2 * d2;
+                }
+            }
+        butterfly(v);
+#pragma unroll
+        for (int s_ = 0; s_ < kLrQkvDepth; ++s_) wload(s_, bq[s_]);      // (in flight across the rest of the LayerNorm)
+        red[wave * kLrRows + own] = v[0];      // (its readers of the first pass are behind the barrier above)
+        __syncthreads();
+        if (tid < kLrRows) {
+            const float var = ((red[tid] + red[kLrRows + tid]) + (red[2 * kLrRows + tid] + red[3 * kLrRows + tid])) * (1.0f / D);
+            stat[kLrRows + tid] = 1.0f / sqrtf(var + q.eps);
+        }
+        __syncthreads();
+        float ga[NT], be[NT];
+#pragma unroll
+        for (int ct = 0; ct < NT; ++ct) {
+            ga[ct] = q.gamma[wave * (32 * NT) + ct * 32 + r];
+            be[ct] = q.beta[wave * (32 * NT) + ct * 32 + r];
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 m = rows4(stat, rt, g), rs = rows4(stat + kLrRows, rt, g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int i = 4 * g + e, row = 32 * rt + 8 * g + 4 * kh + e;
+#pragma unroll
+                    for (int ct = 0; ct < NT; ++ct)
+                        An[row * kAld + wave * (32 * NT) + ct * 32 + r] = f32_to_bf16((acc[rt][ct][i] - m[e]) * rs[e] * ga[ct] + be[ct]);
+                }
+            }
+        __syncthreads();
+        f32x16 qa[2][4];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) qa[rt][ct][i] = 0.f;
+        static_assert(kSteps % kRing == 0, "the ring is walked in whole turns");
+#pragma unroll 1
+        for (int s0 = 0; s0 < kSteps; s0 += kRing)
+            static_for<0, kRing>([&](auto s_) {
+                constexpr int S = decltype(s_)::value;
+                if (s0 + S + kLrQkvDepth < kSteps) wload(s0 + S + kLrQkvDepth, bq[(S + kLrQkvDepth) % kRing]);
+                const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(An + r * kAld + 16 * (s0 + S) + 8 * kh);
+                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(An + (32 + r) * kAld + 16 * (s0 + S) + 8 * kh);
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    qa[0][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, bq[S][ct], qa[0][ct], 0, 0, 0);
+                    qa[1][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, bq[S][ct], qa[1][ct], 0, 0, 0);
+                }
+            });
+        __syncthreads();          // every wave has read its last fragment of An: the q/kv tile takes its place
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    Qs[(32 * rt + (i & 3) + 8 * (i >> 2) + 4 * kh) * kLrQkvLd + wave * 128 + ct * 32 + r] = f32_to_bf16(qa[rt][ct][i]);
+        __syncthreads();
+        uint16_t* qb = q.qkv + (int64_t)b * M * q.ld;
+        for (int row = wave; row < kLrRows; row += 4)       // a wave stores one whole 1-KiB row per instruction
+            if (y0 + row < M)
+                *reinterpret_cast<u32x4*>(qb + (int64_t)(y0 + row) * q.ld + lane * 8) =
+                    *reinterpret_cast<const u32x4*>(Qs + row * kLrQkvLd + lane * 8);
+    }
+}
+
+template <int NT, int kSplit = 0>
+__global__ __launch_bounds__(256) void length_regulate_kernel(const float* __restrict__ align, const float* __restrict__ dur_f,
+                                                              const int64_t* __restrict__ dur_i,
+                                                              const int64_t* __restrict__ enc_len,
+                                                              const float* __restrict__ x, int64_t ldx,
+                                                              float* __restrict__ out, int64_t* __restrict__ dec_len,
+                                                              uint8_t* __restrict__ dec_mask, int M, int L, int max_len,
+                                                              int dur_cols) {
+    length_regulate_body<NT, kSplit, false>(align, dur_f, dur_i, enc_len, x, ldx, out, dec_len, dec_mask, M, L, max_len, dur_cols,
+                                            LrQkv{});
+}
+
+// two workgroups per CU (the second argument is waves per SIMD): 256 registers a lane, 68 KB of LDS
+__global__ __launch_bounds__(256, 2) void length_regulate_qkv_kernel(const float* __restrict__ align, const float* __restrict__ dur_f,
+                                                                     const int64_t* __restrict__ dur_i,
+                                                                     const int64_t* __restrict__ enc_len,
+                                                                     const float* __restrict__ x, int64_t ldx,
+                                                                     float* __restrict__ out, int64_t* __restrict__ dec_len,
+                                                                     uint8_t* __restrict__ dec_mask, int M, int L, int max_len,
+                                                                     int dur_cols, LrQkv q) {
+    length_regulate_body<3, 1, true>(align, dur_f, dur_i, enc_len, x, ldx, out, dec_len, dec_mask, M, L, max_len, dur_cols, q);
 }
 
 }  // namespace
@@ -420,6 +619,26 @@ extern "C" int32_t ispk_embed_tokens_f32(const int64_t* text, const float* table
     const int rows = B * L;
     hipLaunchKernelGGL(embed_tokens_kernel, dim3((rows + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), text,
                        table, ld_table, vocab, text_len, emb, mask, rows, L, D);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_embed_tokens_qkv(const int64_t* text, const float* table, int64_t ld_table, int32_t vocab,
+                                         const int64_t* text_len, float* emb, uint8_t* mask, const uint16_t* qkv_table,
+                                         int64_t ld_qkv_table, uint16_t* qkv, int32_t B, int32_t L, int32_t D, int32_t N,
+                                         ispk_stream_t stream) {
+    ISPK_REQUIRE(text && table && emb && qkv_table && qkv, ISPK_E_NULL, "embed_tokens_qkv: null pointer");
+    ISPK_REQUIRE(B >= 0 && L >= 1 && D >= 4 && N >= 8 && vocab >= 1, ISPK_E_SHAPE,
+                 "embed_tokens_qkv: bad shape B=%d L=%d D=%d N=%d V=%d", B, L, D, N, vocab);
+    ISPK_REQUIRE((int64_t)B * L <= INT32_MAX, ISPK_E_SHAPE, "embed_tokens_qkv: B * L = %lld rows exceed int32",
+                 (long long)B * L);
+    ISPK_REQUIRE(D % 4 == 0 && ld_table % 4 == 0 && ld_table >= D && ispk_aligned(table, 16) && ispk_aligned(emb, 16),
+                 ISPK_E_ALIGN, "embed_tokens_qkv: D / ld_table must be multiples of 4 and table / emb 16-byte aligned");
+    ISPK_REQUIRE(N % 8 == 0 && ld_qkv_table % 8 == 0 && ld_qkv_table >= N && ispk_aligned(qkv_table, 16) && ispk_aligned(qkv, 16),
+                 ISPK_E_ALIGN, "embed_tokens_qkv: N / ld_qkv_table must be multiples of 8 and qkv_table / qkv 16-byte aligned");
+    if (B == 0) return 0;
+    const int rows = B * L;
+    hipLaunchKernelGGL(embed_tokens_qkv_kernel, dim3((rows + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), text,
+                       table, ld_table, vocab, text_len, emb, mask, qkv_table, ld_qkv_table, qkv, rows, L, D, N);
     return ispk_launch_status();
 }
 
@@ -492,7 +711,7 @@ extern "C" int32_t ispk_time_embedding_f32(const float* t, int32_t n, const floa
 static int32_t length_regulate_launch(const float* alignment, const float* dur_f32, const int64_t* dur_i64, const int64_t* enc_len,
                                       const float* x, int64_t ldx, float* out, int64_t* dec_len, uint8_t* dec_mask, int32_t B,
                                       int32_t M, int32_t L, int32_t D, int32_t max_len, int32_t dur_cols, ispk_stream_t stream,
-                                      int split) {
+                                      int split, const LrQkv* qkv = nullptr) {
     ISPK_REQUIRE(x && out && dec_len, ISPK_E_NULL, "length_regulate: null pointer");
     ISPK_REQUIRE((dur_f32 != nullptr) != (dur_i64 != nullptr), ISPK_E_NULL,
                  "length_regulate: exactly one of dur_f32 / dur_i64 must be given");
@@ -514,6 +733,17 @@ static int32_t length_regulate_launch(const float* alignment, const float* dur_f
         hipLaunchKernelGGL((length_regulate_kernel<NT_, SP_>), grid, dim3(256), lds, s, alignment, dur_f32, dur_i64, enc_len, x, \
                            ldx, out, dec_len, dec_mask, M, L, max_len, dur_cols);                                      \
     } while (0)
+    if (qkv) {
+        ISPK_REQUIRE(qkv->gamma && qkv->beta && qkv->w && qkv->qkv, ISPK_E_NULL, "length_regulate_qkv: null pointer");
+        ISPK_REQUIRE(D == 384 && split == 1, ISPK_E_UNSUPPORTED, "length_regulate_qkv: dim %d (built for 384, bf16 terms)", D);
+        ISPK_REQUIRE(qkv->ld >= kLrQkvN && qkv->ld % 8 == 0 && ispk_aligned(qkv->qkv, 16) && ispk_aligned(qkv->w, 16), ISPK_E_ALIGN,
+                     "length_regulate_qkv: ld_qkv must be a multiple of 8 and >= 512, qkv / Wqkv_chunks 16-byte aligned");
+        const size_t lds_q = lds > kLrQkvLds ? lds : kLrQkvLds;
+        ISPK_RESERVE_LDS((&length_regulate_qkv_kernel), lds_q, "length_regulate_qkv");
+        hipLaunchKernelGGL(length_regulate_qkv_kernel, grid, dim3(256), lds_q, s, alignment, dur_f32, dur_i64, enc_len, x, ldx, out,
+                           dec_len, dec_mask, M, L, max_len, dur_cols, *qkv);
+        return ispk_launch_status();
+    }
     if (D == 384) { if (split == 2) ISPK_LR(3, 2); else if (split) ISPK_LR(3, 1); else ISPK_LR(3, 0); }
     else { if (split == 2) ISPK_LR(2, 2); else if (split) ISPK_LR(2, 1); else ISPK_LR(2, 0); }
 #undef ISPK_LR
@@ -534,6 +764,17 @@ extern "C" int32_t ispk_length_regulate_split_bf16(const float* alignment, const
                                                    int32_t D, int32_t max_len, int32_t dur_cols, ispk_stream_t stream) {
     return length_regulate_launch(alignment, dur_f32, dur_i64, enc_len, x, ldx, out, dec_len, dec_mask, B, M, L, D, max_len, dur_cols,
                                   stream, 1);
+}
+
+extern "C" int32_t ispk_length_regulate_qkv_bf16(const float* alignment, const float* dur_f32, const int64_t* dur_i64,
+                                                 const int64_t* enc_len, const float* x, int64_t ldx, float* out,
+                                                 int64_t* dec_len, uint8_t* dec_mask, const float* norm_gamma,
+                                                 const float* norm_beta, float norm_eps, const uint16_t* Wqkv_chunks, uint16_t* qkv,
+                                                 int64_t ld_qkv, int32_t B, int32_t M, int32_t L, int32_t D, int32_t max_len,
+                                                 int32_t dur_cols, ispk_stream_t stream) {
+    const LrQkv q{norm_gamma, norm_beta, norm_eps, Wqkv_chunks, qkv, ld_qkv};
+    return length_regulate_launch(alignment, dur_f32, dur_i64, enc_len, x, ldx, out, dec_len, dec_mask, B, M, L, D, max_len, dur_cols,
+                                  stream, 1, &q);
 }
 
 extern "C" int32_t ispk_length_regulate_split_f16(const float* alignment, const float* dur_f32, const int64_t* dur_i64,

@@ -117,6 +117,13 @@ class SegmentedForward:
                            "flow_time": flow_time.clone() if flow_time is not None else torch.rand(b, device=dev)}
         self.model, self.side = model, torch.cuda.Stream(device=dev, priority=side_priority)
         frames = mel.shape[2]
+        # One eager pass over all three pieces first: every staged weight image exists and is current before the FIRST capture.
+        # A later piece's warm-up that re-staged a stale image (say the decoder's, after a weight changed) would otherwise
+        # invalidate the pieces already captured (`GraphedCall.replay` compares the process-wide count).
+        st = model.forward_front(s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"], s["energy"])
+        model.forward_side(st, s["text_len"], s["mel_len"], s["pitch"], s["energy"], s["flow_noise"], s["flow_time"])
+        model.forward_back(st, s["text_len"], s["mel_len"], frames)
+        torch.cuda.synchronize()
         self.g_front = GraphedCall(lambda: model.forward_front(s["text"], s["text_len"], s["mel"], s["mel_len"], s["pitch"],
                                                                s["energy"]), warmup)
         st = self.g_front.out

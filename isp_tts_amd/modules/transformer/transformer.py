@@ -233,8 +233,10 @@ class Transformer(nn.Module, Constructor):
                 context_mask: Optional[Tensor] = None, attention_mask: Optional[Tensor] = None,
                 adaptive_condition: Optional[Tensor] = None, return_intermediates: bool = False, *,
                 key_len: Optional[Tensor] = None, projected: Optional[Tensor] = None,
-                out_dtype: torch.dtype = torch.float32, final_norm: bool = True):
-        """`final_norm=False`: `.out` is the last layer's raw output - for a caller whose next kernel applies `self.norm` itself
+                out_dtype: torch.dtype = torch.float32, final_norm: bool = True, handed: Handed = Handed()):
+        """`handed`: what the caller's kernels already produced of layer 0's attention_norm over `x` (`Handed(Hand.QKV, rows)`: its
+        q/kv rows) - layer 0 then plans as any layer does behind a producing one.
+        `final_norm=False`: `.out` is the last layer's raw output - for a caller whose next kernel applies `self.norm` itself
         (the flow predictor's head, `runtime.flow_head`).
         `projected` lets a caller that already holds project_emb(x) (e.g. the Euler loop, which re-projects only the
         3 flow channels per step) skip the projection.  `out_dtype=torch.bfloat16` makes the final LayerNorm emit bf16
@@ -249,7 +251,6 @@ class Transformer(nn.Module, Constructor):
             key_len = mask.sum(dim=1)
         intermediates = []
         ada = self._ada_all(adaptive_condition) if (self.adaptive_norm and adaptive_condition is not None) else None
-        handed = Handed()
         for li, layer in enumerate(self.layers):
             res = layer(out, mask=mask, context=context, context_mask=context_mask, attention_mask=attention_mask,
                         adaptive_condition=adaptive_condition, key_len=key_len, ada=None if ada is None else ada[li],

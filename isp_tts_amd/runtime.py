@@ -85,12 +85,15 @@ SIGNATURES = {
     "ispk_hard_regulate_bwd_f32": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_hard_average_f32": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P],
     "ispk_embed_tokens_f32": [_P, _P, _I64, _I32, _P, _P, _P, _I32, _I32, _I32, _P],
+    "ispk_embed_tokens_qkv": [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_add_speaker_f32": [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_add_speaker_out_f32": [_P, _P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_speaker_grad_f32": [_P, _P, _I32, _P, _P, _I64, _P, _I64, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_time_embedding_f32": [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P],
     "ispk_length_regulate_f32": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_length_regulate_split_bf16": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+    "ispk_length_regulate_qkv_bf16": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _F32, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32,
+                                      _I32, _P],
     "ispk_length_regulate_split_f16": [_P, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P],
     "ispk_pad_rows_f32": [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _P],
     "ispk_masked_instnorm_f32": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F32, _P],
@@ -1045,6 +1048,27 @@ def embed_tokens(text: Tensor, table: Tensor, text_len: Optional[Tensor] = None,
     return emb, mask
 
 
+def embed_tokens_qkv(text: Tensor, table: Tensor, qkv_table: Tensor, text_len: Optional[Tensor] = None, want_mask: bool = True):
+    """ispk_embed_tokens_qkv: `embed_tokens` plus the first layer's q/kv rows gathered with the same ids from `qkv_table` (bf16
+    [vocab, N]: attention_norm + [to_q; to_kv] of every table row) -> (emb fp32 [B,L,D], mask bool [B,L] | None, qkv bf16 [B,L,N])."""
+    _dev(text, table, qkv_table, text_len)
+    assert text.dtype == torch.int64 and text.ndim == 2 and table.dtype == torch.float32 and table.stride(1) == 1
+    B, L = text.shape
+    V, D = table.shape
+    N = qkv_table.shape[1]
+    assert qkv_table.dtype == torch.bfloat16 and qkv_table.shape == (V, N) and qkv_table.stride(1) == 1
+    text = text.contiguous()
+    emb = torch.empty((B, L, D), dtype=torch.float32, device=text.device)
+    qkv = torch.empty((B, L, N), dtype=torch.bfloat16, device=text.device)
+    mask = torch.empty((B, L), dtype=torch.bool, device=text.device) if want_mask else None
+    if text_len is not None:
+        text_len = text_len.to(torch.int64).contiguous()
+    _launch("embed_tokens_qkv_kernel", 0.0, B * L * (8.0 * D + 4.0 * N), lib().ispk_embed_tokens_qkv, text.data_ptr(),
+            table.data_ptr(), table.stride(0), V, _ptr(text_len), emb.data_ptr(), _ptr(mask), qkv_table.data_ptr(),
+            qkv_table.stride(0), qkv.data_ptr(), B, L, D, N, _stream())
+    return emb, mask, qkv
+
+
 def _speaker_ids(speaker: Tensor, B: int):
     """-> (contiguous int64 ids, id_stride): `speaker` int64 [B, 1] (the collator's field, collator.py:59) = one id per utterance,
     or one element = one id for the whole batch (the notebook's `torch.tensor([id])`)."""
@@ -1123,11 +1147,14 @@ def time_embedding(t: Tensor, inv_freq: Tensor, freq_scale: Tensor, w0: Tensor, 
 
 
 def length_regulate(x: Tensor, durations: Tensor, alignment: Optional[Tensor], frames: int, max_len: int = -1,
-                    enc_len: Optional[Tensor] = None, want_mask: bool = True, split_bf16=False):
+                    enc_len: Optional[Tensor] = None, want_mask: bool = True, split_bf16=False, next_qkv: Optional[tuple] = None):
     """ispk_length_regulate_f32 -> (out fp32 [B, frames, D], dec_len int64 [B], dec_mask bool [B, frames] | None).
     alignment fp32 [B, frames, L] (forward), or None: the soft path generated from the fp32 `durations` (infer).
     `split_bf16`: True = ispk_length_regulate_split_bf16 (the bf16 compute path: three bf16 MFMAs per product, ~2^-16
-    relative); "f16" = ispk_length_regulate_split_f16 (the split-fp16 parity path: fp16 terms, fp32-grade)."""
+    relative); "f16" = ispk_length_regulate_split_f16 (the split-fp16 parity path: fp16 terms, fp32-grade).
+    `next_qkv` = (gamma, beta, eps, Wqkv_chunks) (bf16 path, D = 384; Wqkv_chunks from `chunk_k16`, [24, 512, 16]):
+    ispk_length_regulate_qkv_bf16 - the same three outputs, bit for bit, and a fourth: the consuming layer's attention_norm +
+    q/kv projection of every output row, bf16 [B, frames, 512], from the kernel's epilogue."""
     _dev(x, durations, alignment, enc_len)
     assert x.dtype == torch.float32 and x.ndim == 3
     if x.stride(2) != 1 or x.stride(0) != x.shape[1] * x.stride(1):
@@ -1151,6 +1178,18 @@ def length_regulate(x: Tensor, durations: Tensor, alignment: Optional[Tensor], f
     dec_len = torch.empty((B,), dtype=torch.int64, device=x.device)
     mask = torch.empty((B, frames), dtype=torch.bool, device=x.device) if want_mask else None
     nb = 4.0 * B * (frames * D + L * D + (frames * L if alignment is not None else 0))
+    if next_qkv is not None:
+        gamma, beta, eps, wqc = next_qkv
+        _dev(gamma, beta, wqc)
+        assert split_bf16 is True and D == 384, "the q/kv epilogue is built for the bf16 path at dim 384"
+        assert wqc.dtype == torch.bfloat16 and wqc.shape == (D // 16, 512, 16) and wqc.is_contiguous()
+        assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == D
+        qkv = torch.empty((B, frames, 512), dtype=torch.bfloat16, device=x.device)
+        _launch("length_regulate_qkv_kernel", 2.0 * B * frames * (L + 512) * D, nb + 2.0 * (B * frames * 512 + 512 * D),
+                lib().ispk_length_regulate_qkv_bf16, _ptr(alignment), _ptr(dur_f), _ptr(dur_i), _ptr(enc_len), x.data_ptr(),
+                x.stride(1), out.data_ptr(), dec_len.data_ptr(), _ptr(mask), gamma.data_ptr(), beta.data_ptr(), float(eps),
+                wqc.data_ptr(), qkv.data_ptr(), 512, B, frames, L, D, max_len, dur_cols, _stream())
+        return out, dec_len, mask, qkv
     fn = (lib().ispk_length_regulate_split_f16 if split_bf16 == "f16" else
           lib().ispk_length_regulate_split_bf16 if split_bf16 else lib().ispk_length_regulate_f32)
     _launch("length_regulate_kernel<split_f16>" if split_bf16 == "f16" else "length_regulate_kernel<bf16x3>" if split_bf16
