@@ -1,0 +1,394 @@
+"""Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
+the Vocos and HiFi-GAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip)."""
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from .. import runtime as _rt
+
+__all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_features", "resampled_samples", "resample",
+           "STATS_MAX_FRAMES", "feature_stats", "CONDITION_TABLE_DOUBLES", "CONDITION_MAX_SAMPLES", "CONDITION_RATES",
+           "audio_measure_workspace_floats", "_mono_batch", "_out_like", "audio_measure", "audio_apply", "pcm16", "VOCODER_HOP",
+           "VOCODER_TABLE_FLOATS", "_lengths_ptr", "vocoder_unfold", "dwconv7_ln", "istft_head", "HIFIGAN_TILE_ROWS",
+           "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows", "hifigan_conv", "_hifigan_bn",
+           "hifigan_upsample", "hifigan_post"]
+
+
+FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
+FEATURE_TABLE_HEAD = 5120  # tables[0, 5120): W_2048^m as (re, im), then the Hann window; the filterbank weights follow
+
+
+def feature_frames(samples: int) -> int:
+    """Frames of an utterance of `samples` samples: (S + 768 - 1024) // 256 + 1, 0 below 256 samples (where torch.stft raises)."""
+    return (samples - FEATURE_HOP) // FEATURE_HOP + 1 if samples >= FEATURE_HOP else 0
+
+
+def audio_features(audio: Tensor, audio_len: Tensor, tables: Tensor, fb_index: Optional[Tensor], mel: Optional[Tensor],
+                   mel_len: Optional[Tensor], pitch: Optional[Tensor], energy: Optional[Tensor], tau_min: int = 1,
+                   tau_max: int = 512, sample_rate: float = 0.0, threshold: float = 0.0, pitch_mean: float = 0.0,
+                   pitch_std: float = 1.0) -> None:
+    """ispk_audio_features_f32, one launch, no host read: fills the given outputs (each may be None) of the fp32 waveforms
+    audio [B, S] (unit stride on S, any row stride) with int64 lengths audio_len [B].  mel fp32 [B, n_mels, M], pitch / energy
+    fp32 [B, M], mel_len int64 [B], all contiguous; tables fp32 and fb_index int32 as include/ispk.h lays them out
+    (data.AcousticFeatures builds them).  The kernel reads no filterbank weight past tables.numel(), whatever fb_index
+    (device data, not read here) says."""
+    _rt._dev(audio, audio_len, tables, fb_index, mel, mel_len, pitch, energy)
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and audio.stride(1) == 1, "audio: fp32 [B, S], unit stride on S"
+    assert audio_len.dtype == torch.int64 and audio_len.ndim == 1 and audio_len.is_contiguous()
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= FEATURE_TABLE_HEAD
+    B, S = audio.shape
+    if audio_len.shape[0] != B:
+        raise ValueError(f"{audio_len.shape[0]} lengths for {B} waveforms")
+    M, n_mels = None, 0
+    for name, t, dt, nd in (("mel", mel, torch.float32, 3), ("pitch", pitch, torch.float32, 2),
+                            ("energy", energy, torch.float32, 2), ("mel_len", mel_len, torch.int64, 1)):
+        if t is None:
+            continue
+        if t.dtype != dt or t.ndim != nd or not t.is_contiguous() or t.shape[0] != B:
+            raise ValueError(f"{name}: need a contiguous {dt} tensor of {nd} dims and {B} rows, got {t.dtype} {tuple(t.shape)}")
+        if nd > 1:
+            if M is not None and t.shape[-1] != M:
+                raise ValueError(f"{name}: {t.shape[-1]} frames, another output has {M}")
+            M = t.shape[-1]
+    if mel is not None:
+        n_mels = mel.shape[1]
+        assert fb_index is not None and fb_index.dtype == torch.int32 and fb_index.numel() == 2 * n_mels + 1
+    if B == 0:
+        return
+    _rt._launch("features_kernel", 0.0, 4.0 * audio.numel() + 4.0 * (n_mels + 2) * B * (M or 0), _rt.lib().ispk_audio_features_f32,
+                audio.data_ptr(), audio.stride(0), audio_len.data_ptr(), tables.data_ptr(), tables.numel(), _rt._ptr(fb_index), n_mels, _rt._ptr(mel),
+                _rt._ptr(mel_len), _rt._ptr(pitch), _rt._ptr(energy), B, S, M if M is not None else _rt.feature_frames(S), tau_min, tau_max,
+                sample_rate, threshold, pitch_mean, pitch_std, _rt._stream())
+
+
+def resampled_samples(samples: int, orig: int, dest: int) -> int:
+    """ceil(dest * samples / orig): the output length of `samples` input samples at the reduced rates orig -> dest."""
+    return (samples * dest + orig - 1) // orig
+
+
+def resample(audio: Tensor, audio_len: Tensor, taps: Tensor, first: Tensor, orig: int, dest: int, width: int,
+             out: Optional[Tensor] = None, out_len: Optional[Tensor] = None):
+    """ispk_resample_f32, one launch, no host read: fp32 audio [B, S] or [B, C, S] (unit stride on S) with int64 lengths
+    [B] -> (fp32 [B, ceil(dest S / orig)], int64 [B]); several channels are averaged.  `orig`, `dest` are the reduced rates,
+    taps fp32 [dest, T] / first int32 [dest] the compact polyphase table (data.Resampler builds it)."""
+    _rt._dev(audio, audio_len, taps, first, out, out_len)
+    if audio.dtype != torch.float32 or audio.ndim not in (2, 3) or audio.stride(-1) != 1:
+        raise ValueError(f"audio: fp32 [B, S] or [B, C, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} "
+                         f"strides {tuple(audio.stride())}")
+    B, S = audio.shape[0], audio.shape[-1]
+    C = audio.shape[1] if audio.ndim == 3 else 1
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    assert taps.dtype == torch.float32 and taps.ndim == 2 and taps.is_contiguous() and taps.shape[0] == dest
+    assert first.dtype == torch.int32 and first.shape == (dest,) and first.is_contiguous()
+    S_out = _rt.resampled_samples(S, orig, dest)
+    if out is None:
+        out = torch.empty((B, S_out), dtype=torch.float32, device=audio.device)
+    if out_len is None:
+        out_len = torch.empty((B,), dtype=torch.int64, device=audio.device)
+    if out.dtype != torch.float32 or out.shape != (B, S_out) or out.stride(1) != 1:
+        raise ValueError(f"out: fp32 [{B}, {S_out}] with unit stride on the samples, got {out.dtype} {tuple(out.shape)}")
+    if out_len.dtype != torch.int64 or out_len.shape != (B,) or not out_len.is_contiguous():
+        raise ValueError(f"out_len: contiguous int64 [{B}], got {out_len.dtype} {tuple(out_len.shape)}")
+    if B == 0:
+        return out, out_len
+    _rt._launch("resample_kernel", 2.0 * taps.shape[1] * B * S_out, 4.0 * (B * C * S + B * S_out), _rt.lib().ispk_resample_f32,
+                audio.data_ptr(), audio.stride(0), audio.stride(1) if audio.ndim == 3 else 0, audio_len.data_ptr(),
+                taps.data_ptr(), taps.numel(), first.data_ptr(), out.data_ptr(), out.stride(0), out_len.data_ptr(), B, C, S, S_out,
+                orig, dest, width, taps.shape[1], _rt._stream())
+    return out, out_len
+
+
+STATS_MAX_FRAMES = 4096    # ispk_feature_stats_f64 sorts an utterance in LDS
+
+
+def feature_stats(pitch: Optional[Tensor], energy: Optional[Tensor], mel_len: Optional[Tensor], partial: Optional[Tensor],
+                  state: Tensor, reset: bool = False) -> None:
+    """ispk_feature_stats_f64, a launch pair, no host read: the per-utterance outlier-filtered (count, mean, M2, min, max) of
+    pitch / energy fp32 [B, M] into partial float64 [B, 2, 5], folded in utterance order into state float64 [2, 5].  With
+    pitch None (and reset) it only writes the empty state."""
+    _rt._dev(pitch, energy, mel_len, partial, state)
+    assert state.dtype == torch.float64 and state.shape == (2, 5) and state.is_contiguous()
+    if pitch is None:
+        _rt._launch("stats_fold_kernel", 0.0, 80.0, _rt.lib().ispk_feature_stats_f64, None, 0, None, 0, None, None, state.data_ptr(),
+                    0, 0, int(reset), _rt._stream())
+        return
+    for name, t in (("pitch", pitch), ("energy", energy)):
+        if t.dtype != torch.float32 or t.ndim != 2 or t.stride(1) != 1 or t.shape != pitch.shape:
+            raise ValueError(f"{name}: fp32 {tuple(pitch.shape)} with unit stride on the frames, got {t.dtype} {tuple(t.shape)} "
+                             f"strides {tuple(t.stride())}")
+    B, M = pitch.shape
+    if mel_len.dtype != torch.int64 or mel_len.shape != (B,) or not mel_len.is_contiguous():
+        raise ValueError(f"mel_len: contiguous int64 [{B}], got {mel_len.dtype} {tuple(mel_len.shape)}")
+    assert partial.dtype == torch.float64 and partial.shape == (B, 2, 5) and partial.is_contiguous()
+    _rt._launch("feature_stats_kernel", 0.0, 8.0 * B * M, _rt.lib().ispk_feature_stats_f64, pitch.data_ptr(), pitch.stride(0),
+                energy.data_ptr(), energy.stride(0), mel_len.data_ptr(), partial.data_ptr(), state.data_ptr(), B, M, int(reset),
+                _rt._stream())
+
+
+CONDITION_TABLE_DOUBLES = 152     # 7 coefficients, one unused, nine 4 x 4 powers of the state transition (include/ispk.h)
+CONDITION_MAX_SAMPLES = 1 << 24
+CONDITION_RATES = (8000, 768000)
+
+
+def audio_measure_workspace_floats(B: int, S: int, sample_rate: int) -> int:
+    """ispk_audio_measure_f64: per item the 256-sample square sums, the final states of every 32-sample chunk (4 doubles) and
+    8,192-sample segment, 12 step partials and a peak per segment, and the step sums - in doubles, two floats each."""
+    W, NH, NS = max(1, -(-S // 8192)), max(1, -(-S // 256)), S // (sample_rate // 10) + 1
+    return 2 * B * (NH + W * (256 * 4 + 4 + 12 + 1) + NS)
+
+
+def _mono_batch(audio: Tensor, audio_len: Optional[Tensor]) -> tuple[int, int]:
+    if audio.dtype != torch.float32 or audio.ndim != 2 or audio.stride(1) != 1:
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    if S > CONDITION_MAX_SAMPLES or B > 65535:
+        raise ValueError(f"audio: at most 65535 utterances of {CONDITION_MAX_SAMPLES} samples, got {tuple(audio.shape)}")
+    if audio_len is not None and (audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous()):
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    return B, S
+
+
+def _out_like(name: str, t: Tensor, dtype, shape) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or (t.ndim and t.stride(-1) != 1) or (t.ndim == 1 and not t.is_contiguous()):
+        raise ValueError(f"{name}: {dtype} {tuple(shape)} with unit stride on the last axis, got {t.dtype} {tuple(t.shape)}")
+
+
+def audio_measure(audio: Tensor, audio_len: Tensor, table: Tensor, sample_rate: int, trim_mode: int, trim_threshold: float,
+                  pad_frames: int, gain_mode: int, target_lufs: float, peak_limit: float, bounds: Optional[Tensor] = None,
+                  loudness: Optional[Tensor] = None, peak: Optional[Tensor] = None, gain: Optional[Tensor] = None):
+    """ispk_audio_measure_f64, three launches, no host read: fp32 audio [B, S] (unit stride on S) with int64 lengths [B] ->
+    (bounds int64 [B, 2], loudness float64 [B], peak fp32 [B], gain fp32 [B]).  `table` float64 [152] as include/ispk.h lays
+    it out (data.AudioConditioner builds it)."""
+    _rt._dev(audio, audio_len, table, bounds, loudness, peak, gain)
+    B, S = _mono_batch(audio, audio_len)
+    assert table.dtype == torch.float64 and table.shape == (CONDITION_TABLE_DOUBLES,) and table.is_contiguous()
+    dev = audio.device
+    bounds = torch.empty((B, 2), dtype=torch.int64, device=dev) if bounds is None else bounds
+    loudness = torch.empty((B,), dtype=torch.float64, device=dev) if loudness is None else loudness
+    peak = torch.empty((B,), dtype=torch.float32, device=dev) if peak is None else peak
+    gain = torch.empty((B,), dtype=torch.float32, device=dev) if gain is None else gain
+    _out_like("bounds", bounds, torch.int64, (B, 2))
+    if not bounds.is_contiguous():
+        raise ValueError("bounds: contiguous int64 [B, 2]")
+    _out_like("loudness", loudness, torch.float64, (B,))
+    _out_like("peak", peak, torch.float32, (B,))
+    _out_like("gain", gain, torch.float32, (B,))
+    if B == 0:
+        return bounds, loudness, peak, gain
+    ws = _rt.workspace(dev, _rt.audio_measure_workspace_floats(B, S, sample_rate))
+    _rt._launch("audio_measure_kernels", 56.0 * B * S, 4.0 * 2 * B * S + 2.0 * 8 * B * S / 8, _rt.lib().ispk_audio_measure_f64, audio.data_ptr(),
+                audio.stride(0), audio_len.data_ptr(), table.data_ptr(), table.numel(), bounds.data_ptr(), loudness.data_ptr(),
+                peak.data_ptr(), gain.data_ptr(), ws.data_ptr(), ws.numel(), B, S, int(sample_rate), int(trim_mode),
+                float(trim_threshold), int(pad_frames), int(gain_mode), float(target_lufs), float(peak_limit), _rt._stream())
+    return bounds, loudness, peak, gain
+
+
+def audio_apply(audio: Tensor, bounds: Tensor, gain: Optional[Tensor], out: Optional[Tensor] = None,
+                out_len: Optional[Tensor] = None):
+    """ispk_audio_apply_f32, one launch: out[b, i] = gain[b] * audio[b, start_b + i] below end_b - start_b, then zeros; the
+    lengths go to out_len.  `out` fp32 [B, S_out] may not overlap `audio`."""
+    _rt._dev(audio, bounds, gain, out, out_len)
+    B, S = _mono_batch(audio, None)
+    dev = audio.device
+    out = torch.empty((B, S), dtype=torch.float32, device=dev) if out is None else out
+    out_len = torch.empty((B,), dtype=torch.int64, device=dev) if out_len is None else out_len
+    if out.ndim != 2:
+        raise ValueError(f"out: fp32 [{B}, S_out], got {tuple(out.shape)}")
+    _out_like("out", out, torch.float32, (B, out.shape[1]))
+    _out_like("out_len", out_len, torch.int64, (B,))
+    _out_like("bounds", bounds, torch.int64, (B, 2))
+    if gain is not None:
+        _out_like("gain", gain, torch.float32, (B,))
+    if B == 0:
+        return out, out_len
+    _rt._launch("cond_apply_kernel", 1.0 * B * S, 4.0 * (B * S + out.numel()), _rt.lib().ispk_audio_apply_f32, audio.data_ptr(), audio.stride(0),
+                bounds.data_ptr(), _rt._ptr(gain), out.data_ptr(), out.stride(0), out_len.data_ptr(), B, S, out.shape[1], _rt._stream())
+    return out, out_len
+
+
+def pcm16(audio: Tensor, audio_len: Tensor, dither: bool = False, seed: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """ispk_pcm16, one launch: fp32 [B, S] -> int16 [B, S], clamp(rint(32768 x + d)), zero past audio_len."""
+    _rt._dev(audio, audio_len, out)
+    B, S = _mono_batch(audio, audio_len)
+    out = torch.empty((B, S), dtype=torch.int16, device=audio.device) if out is None else out
+    _out_like("out", out, torch.int16, (B, S))
+    if B == 0 or S == 0:
+        return out
+    _rt._launch("pcm16_kernel", 0.0, 6.0 * B * S, _rt.lib().ispk_pcm16, audio.data_ptr(), audio.stride(0), audio_len.data_ptr(),
+                out.data_ptr(), out.stride(0), B, S, int(bool(dither)), int(seed) & 0xFFFFFFFFFFFFFFFF, _rt._stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------- Vocos vocoder
+VOCODER_HOP = 256             # ispk_istft_head_f32: n_fft 1024, hop 256, padding "same"
+VOCODER_TABLE_FLOATS = 2 * 2048 + 1024
+
+
+def _lengths_ptr(mel_len: Optional[Tensor], B: int) -> Optional[int]:
+    if mel_len is None:
+        return None
+    if mel_len.dtype != torch.int64 or mel_len.shape != (B,) or not mel_len.is_contiguous():
+        raise ValueError(f"mel_len: contiguous int64 [{B}], got {mel_len.dtype} {tuple(mel_len.shape)}")
+    return mel_len.data_ptr()
+
+
+def vocoder_unfold(mel: Tensor, mel_len: Optional[Tensor], rows: Tensor, row_mask: Optional[Tensor] = None) -> Tensor:
+    """ispk_vocoder_unfold: mel fp32 / fp16 [B, C, T] (any strides) -> the embedding convolution's GEMM rows [B*T, K] (fp32 or
+    bf16, K % 8 == 0, K >= 7 C; column j*C + c = tap j of channel c), zero past mel_len; row_mask bool [B*T] (t < mel_len)."""
+    _rt._dev(mel, mel_len, rows, row_mask)
+    assert mel.ndim == 3 and mel.dtype in (torch.float32, torch.float16)
+    B, C, T = mel.shape
+    assert rows.ndim == 2 and rows.shape[0] == B * T and rows.stride(1) == 1 and rows.dtype in (torch.float32, torch.bfloat16)
+    assert row_mask is None or (row_mask.dtype == torch.bool and row_mask.numel() == B * T and row_mask.is_contiguous())
+    K = rows.shape[1]
+    ml = _lengths_ptr(mel_len, B)
+    if B * T == 0:
+        return rows
+    _rt._launch(f"vocoder_unfold_kernel<{'f16' if mel.dtype == torch.float16 else 'f32'},"
+                f"{'bf16' if rows.dtype == torch.bfloat16 else 'f32'}>", 0.0,
+                float(mel.numel() * mel.element_size() + rows.numel() * rows.element_size() + B * T), _rt.lib().ispk_vocoder_unfold,
+                mel.data_ptr(), int(mel.dtype == torch.float16), mel.stride(0), mel.stride(1), mel.stride(2), ml, rows.data_ptr(),
+                int(rows.dtype == torch.bfloat16), rows.stride(0), _rt._ptr(row_mask), B, C, T, K, _rt._stream())
+    return rows
+
+
+def dwconv7_ln(x: Tensor, T: int, weight: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, mel_len: Optional[Tensor],
+               eps: float = 1e-6, out_dtype: torch.dtype = torch.float32, out: Optional[Tensor] = None) -> Tensor:
+    """ispk_dwconv7_ln_f32: x fp32 [B*T, D] rows (unit column stride) -> LayerNorm(depthwise conv7(x)) fp32 / bf16 [B*T, D],
+    each utterance's frames [0, mel_len) convolved alone, rows past mel_len zero.  weight fp32 [D, 7] contiguous."""
+    _rt._dev(x, weight, bias, gamma, beta, mel_len, out)
+    assert x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1
+    R, D = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.shape == (D, 7) and weight.is_contiguous()
+    if out is None:
+        out = torch.empty((R, D), dtype=out_dtype, device=x.device)
+    assert out.shape == (R, D) and out.stride(1) == 1 and out.dtype in (torch.float32, torch.bfloat16)
+    ml = _lengths_ptr(mel_len, B)
+    if R == 0:
+        return out
+    _rt._launch(f"dwconv7_ln_kernel<{D // 64},{'bf16' if out.dtype == torch.bfloat16 else 'f32'}>", 18.0 * R * D,
+                float(R * D * (4 + out.element_size())), _rt.lib().ispk_dwconv7_ln_f32, x.data_ptr(), x.stride(0), weight.data_ptr(),
+                bias.data_ptr(), gamma.data_ptr(), beta.data_ptr(), eps, ml, out.data_ptr(), int(out.dtype == torch.bfloat16),
+                out.stride(0), B, T, D, _rt._stream())
+    return out
+
+
+def istft_head(h: Tensor, T: int, mel_len: Optional[Tensor], tables: Tensor, audio: Tensor,
+               audio_len: Optional[Tensor] = None) -> Tensor:
+    """ispk_istft_head_f32: the head Linear's fp32 rows h [B*T, >= 1026] (log-magnitudes in columns 0-512, phases in 513-1025)
+    -> audio fp32 [B, S] (unit stride on S, S >= 256 T; zero from 256 mel_len on) and audio_len int64 [B] = 256 mel_len."""
+    _rt._dev(h, mel_len, tables, audio, audio_len)
+    assert h.dtype == torch.float32 and h.ndim == 2 and h.stride(1) == 1
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and audio.stride(1) == 1
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= VOCODER_TABLE_FLOATS
+    B, S = audio.shape
+    assert h.shape[0] == B * T
+    assert audio_len is None or (audio_len.dtype == torch.int64 and audio_len.shape == (B,) and audio_len.is_contiguous())
+    ml = _lengths_ptr(mel_len, B)
+    if B == 0:
+        return audio
+    R = B * T
+    _rt._launch("istft_head_kernel", R * 1.25 * (5.0 * 512 * 9 + 20.0 * 513), float(R * 1026 * 4 + B * S * 4),
+                _rt.lib().ispk_istft_head_f32, h.data_ptr(), h.stride(0), ml, tables.data_ptr(), tables.numel(), audio.data_ptr(),
+                audio.stride(0), _rt._ptr(audio_len), B, T, S, _rt._stream())
+    return audio
+
+
+# ------------------------------------------------------------------------------------------------- HiFi-GAN vocoder
+HIFIGAN_TILE_ROWS = 128       # ispk_hifigan_tile_rows(): time positions per workgroup of the convolution kernels
+HIFIGAN_MAX_CHANNELS = 512    # C_in, C_out: multiples of 32 up to this
+HIFIGAN_MAX_KERNEL, HIFIGAN_MAX_DILATION = 11, 12
+
+
+def _hifigan_rows(x: Tensor, name: str) -> None:
+    assert x.dtype == torch.float32 and x.ndim == 2 and x.stride(1) == 1, f"{name}: fp32 rows [R, C] with unit column stride"
+
+
+def hifigan_conv(x: Tensor, T: int, weight: Tensor, bias: Optional[Tensor], k: int, dilation: int = 1, slope: float = 1.0,
+                 resid: Optional[Tensor] = None, out: Optional[Tensor] = None, accumulate: bool = False, scale: float = 1.0,
+                 lengths: Optional[Tensor] = None, len_mul: int = 1) -> Tensor:
+    """ispk_hifigan_conv_{f32,bf16} by weight.dtype: x fp32 [B*T, C_in] rows -> out fp32 [B*T, C_out] =
+    [out +] scale * (bias + Conv1d(k, dilation, "same")(leaky_relu(x, slope)) [+ resid]); weight image [k, C_out, C_in].
+    lengths int64 [B]: utterance b has lengths[b] * len_mul valid rows, the rest read and are written as zeros."""
+    _rt._dev(x, weight, bias, resid, out, lengths)
+    _hifigan_rows(x, "x")
+    R, C_in = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.ndim == 3 and weight.is_contiguous() and weight.shape[0] == k and weight.shape[2] == C_in
+    assert weight.dtype in (torch.float32, torch.bfloat16)
+    C_out = weight.shape[1]
+    assert not accumulate or out is not None, "accumulate needs out="
+    if out is None:
+        out = torch.empty((R, C_out), dtype=torch.float32, device=x.device)
+    _hifigan_rows(out, "out")
+    assert out.shape == (R, C_out)
+    if resid is not None:
+        _hifigan_rows(resid, "resid")
+        assert resid.shape == (R, C_out)
+    ln = _lengths_ptr(lengths, B)
+    if R == 0:
+        return out
+    bf = weight.dtype == torch.bfloat16
+    _rt._launch(f"hifigan_conv_kernel<{'bf16' if bf else 'f32'},{_hifigan_bn(C_out)}>", 2.0 * R * C_out * C_in * k,
+                float(R * 4 * (C_in + C_out * (1 + (resid is not None) + bool(accumulate))) + weight.numel() * weight.element_size()),
+                _rt.lib().ispk_hifigan_conv_bf16 if bf else _rt.lib().ispk_hifigan_conv_f32, x.data_ptr(), x.stride(0), weight.data_ptr(),
+                _rt._ptr(bias), _rt._ptr(resid), _rt._ld(resid), out.data_ptr(), out.stride(0), ln, len_mul, B,
+                T, C_in, C_out, k, dilation, slope, scale, int(accumulate), _rt._stream())
+    return out
+
+
+def _hifigan_bn(C_out: int) -> int:
+    return 128 if C_out % 128 == 0 else 64 if C_out % 64 == 0 else 32
+
+
+def hifigan_upsample(x: Tensor, T: int, weight: Tensor, bias: Optional[Tensor], k: int, stride: int, slope: float = 0.1,
+                     out: Optional[Tensor] = None, lengths: Optional[Tensor] = None, len_mul: int = 1) -> Tensor:
+    """ispk_hifigan_upsample_{f32,bf16} by weight.dtype: x fp32 [B*T, C_in] rows -> out fp32 [B*T*stride, C_out] = bias +
+    ConvTranspose1d(k, stride, padding (k - stride) / 2)(leaky_relu(x, slope)); weight image [k, C_out, C_in] (the module's
+    [C_in, C_out, k] permuted).  lengths[b] * len_mul valid INPUT rows; output rows past stride times that are zeros."""
+    _rt._dev(x, weight, bias, out, lengths)
+    _hifigan_rows(x, "x")
+    R, C_in = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R and weight.ndim == 3 and weight.is_contiguous() and weight.shape[0] == k and weight.shape[2] == C_in
+    assert weight.dtype in (torch.float32, torch.bfloat16)
+    C_out = weight.shape[1]
+    if out is None:
+        out = torch.empty((R * stride, C_out), dtype=torch.float32, device=x.device)
+    _hifigan_rows(out, "out")
+    assert out.shape == (R * stride, C_out)
+    ln = _lengths_ptr(lengths, B)
+    if R == 0:
+        return out
+    bf = weight.dtype == torch.bfloat16
+    _rt._launch(f"hifigan_conv_kernel<{'bf16' if bf else 'f32'},{_hifigan_bn(C_out)}>(T)", 2.0 * R * C_out * C_in * k,
+                float(R * 4 * (C_in + C_out * stride) + weight.numel() * weight.element_size()),
+                _rt.lib().ispk_hifigan_upsample_bf16 if bf else _rt.lib().ispk_hifigan_upsample_f32, x.data_ptr(), x.stride(0),
+                weight.data_ptr(), _rt._ptr(bias), out.data_ptr(), out.stride(0), ln, len_mul, B, T, C_in, C_out, k, stride, slope,
+                _rt._stream())
+    return out
+
+
+def hifigan_post(x: Tensor, T: int, weight: Tensor, bias: Tensor, audio: Tensor, audio_len: Optional[Tensor] = None,
+                 lengths: Optional[Tensor] = None, len_mul: int = 1, slope: float = 0.01) -> Tensor:
+    """ispk_hifigan_post_f32: x fp32 [B*T, C] rows -> audio fp32 [B, S >= T] = tanh(bias + conv7(leaky_relu(x, slope))), zeros
+    from lengths[b] * len_mul on; audio_len int64 [B] = lengths[b] * len_mul.  weight fp32 [7, C] contiguous, bias fp32 [1]."""
+    _rt._dev(x, weight, bias, audio, audio_len, lengths)
+    _hifigan_rows(x, "x")
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and (audio.stride(1) == 1 or audio.shape[1] <= 1)
+    B, S = audio.shape
+    C = x.shape[1]
+    assert x.shape[0] == B * T and weight.shape == (7, C) and weight.is_contiguous() and weight.dtype == torch.float32
+    assert bias.dtype == torch.float32 and bias.numel() == 1
+    assert audio_len is None or (audio_len.dtype == torch.int64 and audio_len.shape == (B,) and audio_len.is_contiguous())
+    ln = _lengths_ptr(lengths, B)
+    if B == 0:
+        return audio
+    _rt._launch("hifigan_post_kernel", 14.0 * B * T * C, float(B * T * C * 4 + B * S * 4), _rt.lib().ispk_hifigan_post_f32,
+                _rt._ptr(x) if x.numel() else None, x.stride(0), weight.data_ptr(), bias.data_ptr(), ln, len_mul, audio.data_ptr(),
+                max(audio.stride(0), S), _rt._ptr(audio_len), B, T, S, C, slope, _rt._stream())
+    return audio

@@ -29,13 +29,13 @@ class Spy(TorchDispatchMode):
         if not name.startswith(SKIP):
             where = "?"
             for fr in reversed(traceback.extract_stack()):
-                if "isp_tts_amd" in fr.filename and "runtime.py" not in fr.filename:
+                if "isp_tts_amd" in fr.filename and "runtime.py" not in fr.filename and "/bindings/" not in fr.filename:
                     where = f"{fr.filename.split('isp_tts_amd/')[-1]}:{fr.lineno}"
                     break
             else:
                 for fr in reversed(traceback.extract_stack()):
-                    if "runtime.py" in fr.filename:
-                        where = f"runtime.py:{fr.lineno}"
+                    if "runtime.py" in fr.filename or "/bindings/" in fr.filename:
+                        where = f"{fr.filename.split('isp_tts_amd/')[-1]}:{fr.lineno}"
                         break
             log[(where, name)] += 1
         return func(*args, **(kwargs or {}))
