@@ -593,7 +593,7 @@ int32_t ispk_hard_average_f32(const float* pitch, const float* energy, const int
  *                              row padding_idx gets zeros.
  * ispk_grad_sqnorm_f32         out[0] = sum g[i]^2 over a flat gradient arena (what clip_grad_norm_ needs,
  *                              experiments/optimizers.py:236-237); partial = 2048 floats (8 KB, 8-byte aligned) of scratch;
- *                              fp64 accumulation in a fixed order.
+ *                              fp64 accumulation in a fixed order.  n = 0 (g may then be NULL) gives 0.
  * ispk_adamw_f32               one torch.optim.AdamW step (optimizers.py:72-74; amsgrad off) over flat arenas p, g, m, v of n
  *                              floats.  Elements [0, n_decay) are the weight-decay group of optimizers.py:15-20 (tensors
  *                              with >= 2 non-unit dimensions): they get `weight_decay` and, when grad_sqnorm (device, the

@@ -906,7 +906,7 @@ extern "C" int32_t ispk_colsum_f32(const float* x, int64_t ldx, int64_t rows, in
 }
 
 extern "C" int32_t ispk_grad_sqnorm_f32(const float* g, int64_t n, float* partial, float* out, ispk_stream_t stream) {
-    ISPK_REQUIRE(g && partial && out, -1, "ispk_grad_sqnorm_f32: null pointer");
+    ISPK_REQUIRE((g || n == 0) && partial && out, -1, "ispk_grad_sqnorm_f32: null pointer");      // (an empty arena may be NULL: sum 0)
     ISPK_REQUIRE(n >= 0 && ispk_aligned(g, 16) && ispk_aligned(partial, 8), -2,
                  "ispk_grad_sqnorm_f32: n < 0, g not 16-byte aligned or partial not 8-byte aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
