@@ -1041,7 +1041,9 @@ int32_t ispk_conv_weight_flip_f32(const float* w, float* wf, int32_t O, int32_t 
  *                             with k - stride even (stride <= 64, k <= 128); output length stride * input length.
  * ispk_hifigan_post_f32       audio[b][s] = tanh(bias[0] + sum_j sum_c w[j][c] leaky_relu(x[b*T + s + j - 3][c], slope)), the
  *                             7-tap C -> 1 output convolution in fp32, for s < len[b] * len_mul, 0 from there to S (S >= T,
- *                             ld_audio >= S); audio_len[b] = len[b] * len_mul (may be NULL).  w fp32 [7][C]. */
+ *                             ld_audio >= S); audio_len[b] = len[b] * len_mul (may be NULL).  w fp32 [7][C].
+ * ispk_hifigan_post_clamp_f32 the same with clamp(v, -1, 1) in place of tanh(v) (BigVGAN's use_tanh_at_final = false): the
+ *                             same kernel under a template parameter, ispk_hifigan_post_f32's results are unchanged. */
 int32_t ispk_hifigan_tile_rows(void);
 int32_t ispk_hifigan_conv_f32(const float* x, int64_t ldx, const float* w, const float* bias, const float* resid, int64_t ldr,
                               float* out, int64_t ldo, const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C_in,
@@ -1060,6 +1062,31 @@ int32_t ispk_hifigan_upsample_bf16(const float* x, int64_t ldx, const uint16_t* 
 int32_t ispk_hifigan_post_f32(const float* x, int64_t ldx, const float* w, const float* bias, const int64_t* len,
                               int32_t len_mul, float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B, int32_t T,
                               int32_t S, int32_t C, float slope, ispk_stream_t stream);
+int32_t ispk_hifigan_post_clamp_f32(const float* x, int64_t ldx, const float* w, const float* bias, const int64_t* len,
+                                    int32_t len_mul, float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B, int32_t T,
+                                    int32_t S, int32_t C, float slope, ispk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * BigVGAN generator (csrc/bigvgan.hip; isp_tts_amd/bigvgan.py): the anti-aliased periodic activation.  The convolutions
+ * are the HiFi-GAN entries above with slope 1.  Rows, lengths and limits are exactly those of the HiFi-GAN entries: x and out
+ * are fp32 rows [B * T][C] with unit column stride, 16-byte aligned, ldx and ldo multiples of 4; the valid length of
+ * utterance b is len[b] * len_mul rows (len NULL: T; a value outside [0, T] counts as 0); rows at or past it are never read
+ * and are written as zeros; C is a multiple of 32 up to 512 (anything else: E_UNSUP).  A workgroup never spans two
+ * utterances and the result of utterance b depends neither on its neighbours nor on B.
+ *
+ * ispk_snake_aa_tile_rows     rows of one utterance per workgroup (512): the tests' tile edges.
+ * ispk_snake_aa_f32           per utterance of n valid rows, channel c, row t < n, with fu = taps[0 .. 12), fd = taps[12 .. 24):
+ *                               u[s] = 2 sum_{i = ceil((s+4)/2)}^{floor((s+15)/2)} fu[s + 15 - 2 i] x[clamp(i - 5, 0, n-1)][c]
+ *                               a[s] = u[s] + inv_b[c] sin(al[c] u[s])^2                                   s in [0, 2n)
+ *                               out[t][c] = sum_{j=0}^{11} fd[j] a[clamp(2 t + j - 5, 0, 2n-1)]
+ *                             = replicate-pad 5, 2x transposed-convolution upsampling with fu, snake, replicate-pad (5, 6),
+ *                             stride-2 convolution with fd.  al, inv_b fp32 [C] (16-byte aligned) and taps fp32 [24] are
+ *                             device memory.  Out of place only: out == x is E_SHAPE (the rows around t are read).  fp32
+ *                             throughout, accurate sinf (the argument is not range-limited). */
+int32_t ispk_snake_aa_tile_rows(void);
+int32_t ispk_snake_aa_f32(const float* x, int64_t ldx, const float* al, const float* inv_b, const float* taps, float* out,
+                          int64_t ldo, const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C,
+                          ispk_stream_t stream);
 
 #ifdef __cplusplus
 }

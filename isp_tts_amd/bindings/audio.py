@@ -1,5 +1,5 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
-the Vocos and HiFi-GAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip)."""
+the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip)."""
 from typing import Optional
 
 import torch
@@ -12,7 +12,7 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "audio_measure_workspace_floats", "_mono_batch", "_out_like", "audio_measure", "audio_apply", "pcm16", "VOCODER_HOP",
            "VOCODER_TABLE_FLOATS", "_lengths_ptr", "vocoder_unfold", "dwconv7_ln", "istft_head", "HIFIGAN_TILE_ROWS",
            "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows", "hifigan_conv", "_hifigan_bn",
-           "hifigan_upsample", "hifigan_post"]
+           "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -374,9 +374,10 @@ def hifigan_upsample(x: Tensor, T: int, weight: Tensor, bias: Optional[Tensor], 
 
 
 def hifigan_post(x: Tensor, T: int, weight: Tensor, bias: Tensor, audio: Tensor, audio_len: Optional[Tensor] = None,
-                 lengths: Optional[Tensor] = None, len_mul: int = 1, slope: float = 0.01) -> Tensor:
+                 lengths: Optional[Tensor] = None, len_mul: int = 1, slope: float = 0.01, final_clamp: bool = False) -> Tensor:
     """ispk_hifigan_post_f32: x fp32 [B*T, C] rows -> audio fp32 [B, S >= T] = tanh(bias + conv7(leaky_relu(x, slope))), zeros
-    from lengths[b] * len_mul on; audio_len int64 [B] = lengths[b] * len_mul.  weight fp32 [7, C] contiguous, bias fp32 [1]."""
+    from lengths[b] * len_mul on; audio_len int64 [B] = lengths[b] * len_mul.  weight fp32 [7, C] contiguous, bias fp32 [1].
+    final_clamp: ispk_hifigan_post_clamp_f32, clamp(., -1, 1) in place of tanh."""
     _rt._dev(x, weight, bias, audio, audio_len, lengths)
     _hifigan_rows(x, "x")
     assert audio.dtype == torch.float32 and audio.ndim == 2 and (audio.stride(1) == 1 or audio.shape[1] <= 1)
@@ -388,7 +389,38 @@ def hifigan_post(x: Tensor, T: int, weight: Tensor, bias: Tensor, audio: Tensor,
     ln = _lengths_ptr(lengths, B)
     if B == 0:
         return audio
-    _rt._launch("hifigan_post_kernel", 14.0 * B * T * C, float(B * T * C * 4 + B * S * 4), _rt.lib().ispk_hifigan_post_f32,
+    _rt._launch("hifigan_post_kernel<clamp>" if final_clamp else "hifigan_post_kernel", 14.0 * B * T * C,
+                float(B * T * C * 4 + B * S * 4), _rt.lib().ispk_hifigan_post_clamp_f32 if final_clamp else _rt.lib().ispk_hifigan_post_f32,
                 _rt._ptr(x) if x.numel() else None, x.stride(0), weight.data_ptr(), bias.data_ptr(), ln, len_mul, audio.data_ptr(),
                 max(audio.stride(0), S), _rt._ptr(audio_len), B, T, S, C, slope, _rt._stream())
     return audio
+
+
+# --------------------------------------------------------------------------------------------------- BigVGAN vocoder
+SNAKE_AA_TILE_ROWS = 512      # ispk_snake_aa_tile_rows(): rows of one utterance per workgroup of the activation kernel
+
+
+def snake_aa(x: Tensor, T: int, al: Tensor, inv_b: Tensor, taps: Tensor, out: Optional[Tensor] = None,
+             lengths: Optional[Tensor] = None, len_mul: int = 1) -> Tensor:
+    """ispk_snake_aa_f32: x fp32 [B*T, C] rows -> out fp32 [B*T, C], the anti-aliased snake activation per utterance and
+    channel: 2x upsampling with taps[:12] (replicate padding), u + inv_b sin(al u)^2, 2x low-pass downsampling with taps[12:].
+    al, inv_b fp32 [C], taps fp32 [24], all contiguous.  lengths[b] * len_mul valid rows, the rest is never read and written
+    as zeros.  Out of place only."""
+    _rt._dev(x, al, inv_b, taps, out, lengths)
+    _hifigan_rows(x, "x")
+    R, C = x.shape
+    B = R // T if T > 0 else 0
+    assert B * T == R
+    for name, t, n in (("al", al, C), ("inv_b", inv_b, C), ("taps", taps, 24)):
+        assert t.dtype == torch.float32 and t.shape == (n,) and t.is_contiguous(), f"{name}: contiguous fp32 [{n}]"
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    _hifigan_rows(out, "out")
+    assert out.shape == (R, C)
+    ln = _lengths_ptr(lengths, B)
+    if R == 0:
+        return out
+    _rt._launch("snake_aa_kernel", 56.0 * R * C, 8.0 * R * C, _rt.lib().ispk_snake_aa_f32, x.data_ptr(), x.stride(0),
+                al.data_ptr(), inv_b.data_ptr(), taps.data_ptr(), out.data_ptr(), out.stride(0), ln, len_mul, B, T, C,
+                _rt._stream())
+    return out

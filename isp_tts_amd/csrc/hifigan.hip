@@ -20,9 +20,10 @@
 //       Epilogue: + bias, + residual row, then out = scale * v or out = fma(scale, v, out) (the MRF mean accumulated by the
 //       last unit of each ResBlock); output rows at or past the utterance's length are written as zeros.  A tile that lies
 //       wholly past the length writes its zeros and leaves.
-//   hifigan_post_kernel                grid (ceil(S / 256), B), 256 threads, one output sample each: leaky-ReLU -> 7-tap
+//   hifigan_post_kernel<CLAMP>         grid (ceil(S / 256), B), 256 threads, one output sample each: leaky-ReLU -> 7-tap
 //       C -> 1 convolution (fp32 fma chain in channel-chunk, tap, channel order over an LDS window of 262 rows x 32 channels,
-//       row pitch 33) -> + bias -> tanhf; zeros at and past the utterance's length; audio_len.
+//       row pitch 33) -> + bias -> tanhf, or clamp to [-1, 1] (BigVGAN's use_tanh_at_final = false); zeros at and past the
+//       utterance's length; audio_len.
 // Sums run in a fixed order that depends only on the position inside the utterance: a ragged batch gives each utterance the
 // bits it gets alone, and repeated calls and graph replays give the same bits.  A device length outside [0, T] counts as 0.
 //
@@ -301,6 +302,7 @@ constexpr int kPostS = 256;                       // samples per workgroup
 constexpr int kPostWin = kPostS + 6;
 constexpr int kPostPitch = kKC + 1;               // odd row pitch: consecutive samples read distinct banks
 
+template <bool CLAMP>
 __global__ __launch_bounds__(kPostS) void hifigan_post_kernel(const float* __restrict__ x, int64_t ldx,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
                                                               const int64_t* __restrict__ len, int len_mul,
@@ -339,7 +341,35 @@ __global__ __launch_bounds__(kPostS) void hifigan_post_kernel(const float* __res
             for (int c = 0; c < kKC; ++c) acc = fmaf(xr[c], wj[c], acc);
         }
     }
-    if (s < S) arow[s] = s < n ? tanhf(acc + bias[0]) : 0.f;
+    if (s < S) {
+        const float v = acc + bias[0];
+        if (CLAMP) arow[s] = s < n ? (v < -1.f ? -1.f : v > 1.f ? 1.f : v) : 0.f;
+        else arow[s] = s < n ? tanhf(v) : 0.f;
+    }
+}
+
+int32_t post_entry(bool clamp, const char* what, const float* x, int64_t ldx, const float* w, const float* bias,
+                   const int64_t* len, int32_t len_mul, float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B, int32_t T,
+                   int32_t S, int32_t C, float slope, ispk_stream_t stream) {
+    if (B == 0) return 0;
+    ISPK_REQUIRE(audio && ((x && w && bias) || T == 0), -1, "%s: null pointer", what);
+    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 0 && S >= T && ld_audio >= S && len_mul >= 1, -2,
+                 "%s: bad shape B=%d T=%d S=%d ld_audio=%lld len_mul=%d (S >= T, ld_audio >= S)", what, B, T, S,
+                 (long long)ld_audio, len_mul);
+    if (S == 0 && !audio_len) return 0;
+    ISPK_REQUIRE(T == 0 || (C >= 32 && C <= kMaxC && C % 32 == 0), -4,
+                 "%s: unsupported channel count C=%d (multiples of 32 up to %d are built)", what, C, kMaxC);
+    ISPK_REQUIRE(T == 0 || (ldx >= C && ldx % 4 == 0 && ispk_aligned(x, 16)), -3,
+                 "%s: x needs 16-byte aligned rows of at least C floats (ldx=%lld)", what, (long long)ldx);
+    const int nblk = S > 0 ? (S + kPostS - 1) / kPostS : 1;
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (clamp)
+        hipLaunchKernelGGL(hifigan_post_kernel<true>, dim3(nblk, B), dim3(kPostS), 0, s, x, ldx, w, bias, len, len_mul, audio,
+                           ld_audio, audio_len, T, S, C, slope);
+    else
+        hipLaunchKernelGGL(hifigan_post_kernel<false>, dim3(nblk, B), dim3(kPostS), 0, s, x, ldx, w, bias, len, len_mul, audio,
+                           ld_audio, audio_len, T, S, C, slope);
+    return ispk_launch_status();
 }
 
 }  // namespace
@@ -381,18 +411,14 @@ extern "C" int32_t ispk_hifigan_upsample_bf16(const float* x, int64_t ldx, const
 extern "C" int32_t ispk_hifigan_post_f32(const float* x, int64_t ldx, const float* w, const float* bias, const int64_t* len,
                                          int32_t len_mul, float* audio, int64_t ld_audio, int64_t* audio_len, int32_t B,
                                          int32_t T, int32_t S, int32_t C, float slope, ispk_stream_t stream) {
-    if (B == 0) return 0;
-    ISPK_REQUIRE(audio && ((x && w && bias) || T == 0), -1, "ispk_hifigan_post_f32: null pointer");
-    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 0 && S >= T && ld_audio >= S && len_mul >= 1, -2,
-                 "ispk_hifigan_post_f32: bad shape B=%d T=%d S=%d ld_audio=%lld len_mul=%d (S >= T, ld_audio >= S)", B, T, S,
-                 (long long)ld_audio, len_mul);
-    if (S == 0 && !audio_len) return 0;
-    ISPK_REQUIRE(T == 0 || (C >= 32 && C <= kMaxC && C % 32 == 0), -4,
-                 "ispk_hifigan_post_f32: unsupported channel count C=%d (multiples of 32 up to %d are built)", C, kMaxC);
-    ISPK_REQUIRE(T == 0 || (ldx >= C && ldx % 4 == 0 && ispk_aligned(x, 16)), -3,
-                 "ispk_hifigan_post_f32: x needs 16-byte aligned rows of at least C floats (ldx=%lld)", (long long)ldx);
-    const int nblk = S > 0 ? (S + kPostS - 1) / kPostS : 1;
-    hipLaunchKernelGGL(hifigan_post_kernel, dim3(nblk, B), dim3(kPostS), 0, reinterpret_cast<hipStream_t>(stream), x, ldx, w,
-                       bias, len, len_mul, audio, ld_audio, audio_len, T, S, C, slope);
-    return ispk_launch_status();
+    return post_entry(false, "ispk_hifigan_post_f32", x, ldx, w, bias, len, len_mul, audio, ld_audio, audio_len, B, T, S, C, slope,
+                      stream);
+}
+
+extern "C" int32_t ispk_hifigan_post_clamp_f32(const float* x, int64_t ldx, const float* w, const float* bias,
+                                               const int64_t* len, int32_t len_mul, float* audio, int64_t ld_audio,
+                                               int64_t* audio_len, int32_t B, int32_t T, int32_t S, int32_t C, float slope,
+                                               ispk_stream_t stream) {
+    return post_entry(true, "ispk_hifigan_post_clamp_f32", x, ldx, w, bias, len, len_mul, audio, ld_audio, audio_len, B, T, S, C,
+                      slope, stream);
 }

@@ -384,6 +384,90 @@ def make_hifigan_state_dict(dims=HIFIGAN_DIMS["v1"], seed: int = SEED, weight_no
     return sd
 
 
+# ----------------------------------------------------------------------------------------------------- BigVGAN generators
+# name -> generator configuration (bigvgan.BigVGan's constructor arguments).  "base": the published 22.05 kHz base model.
+# "odd" / "odd2": HIFIGAN_DIMS["odd"]'s geometry with AMPBlock "1" / "2", plain snake without logscale, no bias in conv_post
+# and a clamp in place of the final tanh.
+BIGVGAN_DIMS = {
+    "base": dict(n_mels=80, upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
+                 resblock="1", resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3,
+                 activation="snakebeta", snake_logscale=True, use_bias_at_final=True, use_tanh_at_final=True),
+    "odd": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
+                resblock="1", resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3, 5),) * 2,
+                activation="snake", snake_logscale=False, use_bias_at_final=False, use_tanh_at_final=False),
+    "odd2": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
+                 resblock="2", resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3), (2, 5)),
+                 activation="snake", snake_logscale=False, use_bias_at_final=False, use_tanh_at_final=False),
+}
+
+
+def bigvgan_filter() -> torch.Tensor:
+    """The anti-aliasing low-pass of BigVGAN's activations, float64 [12]: 0.5 kaiser_window(12, beta) sinc(0.5 (j - 5.5)) with
+    beta = 0.1102 (A - 8.7), A = 2.285 * 5 * pi * 1.2 + 7.95, normalised to sum 1."""
+    beta = 0.1102 * (2.285 * 5 * math.pi * 1.2 + 7.95 - 8.7)
+    j = torch.arange(12, dtype=torch.float64)
+    f = 0.5 * torch.kaiser_window(12, periodic=False, beta=beta, dtype=torch.float64) * torch.sinc(0.5 * (j - 5.5))
+    return f / f.sum()
+
+
+def make_bigvgan_state_dict(dims=BIGVGAN_DIMS["base"], seed: int = SEED, weight_norm: Optional[str] = None) -> dict[str, torch.Tensor]:
+    """Synthetic BigVGAN generator weights in the official state-dict layout (ups.{i}.0, resblocks.{n}.activations.{l}.act.alpha
+    / beta, the filter buffers, activation_post), from keyed streams.  Convolution weights are N(0, s^2 / (C_in k)) with s = 1
+    (first convolution of a type "1" unit), 0.5 (second), 0.7 (type "2"), up-convolutions N(0, 1 / (C_in k / stride)), biases
+    N(0, 0.05^2): the activations' inputs have an rms around 1.  al is log-uniform in [1, 6] and B in [1, 4] (stored as their
+    logarithms with snake_logscale), so al |u| lies around 1 to 10.  conv_post is scaled for output peaks of 0.2 - 0.9 under a
+    final tanh, and so that a few per cent of the samples clamp on either side without one.  The filters are bigvgan_filter().
+    weight_norm as in make_hifigan_state_dict."""
+    if weight_norm not in (None, "g_v", "parametrized"):
+        raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
+    C0, rates, up_k = dims["upsample_initial_channel"], dims["upsample_rates"], dims["upsample_kernel_sizes"]
+    beta, logscale = dims.get("activation", "snakebeta") == "snakebeta", dims.get("snake_logscale", True)
+    sd: dict[str, torch.Tensor] = {}
+    filt = bigvgan_filter().float().reshape(1, 1, 12)
+
+    def put(name: str, shape, fan: float, s: float, bias: bool = True):
+        w = _normal(f"bvg/{name}.w", shape, s / math.sqrt(fan), seed=seed)
+        if weight_norm is None:
+            sd[name + ".weight"] = w
+        else:
+            gk, vk = (".weight_g", ".weight_v") if weight_norm == "g_v" else (".parametrizations.weight.original0",
+                                                                             ".parametrizations.weight.original1")
+            ones = [1] * (len(shape) - 1)
+            f = torch.from_numpy(_rng(f"bvg/{name}.f", seed).uniform(0.5, 2.0, size=(shape[0], *ones)).astype(np.float32))
+            sd[name + gk] = w.double().flatten(1).norm(dim=1).reshape(shape[0], *ones).float()
+            sd[name + vk] = w * f
+        if bias:
+            sd[name + ".bias"] = _normal(f"bvg/{name}.b", (shape[0] if not name.startswith("ups.") else shape[1],), 0.05, seed=seed)
+
+    def act(name: str, C: int):
+        for key, lo, hi in (("alpha", 1.0, 6.0),) + ((("beta", 1.0, 4.0),) if beta else ()):
+            v = np.exp(_rng(f"bvg/{name}.{key}", seed).uniform(math.log(lo), math.log(hi), size=(C,)))
+            sd[f"{name}.act.{key}"] = torch.from_numpy((np.log(v) if logscale else v).astype(np.float32))
+        sd[name + ".upsample.filter"] = filt.clone()
+        sd[name + ".downsample.lowpass.filter"] = filt.clone()
+
+    put("conv_pre", (C0, dims["n_mels"], 7), dims["n_mels"] * 7, 0.25)
+    J = len(dims["resblock_kernel_sizes"])
+    for i, (u, k) in enumerate(zip(rates, up_k)):
+        C = C0 >> i
+        put(f"ups.{i}.0", (C, C // 2, k), C * k / u, 1.0)
+        for j, (r, D) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
+            n = i * J + j
+            for m in range(len(D)):
+                if str(dims["resblock"]) == "1":
+                    put(f"resblocks.{n}.convs1.{m}", (C // 2, C // 2, r), C // 2 * r, 1.0)
+                    put(f"resblocks.{n}.convs2.{m}", (C // 2, C // 2, r), C // 2 * r, 0.5)
+                    act(f"resblocks.{n}.activations.{2 * m}", C // 2)
+                    act(f"resblocks.{n}.activations.{2 * m + 1}", C // 2)
+                else:
+                    put(f"resblocks.{n}.convs.{m}", (C // 2, C // 2, r), C // 2 * r, 0.7)
+                    act(f"resblocks.{n}.activations.{m}", C // 2)
+    act("activation_post", C0 >> len(rates))
+    tanh = dims.get("use_tanh_at_final", True)
+    put("conv_post", (1, C0 >> len(rates), 7), (C0 >> len(rates)) * 7, 0.1 if tanh else 0.6, bias=dims.get("use_bias_at_final", True))
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------------- dataset statistics
 # Batches for data.DatasetStats (tests/golden/dataset_stats.npz holds the reference's results on them): pitch in Hz as the
 # extractor delivers it with mean 0 / std 1 - the discrete values fl(fl(1 / tau) * 22050), tau in 27 .. 524, 0 on unvoiced
