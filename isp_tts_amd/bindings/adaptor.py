@@ -108,6 +108,8 @@ def soft_average(attn_soft: Tensor, pitch: Tensor, energy: Tensor, duration: Opt
     B, M, L = attn_soft.shape
     feats = torch.empty((B, L, 3), dtype=torch.float32, device=attn_soft.device)
     dur = _rt._i64(duration)
+    if B == 0:      # nothing to compute; the C entries would refuse the NULL data_ptr() torch gives an empty tensor
+        return feats
     _rt._launch("soft_average_kernel", 0.0, 4.0 * B * M * L, _rt.lib().ispk_soft_average_f32, attn_soft.contiguous().data_ptr(),
                 pitch.contiguous().data_ptr(), energy.contiguous().data_ptr(), _rt._ptr(dur),
                 _rt._i64(text_len).data_ptr(), feats.data_ptr(), B, M, L, _rt._stream())
@@ -120,6 +122,8 @@ def flow_mix(x0: Tensor, x1: Tensor, t: Tensor, sigma: float):
     B, L, C = x1.shape
     x0c, x1c, tc = x0.float().contiguous(), x1.float().contiguous(), t.float().contiguous()
     xt, flow = torch.empty_like(x1c), torch.empty_like(x1c)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return xt, flow
     _rt._launch("flow_mix_kernel", 0.0, 16.0 * B * L * C, _rt.lib().ispk_flow_mix_f32, x0c.data_ptr(), x1c.data_ptr(), tc.data_ptr(),
                 float(sigma), xt.data_ptr(), flow.data_ptr(), B, L, C, _rt._stream())
     return xt, flow
@@ -135,6 +139,8 @@ def flow_finish(pred_raw: Tensor, flow: Tensor, x0: Tensor, mask: Tensor):
     dur = torch.empty((B, L), dtype=torch.float32, device=pr.device)
     ratio = torch.empty((B,), dtype=torch.float32, device=pr.device)
     loss = torch.empty((), dtype=torch.float32, device=pr.device)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average); the mean over no utterance is NaN, as torch's is
+        return pred, dur, ratio, loss.fill_(float("nan"))
     _rt._launch("flow_finish_kernel", 0.0, 20.0 * B * L * C, _rt.lib().ispk_flow_finish_f32, pr.data_ptr(), fl.data_ptr(),
                 x0c.data_ptr(), mk.data_ptr(), pred.data_ptr(), dur.data_ptr(), ratio.data_ptr(), loss.data_ptr(), B, L, C,
                 _rt._stream())
@@ -155,6 +161,8 @@ def flow_head(y: Tensor, norm_weight: Tensor, norm_bias: Tensor, norm_eps: float
     dur = torch.empty((B, L), dtype=torch.float32, device=y.device)
     ratio = torch.empty((B,), dtype=torch.float32, device=y.device)
     loss = torch.empty((), dtype=torch.float32, device=y.device)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average); the mean over no utterance is NaN, as torch's is
+        return pred, dur, ratio, loss.fill_(float("nan"))
     ws = torch.empty((2 * B * ((L + 15) // 16),), dtype=torch.float32, device=y.device)
     _rt._launch("flow_head_kernels", 0.0, 4.0 * B * L * D, _rt.lib().ispk_flow_head_f32, y.data_ptr(), y.stride(1), norm_weight.data_ptr(),
                 norm_bias.data_ptr(), float(norm_eps), weight.data_ptr(), bias.data_ptr(), fl.data_ptr(), x0c.data_ptr(), mk.data_ptr(),
@@ -171,6 +179,8 @@ def flow_euler(x_t: Tensor, velocity: Tensor, dt: float, mask: Optional[Tensor] 
     if mask is not None:
         mask = mask.contiguous()
         assert mask.dtype == torch.bool and mask.shape == (B, L)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return out
     _rt._launch("flow_euler_kernel", 0.0, 12.0 * B * L * C, _rt.lib().ispk_flow_euler_f32, xc.data_ptr(), vc.data_ptr(), float(dt),
                 _rt._ptr(mask), out.data_ptr(), B, L, C, _rt._stream())
     return out
@@ -196,6 +206,8 @@ def infer_features(pred: Tensor, duration_target: Optional[Tensor], pitch_target
     et = None if energy_target is None else energy_target.float().reshape(B, L).contiguous()
     duration = torch.empty((B, L), dtype=torch.float32, device=pred.device)
     feats = torch.empty((B, L, 2), dtype=torch.float32, device=pred.device)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return duration, feats
     _rt._launch("infer_features_kernel<round>" if round_duration else "infer_features_kernel", 0.0, 24.0 * B * L,
                 _rt.lib().ispk_infer_features_round_f32 if round_duration else _rt.lib().ispk_infer_features_f32, pc.data_ptr(), _rt._ptr(dur_f),
                 _rt._ptr(dur_i), _rt._ptr(pt), _rt._ptr(et), float(duration_factor), float(pitch_factor), float(pitch_delta), float(energy_factor),
@@ -214,6 +226,8 @@ def embed_tokens(text: Tensor, table: Tensor, text_len: Optional[Tensor] = None,
     emb = torch.empty((B, L, D), dtype=torch.float32, device=text.device)
     mask = torch.empty((B, L), dtype=torch.bool, device=text.device) if want_mask else None
     text_len = _rt._i64(text_len)
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return emb, mask
     _rt._launch("embed_tokens_kernel", 0.0, 8.0 * B * L * D, _rt.lib().ispk_embed_tokens_f32, text.data_ptr(), table.data_ptr(),
                 table.stride(0), V, _rt._ptr(text_len), emb.data_ptr(), _rt._ptr(mask), B, L, D, _rt._stream())
     return emb, mask
@@ -310,6 +324,8 @@ def time_embedding(t: Tensor, inv_freq: Tensor, freq_scale: Tensor, w0: Tensor, 
     E, H = w1.shape[0], inv_freq.numel()
     assert w0.shape == (E, 1 + 2 * H) and w1.shape == (E, E) and w0.is_contiguous() and w1.is_contiguous()
     out = torch.empty((*t.shape, E), dtype=torch.float32, device=t.device)
+    if tf.numel() == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return out
     _rt._launch("time_embedding_kernel", 0.0, 0.0, _rt.lib().ispk_time_embedding_f32, tf.data_ptr(), tf.numel(), inv_freq.data_ptr(),
                 freq_scale.data_ptr(), H, w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr(), E, out.data_ptr(),
                 _rt._stream())
@@ -337,7 +353,7 @@ def length_regulate(x: Tensor, durations: Tensor, alignment: Optional[Tensor], f
     dur_cols = L
     if durations.dtype == torch.int64:   # only summed: any [B, cols] with the right row sums (e.g. mel_len as [B, 1])
         assert alignment is not None, "the soft path is generated from fp32 durations"
-        dur_i = durations.reshape(B, -1).contiguous()
+        dur_i = durations.reshape(B, -1 if B else max(durations.shape[-1], 1)).contiguous()      # (-1 is ambiguous with no rows)
         dur_cols = dur_i.shape[1]
     else:
         dur_f = durations.to(torch.float32).contiguous()
@@ -347,6 +363,9 @@ def length_regulate(x: Tensor, durations: Tensor, alignment: Optional[Tensor], f
     dec_len = torch.empty((B,), dtype=torch.int64, device=x.device)
     mask = torch.empty((B, frames), dtype=torch.bool, device=x.device) if want_mask else None
     nb = 4.0 * B * (frames * D + L * D + (frames * L if alignment is not None else 0))
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        qkv = () if next_qkv is None else (torch.empty((B, frames, 512), dtype=torch.bfloat16, device=x.device),)
+        return (out, dec_len, mask, *qkv)
     if next_qkv is not None:
         gamma, beta, eps, wqc = next_qkv
         _rt._dev(gamma, beta, wqc)
