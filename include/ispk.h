@@ -315,6 +315,21 @@ int32_t ispk_alibi_mqa_attn_bf16_tiles(const uint16_t* q, int64_t ldq, const uin
                                        const float* slopes, const int64_t* key_len, uint16_t* out, int64_t ldo, int32_t B,
                                        int32_t N, int32_t H, int32_t q_tiles_per_workgroup, ispk_stream_t stream);
 
+/* One attention block of the bf16 forward at N <= 128 positions per batch item in ONE launch (csrc/attn_block.hip):
+ *   qkv = x [Wq; Wkv]^T (bf16)   ->   attention as ispk_alibi_mqa_attn_bf16   ->   out = resid + mask * (attn Wo^T) (fp32)
+ * bit for bit what ispk_gemm_bf16 (ISPK_EP_OUT_BF16), ispk_alibi_mqa_attn_bf16 and ispk_gemm_bf16 (ISPK_EP_MASK_ACC, resid)
+ * give when called in sequence; the attention output itself is not stored.
+ *   x      bf16 [B * N][64 H] at ldx: the layer's normalised rows; or NULL: `qkv` already holds the finished q/kv rows
+ *   qkv    bf16 [B * N][64 H + 128] at ld_qkv = [Q | K | V]: written (x given; every row exactly once) or read (x NULL)
+ *   Wqkv_chunks = ispk_chunk_k16_bf16([Wq; Wkv]): [4 H][64 H + 128][16] (unused when x is NULL);
+ *   Wo_chunks   = ispk_chunk_k16_bf16(Wo): [4 H][64 H][16]
+ *   slopes [H], key_len [B] int64 or NULL as for the attention entries;  mask [B * N] uint8 or NULL (= all rows valid)
+ *   resid, out fp32 [B * N][64 H] at ldr / ldo.   H = 4 or 6 (dim 256 / 384). */
+int32_t ispk_attn_block_short_bf16(const uint16_t* x, int64_t ldx, const uint16_t* Wqkv_chunks, uint16_t* qkv, int64_t ld_qkv,
+                                   const float* slopes, const int64_t* key_len, const uint16_t* Wo_chunks, const float* resid,
+                                   int64_t ldr, const uint8_t* mask, float* out, int64_t ldo, int32_t B, int32_t N, int32_t H,
+                                   ispk_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Aligner front-end (the ConvAttention that produces the MAS input), fp32, channel-last padded layout.
  * Replaces: models/acoustic/modules/alignment.py:69-83 (ConvBlock1D), :159-208 (ConvAttention.forward), :18-37

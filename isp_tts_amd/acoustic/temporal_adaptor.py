@@ -33,6 +33,10 @@ class TransformerTemporalModule(nn.Module, Constructor):
     def __init__(self, input_dim: int = 256, output_dim: int = 256, transformer=None, detach_inputs: bool = False):
         super().__init__()
         self.transformer = Transformer.init(transformer, emb_dim=input_dim)
+        # the one-kernel attention block stays off in this stack: its single layer gains 2.5 us of the 1.9-ms step at 64
+        # utterances and 3.1 us at 8, less than three times the spread of two identical captures (tools/ab_switches.py)
+        for layer in self.transformer.layers:
+            layer.attention.short_block = False
         self.linear_layer = nn.Linear(self.transformer.dim, output_dim, bias=True)
         self.detach_inputs = detach_inputs
         self._cache = StagedWeights()

@@ -8,7 +8,7 @@ from torch import Tensor
 from .. import runtime as _rt
 
 __all__ = ["layernorm", "ffn_pack_w2", "ffn_fused", "ffn_prenorm", "ffn_chunk_w2", "ffn_prenorm2", "chunk_k16", "attn_out_ffn",
-           "ffn_prenorm2_split", "alibi_mqa_attention_raw", "alibi_mqa_attention", "split_f16", "layernorm_split", "_split_label",
+           "ffn_prenorm2_split", "alibi_mqa_attention_raw", "alibi_mqa_attention", "attn_block_short", "split_f16", "layernorm_split", "_split_label",
            "gemm_split", "to_mel_split", "conv5_padded_split", "alibi_mqa_attention_split", "cast_bf16"]
 
 
@@ -287,6 +287,40 @@ def alibi_mqa_attention(qkv: Tensor, heads: int, slopes: Tensor, key_len: Option
     assert W == heads * 64 + 128 and qkv.is_contiguous()
     return _rt.alibi_mqa_attention_raw(qkv, W, qkv[..., heads * 64:], qkv[..., heads * 64 + 64:], W, slopes, key_len, B, N,
                                        heads, q_tiles)
+
+
+def attn_block_short(x: Optional[Tensor], wqkv_c: Optional[Tensor], qkv: Optional[Tensor], heads: int, slopes: Tensor,
+                     key_len: Optional[Tensor], wo_c: Tensor, resid: Tensor, mask: Optional[Tensor]):
+    """ispk_attn_block_short_bf16: one attention block at N <= 128 positions in one launch -> (out fp32 [B, N, D], qkv bf16
+    [B, N, D + 128]), D = heads * 64 in {256, 384}.  Either `x` (bf16 [B, N, D], the normalised rows) with wqkv_c =
+    `chunk_k16([Wq; Wkv])` - the q/kv rows are computed and returned - or `qkv` (finished rows; x and wqkv_c None).
+    wo_c = `chunk_k16(Wo)`; out = resid + mask * (attention @ Wo^T), bit for bit what gemm -> alibi_mqa_attention -> gemm give."""
+    _rt._dev(x, wqkv_c, qkv, slopes, key_len, wo_c, resid, mask)
+    D = heads * 64
+    src = x if x is not None else qkv
+    B, N = src.shape[:2]
+    assert (x is None) != (qkv is None) and src.dim() == 3 and src.dtype == torch.bfloat16 and src.is_contiguous()
+    assert resid.dtype == torch.float32 and resid.shape == (B, N, D) and resid.is_contiguous()
+    assert wo_c.dtype == torch.bfloat16 and wo_c.shape == (D // 16, D, 16) and wo_c.is_contiguous()
+    if x is not None:
+        assert x.shape == (B, N, D) and wqkv_c.dtype == torch.bfloat16 and wqkv_c.shape == (D // 16, D + 128, 16) and wqkv_c.is_contiguous()
+        qkv = torch.empty((B, N, D + 128), dtype=torch.bfloat16, device=x.device)
+    else:
+        assert qkv.shape == (B, N, D + 128)
+    out = torch.empty((B, N, D), dtype=torch.float32, device=src.device)
+    if B == 0:
+        return out, qkv
+    mask = _rt._mask1d(mask)
+    assert mask is None or (mask.numel() == B * N and mask.element_size() == 1)
+    key_len = _rt._i64(key_len)
+    slopes = slopes.to(torch.float32).contiguous()
+    R = B * N
+    flops = 256.0 * B * N * N * heads + 2.0 * R * D * D + (2.0 * R * D * (D + 128) if x is not None else 0.0)
+    nbytes = float(R) * (2 * (D + 128) + 8 * D + (2 * D if x is not None else 0)) + 2.0 * D * D + (2.0 * D * (D + 128) if x is not None else 0.0)
+    _rt._launch(f"attn_block_short_kernel<{heads}>", flops, nbytes, _rt.lib().ispk_attn_block_short_bf16, _rt._ptr(x), D,
+                _rt._ptr(wqkv_c), qkv.data_ptr(), D + 128, slopes.data_ptr(), _rt._ptr(key_len), wo_c.data_ptr(), resid.data_ptr(),
+                D, _rt._ptr(mask), out.data_ptr(), D, B, N, heads, _rt._stream())
+    return out, qkv
 
 
 # ------------------------------------------------------------------------------------------------- split-fp16 (parity-grade fast path)

@@ -19,14 +19,14 @@
 //   * K rows are padded to 68 dwords so each ds_read_b128 lane group hits 16 distinct 4-bank slots.
 //   * bias -slope*|i-j| and the key-length mask are computed in registers; fully masked key blocks are skipped.
 #include "common.h"
+#include "attn_core.h"
 
 namespace {
 
 constexpr int kLdk = 68;   // padded K/V tile row (64 + 4 dwords)
 constexpr int kTileKeys = 64;
 
-__device__ __forceinline__ float xhalf_max(float v) { return fmaxf(v, __shfl_xor(v, 32, 64)); }
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
+// (xhalf_max, xhalf_sum: attn_core.h)
 
 // MAXT 768 (H = 4..6: 3 waves per SIMD, 168 VGPRs) or 1024 (H = 7, 8); STAGE float4 staging registers per thread: a 64-key
 // K/V tile is 2048 float4, so STAGE * 2 H 64 >= 2048 - 4 covers H >= 4, and H <= 3 (128 .. 384 threads) takes <384, 16>.
@@ -230,23 +230,7 @@ namespace {
 //     init (see the softmax comment in the kernel).
 // Per 32x32 (key x query) block a wave issues 8 MFMAs (256 cycles) and ~100 VALU instructions incl. 16 v_exp_f32: the
 // kernel is VALU-issue-bound, not MFMA-bound; 3 waves per SIMD overlap one wave's softmax with another's MFMAs.
-// max over the two 32-lane halves without the LDS round trip of a bpermute: v_permlane32_swap exchanges the upper half
-// of one register with the lower half of another (gfx950).  (Inline asm: the builtin's second result was miscompiled.)
-// v_max3_f32 without the canonicalising v_max x, x that fmaxf() puts in front of every operand (scores are never sNaN)
-__device__ __forceinline__ float max3_raw(float a, float b, float c) {
-    float r;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// exchange the upper half (lanes 32-63) of x with the lower half (lanes 0-31) of y
-__device__ __forceinline__ void half_swap(uint32_t& x, uint32_t& y) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-__device__ __forceinline__ float xhalf_max_swap(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
+// (max3_raw, half_swap, xhalf_max_swap and the per-block code: attn_core.h)
 
 // K/V staging.  The loop was latency-bound with register-staged 64-key tiles one tile ahead (a tile's 2,000 cycles of
 // work cannot cover a 4,000-cycle miss; deeper register prefetch does not fit 168 VGPRs).  Now K and V stream into a
@@ -296,7 +280,6 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
     klen = klen < 1 ? 1 : (klen > N ? N : klen);
     constexpr float kLog2e = 1.4426950408889634f;
     const float scale2 = 0.125f * kLog2e;
-    const float ninf = -__builtin_huge_valf();
     const int nchunks = (klen + kChunkKeys - 1) / kChunkKeys;
 
     // ---- loaders: DMA instruction i of a chunk (i < IPL) moves 8 rows of K (i even) or V (i odd)
@@ -354,7 +337,6 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
     //     2^kLazy, so most blocks skip the 32-register rescale of O; exp2 arguments stay <= kLazy and the row's true
     //     maximum contributes p >= 1, so nothing overflows or underflows (m_ref starts as block 0's exact maximum);
     //   * plain fp32 instructions throughout (packed fp32 issues slowly beside MFMAs; -fno-slp-vectorize for this file).
-    constexpr float kLazy = 16.0f;
     const float nsl = -8.0f * slopes[head];              // = -slope2 / scale2, exact
     const float nsl2 = nsl * scale2;                      // = -slope2
     // +/- nsl * (key offset of accumulator register r): MFMA C operands.  Resident (opaque, or hipcc rebuilds them from
@@ -425,116 +407,16 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
         for (int kblk = 0; kblk < kChunkKeys / 32; ++kblk) {
             const int key0 = c * kChunkKeys + kblk * 32;
             if (key0 >= klen) break;  // wave-uniform
-            if constexpr (ST) { ta = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); }
-            // the 4 K fragments are requested together (opaque asm reads: hipcc would sink each next to its MFMA and wait
-            // for it there); the 8 transposed V reads follow the score MFMAs and land during the softmax
             const uint32_t blk = (uint32_t)(slot * kSlotBytes + kblk * 32 * 128);
-            bf16x8 kf[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) lds_read_b128_asm<0>(kf[ks], koff[ks] + blk);
-            f32x16 s;
-            float base2;                                   // exp2 argument = fma(s, scale2, base2)
-            const float d0 = (float)(key0 + 4 * h - qi);   // key - query of accumulator register 0
-            if constexpr (kResidentC) {
-                lds_wait<0>();
-                __builtin_amdgcn_sched_barrier(0);
-                if (key0 == q0w) {                          // wave-uniform: the one block that straddles the diagonal
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s[r] = fabsf(d0 + (float)((r & 3) + 8 * (r >> 2))) * nsl;
-                    base2 = mref2;
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[0], qf[0], s, 0, 0, 0);
-                } else if (key0 < q0w) {                    // keys before the queries: |d| = -(d0 + c_r)
-                    base2 = fmaf(-nsl2, d0, mref2);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[0], qf[0], cneg, 0, 0, 0);
-                } else {
-                    base2 = fmaf(nsl2, d0, mref2);
-                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[0], qf[0], cpos, 0, 0, 0);
+            // (attn_core.h: the block's scores, softmax and P·V, shared with attn_block.hip)
+            attn_bf16_key_block<kResidentC, ST>(qf, koff, voff, blk, key0, q0w, qi, h, klen, nsl, nsl2, scale2s, cpos, cneg,
+                                                o0, o1, mref2, l2a, l2b, [&] {
+                if (key0 + 32 >= klen && it + 1 < qpw && qt + 1 < nqt) {
+                    // the tile's last score product: Q is dead, fetch the next tile's fragments behind the softmax / PV / store
+                    __builtin_amdgcn_sched_barrier(0);
+                    load_q(qf, (qt + 1) * 64 + qhalf * 32);
                 }
-#pragma unroll
-                for (int ks = 1; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s, 0, 0, 0);
-            } else {
-                if (key0 == q0w) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s[r] = fabsf(d0 + (float)((r & 3) + 8 * (r >> 2))) * nsl;
-                    base2 = mref2;
-                } else if (key0 < q0w) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s[r] = cneg[r];
-                    base2 = fmaf(-nsl2, d0, mref2);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) s[r] = cpos[r];
-                    base2 = fmaf(nsl2, d0, mref2);
-                }
-                lds_wait<0>();
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s, 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            u32x2 vr[2][2][2];   // [st][dim tile][run]: keys key0 + 16st + 4h + 0..3 (run 0) and + 8 (run 1) of this lane's dim
-            static_for<0, 8>([&](auto ic) {
-                constexpr int i8 = decltype(ic)::value, st = i8 >> 2, dt = (i8 >> 1) & 1, run = i8 & 1;
-                lds_read_b64_tr_b16_asm<(16 * st + 8 * run) * 128>(vr[st][dt][run], voff[dt] + blk);
-            });
-            if (key0 + 32 >= klen && it + 1 < qpw && qt + 1 < nqt) {
-                // the tile's last score product: Q is dead, fetch the next tile's fragments behind the softmax / PV / store
-                __builtin_amdgcn_sched_barrier(0);
-                load_q(qf, (qt + 1) * 64 + qhalf * 32);
-            }
-            if constexpr (ST) { __builtin_amdgcn_sched_barrier(0); tb = __builtin_readcyclecounter(); ts[2] += tb - ta; }
-            if (key0 + 32 > klen) {   // the one block that straddles key_len (wave-uniform test)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    s[r] = key < klen ? s[r] : ninf;
-                }
-            }
-            float bmax = max3_raw(s[0], s[1], s[2]);
-#pragma unroll
-            for (int r = 3; r < 15; r += 2) bmax = max3_raw(bmax, s[r], s[r + 1]);
-            // this lane half's block maximum in exp2 units relative to m_ref (the base differs between the halves), then the row's
-            bmax = xhalf_max_swap(fmaf(fmaxf(bmax, s[15]), scale2s, base2));
-            const bool first = key0 == 0;
-            if (first || __builtin_amdgcn_ballot_w64(bmax > kLazy) != 0) {   // wave-uniform
-                // raise the reference to this block's row maximum (block 0: set it), rescale what was accumulated
-                const float delta = first ? bmax : fmaxf(bmax, 0.f);
-                const float alpha = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);
-                mref2 -= delta;
-                base2 -= delta;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    o0[r] *= alpha;
-                    o1[r] *= alpha;
-                }
-                l2a *= alpha;
-                l2b *= alpha;
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                s[2 * j] = __builtin_amdgcn_exp2f(fmaf(s[2 * j], scale2s, base2));
-                s[2 * j + 1] = __builtin_amdgcn_exp2f(fmaf(s[2 * j + 1], scale2s, base2));
-                l2a += s[2 * j];
-                l2b += s[2 * j + 1];
-            }
-            // P -> bf16 B-operand fragments (k-step st = registers 8st .. 8st+7)
-            union { uint32_t u[4]; bf16x8 f; } pf[2];
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pf[st].u[e] = pack_bf16x2(s[8 * st + 2 * e], s[8 * st + 2 * e + 1]);
-            if constexpr (ST) { __builtin_amdgcn_sched_barrier(0); tc = __builtin_readcyclecounter(); ts[3] += tc - tb; }
-            lds_wait<0>();
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int st = 0; st < 2; ++st) {
-                union { uint32_t u[4]; bf16x8 f; } a0, a1;
-                a0.u[0] = vr[st][0][0][0]; a0.u[1] = vr[st][0][0][1]; a0.u[2] = vr[st][0][1][0]; a0.u[3] = vr[st][0][1][1];
-                a1.u[0] = vr[st][1][0][0]; a1.u[1] = vr[st][1][0][1]; a1.u[2] = vr[st][1][1][0]; a1.u[3] = vr[st][1][1][1];
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0.f, pf[st].f, o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1.f, pf[st].f, o1, 0, 0, 0);
-            }
-            if constexpr (ST) { __builtin_amdgcn_sched_barrier(0); td = __builtin_readcyclecounter(); ts[4] += td - tc; }
+            }, ts);
         }
     }
     const float inv = 1.0f / xhalf_sum(l2a + l2b);
@@ -542,22 +424,9 @@ __global__ __launch_bounds__(MAXT) void attn_bf16_kernel(const uint16_t* __restr
     // store-issue-bound.  The two halves of a query trade groups (v_permlane32_swap: half 0 ends up with dims 8g .. 8g+7 of
     // g = 0 and 2, half 1 with those of g = 1 and 3), so a row leaves in 16-byte pieces, half as many instructions.
     uint2 pk[2][4];   // [tile][g]
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        pk[0][g].x = pack_bf16x2(o0[4 * g] * inv, o0[4 * g + 1] * inv);
-        pk[0][g].y = pack_bf16x2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-        pk[1][g].x = pack_bf16x2(o1[4 * g] * inv, o1[4 * g + 1] * inv);
-        pk[1][g].y = pack_bf16x2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-    }
+    pack_rows_bf16(o0, o1, inv, pk);
     if (wide_store) {      // kernel-uniform
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int gp = 0; gp < 2; ++gp) {
-                // x = group 2gp, y = group 2gp+1: afterwards half 0 holds (its x, the partner's x), half 1 (the partner's y, its y)
-                half_swap(pk[t][2 * gp].x, pk[t][2 * gp + 1].x);
-                half_swap(pk[t][2 * gp].y, pk[t][2 * gp + 1].y);
-            }
+        swap_row_halves(pk);
         if (qi < N) {
             uint16_t* op = out + ((int64_t)b * N + qi) * ldo + head * 64 + 8 * h;
 #pragma unroll

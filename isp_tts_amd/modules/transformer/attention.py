@@ -21,6 +21,7 @@ from ...staging import StagedWeights
 from ..constructor import Constructor, ModuleConfig
 from .attend import Attend, AttentionIntermediates
 from .embeddings import LearnedALiBiPositionalBias
+from .plan import short_block_ok
 
 
 class AttentionSharedIntermediates(NamedTuple):
@@ -66,6 +67,9 @@ class Attention(nn.Module, Constructor):
         self.attend = Attend(causal=causal, dropout=dropout, scale=self.scale)
         self.to_out = nn.Linear(self.out_dim, dim, bias=False)
         self.compute_dtype = torch.float32
+        # at <= 128 positions the bf16 no-tape block is ONE kernel where `plan.short_block_ok` allows (off: the three launches;
+        # both give the same bits)
+        self.short_block = True
         self._cache = StagedWeights()
 
     # weights staged for the kernels (fused [to_q; to_kv], optional bf16 copies): one image per dtype, rebuilt when a
@@ -100,6 +104,15 @@ class Attention(nn.Module, Constructor):
         kernel applies this layer's attention_norm and q/kv projection), staged once per weight version."""
         return self._cache.get("wqc", (self.to_q.weight, self.to_kv.weight),
                                lambda: runtime.chunk_k16(self._staged(torch.bfloat16)[0]))
+
+    def _chunked_wo16(self) -> Tensor:
+        """to_out's weight as k-step chunks [out_dim / 16][dim][16] (ispk_attn_block_short_bf16), staged once per weight version."""
+        return self._cache.get("wo16", (self.to_out.weight,),
+                               lambda: runtime.chunk_k16(self._staged(torch.bfloat16)[1]))
+
+    def _no_tape(self) -> bool:
+        return not (torch.is_grad_enabled() and any(p.requires_grad for p in (self.to_q.weight, self.to_kv.weight,
+                                                                              self.to_out.weight)))
 
     def qkv_lnin(self, x: Tensor, norm, stats: Optional[Tensor] = None) -> Tensor:
         """q/kv rows of norm(x) with the LayerNorm applied by the GEMM itself while it stages the fp32 rows x (bf16 path): from
@@ -137,6 +150,22 @@ class Attention(nn.Module, Constructor):
             inter = AttentionIntermediates(queries=qkv[..., :hq].view(b, n, self.heads, 64).transpose(1, 2),
                                            keys=qkv[..., hq:hq + 64], values=qkv[..., hq + 64:])
             return out, inter, AttentionSharedIntermediates(rel_pos_bias=None)
+        hq = self.heads * 64
+        if self.short_block and b <= 65535 and short_block_ok(cdt=dt, tape=not self._no_tape(), residual=residual is not None,
+                                               defer_out=defer_out, n=n, heads=self.heads, dim=self.dim, out_dim=self.out_dim,
+                                               rows=b * n):
+            # one launch: (q/kv projection,) attention, to_out + mask + residual - the same bits as the three below
+            if qkv is not None:
+                assert qkv.dtype == dt and qkv.shape == (b, n, hq + 128)
+                out, _ = runtime.attn_block_short(None, None, qkv, self.heads, slopes, key_len, self._chunked_wo16(), residual, mask)
+            else:
+                if x.dtype != dt:
+                    x = runtime.cast_bf16(x)
+                out, qkv = runtime.attn_block_short(x.contiguous(), self._chunked_wqkv(), None, self.heads, slopes, key_len,
+                                                    self._chunked_wo16(), residual, mask)
+            inter = AttentionIntermediates(queries=qkv[..., :hq].view(b, n, self.heads, 64).transpose(1, 2),
+                                           keys=qkv[..., hq:hq + 64], values=qkv[..., hq + 64:])
+            return out, inter, AttentionSharedIntermediates(rel_pos_bias=None)
         if qkv is not None:
             assert dt == torch.bfloat16 and qkv.dtype == dt and qkv.shape == (b, n, self.heads * 64 + 128)
         else:
@@ -150,7 +179,6 @@ class Attention(nn.Module, Constructor):
         else:
             flags = runtime.EP_MASK_ACC if mask is not None else 0
             out = runtime.gemm(o, wo, resid=residual, mask=mask, flags=flags, out_dtype=torch.float32)
-        hq = self.heads * 64
         inter = AttentionIntermediates(queries=qkv[..., :hq].view(b, n, self.heads, 64).transpose(1, 2),
                                        keys=qkv[..., hq:hq + 64], values=qkv[..., hq + 64:])
         return out, inter, AttentionSharedIntermediates(rel_pos_bias=None)

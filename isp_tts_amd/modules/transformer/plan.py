@@ -34,6 +34,26 @@ MAX_SPLITS = 8
 # rows: 2.004 -> 2.012 ms; 8 utterances per GPU: 1.014 -> 1.066 ms)
 PROJ_FFN_SPLIT_MIN_ROWS = 8192
 
+# The short-sequence attention block as ONE kernel (ispk_attn_block_short_bf16: q/kv projection, attention, to_out with mask and
+# residual) instead of three launches: at most 128 positions per batch item (the whole key range of an item sits in one
+# workgroup's LDS), dims 256 / 384 with 64-wide heads.
+SHORT_BLOCK_MAX_N = 128
+# ... and from this many rows on, per dim.  The kernel itself beats the three launches at every size (tools/bench_attn_block.py,
+# per block, 64 / 8 / 1 utterances of 100 positions: dim 384 30.5 -> 21.8, 20.0 -> 19.4, 19.4 -> 19.3 us; dim 256 22.0 -> 14.7,
+# 16.3 -> 12.9, 15.8 -> 12.9 us); the threshold is set by the graphed step (tools/ab_switches.py, switch off minus on, and the
+# spread of two captures of one configuration):
+#   dim 384, the text encoder's six layers:  +36 us at 6,400 rows (spread 2), +12 .. 20 at 3,200 (9), +9 .. 17 at 1,600 (8),
+#                                            +23 at 800 (0.3): on from one 128-row block (`SPLIT_MIN_ROWS`) - below it a
+#                                            stack is the plain seven launches that the hand-off tests count, and one
+#                                            utterance of 100 rows gains nothing anyway (19.4 -> 19.3 us a block);
+#   dim 256, the flow predictor's three layers, which run on the side stream beside the decoder: +27 us at 6,400 rows (spread 2),
+#                                            -3 .. -12 at 3,200 (9), -1 .. +8 at 1,600 (8), -5.5 at 800 (0.3) - its 512-thread workgroups
+#                                            with 114 KB of LDS take CUs from the decoder's kernels there: on from the one
+#                                            size at which it is measured to win.
+# (The embedding stack's single dim-256 layer gains 2.5 us at 6,400 rows and 3.1 at 800 - not clear of three times the spread:
+# `TransformerTemporalModule` leaves its switch off.)
+SHORT_BLOCK_MIN_ROWS = {384: 128, 256: 6400}
+
 
 @dataclass(frozen=True)
 class Seams:
@@ -198,3 +218,13 @@ def select_plan(*, cdt: torch.dtype, dim: int, heads: int, out_dim: int, inner: 
         # two-GEMM feed-forward (e.g. an activation the fused kernel lacks): feed_forward_norm inside the first Linear's GEMM
         return Plan(qkv, False, Form.LNIN_GEMM)
     return Plan(qkv, False, Form.NORM_FFN_FUSED if ffn_fused_ok(cdt, gelu, dim, rows, seams) else Form.NORM_FFN_GEMMS)
+
+
+def short_block_ok(*, cdt: torch.dtype, tape: bool, residual: bool, defer_out: bool, n: int, heads: int, dim: int, out_dim: int,
+                   rows: int) -> bool:
+    """`Attention.forward` (consulted when its `short_block` switch is on): may this call be ONE ispk_attn_block_short_bf16
+    launch?  bf16 forward without a tape, the residual fused into to_out (so not `defer_out`, where the next kernel applies
+    to_out), at most SHORT_BLOCK_MAX_N positions, heads * 64 = dim in {256, 384}, and enough rows for the kernel to win.
+    Independent of `select_plan`: the plan decides which tensors reach the attention block, this only how it launches."""
+    return (cdt == torch.bfloat16 and not tape and residual and not defer_out and 1 <= n <= SHORT_BLOCK_MAX_N
+            and dim in SHORT_BLOCK_MIN_ROWS and heads * 64 == dim == out_dim and rows >= SHORT_BLOCK_MIN_ROWS[dim])
