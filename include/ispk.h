@@ -1103,6 +1103,33 @@ int32_t ispk_snake_aa_f32(const float* x, int64_t ldx, const float* al, const fl
                           int64_t ldo, const int64_t* len, int32_t len_mul, int32_t B, int32_t T, int32_t C,
                           ispk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Vocoder denoiser (csrc/denoise.hip; isp_tts_amd/denoiser.py): STFT, spectral bias subtraction, ISTFT in one launch, on a
+ * padded mono batch fp32 [B][S] at row stride ld_audio >= S with int64 audio_len [B] on the device (NULL: every utterance has
+ * S samples; a length below 0 or above S counts as 0).  N = 1024, hop 256, K = 513 bins, w the periodic Hann window.
+ *
+ * ispk_denoise_tile_samples   output samples of one utterance per workgroup (4096): the tests' tile edges.
+ * ispk_denoise_f32            per utterance x[0, n), n = audio_len[b] >= 513:
+ *                               xp[p] = x[r(p - 512)], p < n + 1024, r(i) = -i (i < 0), 2 (n - 1) - i (i >= n), else i
+ *                               X_f[k] = sum_j xp[256 f + j] w[j] exp(-2 pi i j k / 1024)    f < F = 1 + n / 256, k <= 512
+ *                               Y_f[k] = X_f[k] max(1 - t_k / |X_f[k]|, 0), 0 where |X_f[k]| = 0;  t_k = strength bias[k]
+ *                               y_f    = irfft_1024(Y_f) (1 / 1024; imaginary parts of bins 0 and 512 dropped)
+ *                               out[s] = (sum_f w[j] y_f[j]) / (sum_f w[j]^2), j = s + 512 - 256 f, over the frames f < F
+ *                                        with 0 <= j < 1024, both sums in ascending f; 0 for n <= s < S
+ *                             = torch.stft(center, reflect), the shrink, torch.istft(center, length = n).  With n < 513 (no
+ *                             reflection) out[s] = x[s] for s < n, bit for bit.  bias fp32 [513] >= 0 and tables fp32 [5120] =
+ *                             W_2048^m as (re, im), then w, both made in float64 and rounded once, are device memory.
+ *                             strength_item (may be NULL): fp32 [B] on the device, replaces `strength` per utterance (a negative
+ *                             or NaN device value counts as 0).  Nothing at or past n is read.  An utterance's samples depend on
+ *                             that utterance alone, every sum runs in a fixed order, no atomics: a ragged batch, repeated calls
+ *                             and graph replays are bit-identical.  Scalar loads and stores: no alignment requirement.
+ * Refused: NULL audio, tables, bias or out (E_NULL); B > 65535, S > 2^31 - 8193, ld_audio or ld_out < S, out == audio (the
+ * neighbouring tiles read the halo), strength negative or NaN (E_SHAPE).  B = 0 or S = 0 is a no-op. */
+int32_t ispk_denoise_tile_samples(void);
+int32_t ispk_denoise_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables,
+                         const float* bias, const float* strength_item, float strength, float* out, int64_t ld_out, int32_t B,
+                         int32_t S, ispk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

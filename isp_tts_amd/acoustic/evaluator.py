@@ -155,13 +155,17 @@ class SynthesisEvaluator:
         return out
 
     @torch.no_grad()
-    def score_infer(self, model, inputs, vocoder=None, features=None, per_item: bool = False, **infer_kwargs) -> dict:
+    def score_infer(self, model, inputs, vocoder=None, features=None, per_item: bool = False, denoiser=None,
+                    **infer_kwargs) -> dict:
         """`model.infer` on inputs["text"] / ["text_len"] (with ["speaker"] if present; `infer_kwargs` go to it: steps,
         flow_noise, max_dec_len ...), its mel and dec_lengths scored against inputs["mel"] / ["mel_len"].  With a Vocoder and
         an AcousticFeatures (pitch in Hz: pitch_mean=0, pitch_std=1) the mel is also vocoded, the waveform's pitch extracted and
-        scored against inputs["pitch_hz"].  Capturable with torch.cuda.graph when `max_dec_len` is given (infer's own rule)."""
+        scored against inputs["pitch_hz"]; a `denoiser` (denoiser.Denoiser) is applied to the waveform between the two.
+        Capturable with torch.cuda.graph when `max_dec_len` is given (infer's own rule)."""
         if (vocoder is None) != (features is None):
             raise ValueError("give both the vocoder and the feature extractor or neither")
+        if denoiser is not None and vocoder is None:
+            raise ValueError("a denoiser needs the vocoder whose waveform it cleans")
         if features is not None and (not features.pitch or features.pitch_mean != 0.0 or features.pitch_std != 1.0):
             raise ValueError("the feature extractor must deliver pitch in Hz (pitch=True, pitch_mean=0, pitch_std=1)")
         speaker = inputs.get("speaker") if isinstance(inputs, dict) else getattr(inputs, "speaker", None)
@@ -171,6 +175,8 @@ class SynthesisEvaluator:
         pitch_out = pitch_target = None
         if vocoder is not None:
             audio, audio_len = vocoder(mel, adaptor.dec_lengths)
+            if denoiser is not None:
+                audio, audio_len = denoiser(audio, audio_len)
             pitch_out, pitch_target = features(audio, audio_len)["pitch"], _field(inputs, "pitch_hz")
         return self(mel, adaptor.dec_lengths, _field(inputs, "mel"), _field(inputs, "mel_len"), pitch_out, pitch_target, per_item=per_item)
 

@@ -1,5 +1,6 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
-the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip)."""
+the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip) with their denoiser
+(csrc/denoise.hip)."""
 from typing import Optional
 
 import torch
@@ -12,7 +13,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "audio_measure_workspace_floats", "_mono_batch", "_out_like", "audio_measure", "audio_apply", "pcm16", "VOCODER_HOP",
            "VOCODER_TABLE_FLOATS", "_lengths_ptr", "vocoder_unfold", "dwconv7_ln", "istft_head", "HIFIGAN_TILE_ROWS",
            "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows", "hifigan_conv", "_hifigan_bn",
-           "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa"]
+           "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa", "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT",
+           "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -423,4 +425,44 @@ def snake_aa(x: Tensor, T: int, al: Tensor, inv_b: Tensor, taps: Tensor, out: Op
     _rt._launch("snake_aa_kernel", 56.0 * R * C, 8.0 * R * C, _rt.lib().ispk_snake_aa_f32, x.data_ptr(), x.stride(0),
                 al.data_ptr(), inv_b.data_ptr(), taps.data_ptr(), out.data_ptr(), out.stride(0), ln, len_mul, B, T, C,
                 _rt._stream())
+    return out
+
+
+# -------------------------------------------------------------------------------------------------- vocoder denoiser
+DENOISE_TILE_SAMPLES = 4096   # ispk_denoise_tile_samples(): output samples of one utterance per workgroup
+DENOISE_N_FFT, DENOISE_HOP = 1024, 256
+DENOISE_TABLE_FLOATS = 2 * 2048 + 1024     # W_2048^m as (re, im), then the periodic Hann window, both made in float64
+
+
+def denoise(audio: Tensor, audio_len: Optional[Tensor], tables: Tensor, bias: Tensor, strength,
+            out: Optional[Tensor] = None) -> Tensor:
+    """ispk_denoise_f32, one launch, no host read: fp32 audio [B, S] (unit stride on S, any row stride) with int64 lengths [B]
+    (None: all S samples) -> out fp32 [B, S]: STFT (1024 / 256, periodic Hann, reflect-centred), every bin's magnitude less
+    strength * bias[k] clamped at zero with the phase kept, ISTFT; zeros from audio_len on, utterances below 513 samples
+    copied.  bias fp32 [513], tables fp32 [5120] (denoiser.Denoiser builds both); strength a float >= 0, or an fp32 [B] device
+    tensor with one value per utterance.  Out of place only."""
+    per_item = strength if isinstance(strength, Tensor) else None
+    _rt._dev(audio, audio_len, tables, bias, per_item, out)
+    if audio.dtype != torch.float32 or audio.ndim != 2 or audio.stride(1) != 1:
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    if audio_len is not None and (audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous()):
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= DENOISE_TABLE_FLOATS
+    assert bias.dtype == torch.float32 and bias.numel() == DENOISE_N_FFT // 2 + 1 and bias.is_contiguous()
+    if per_item is not None:
+        if per_item.dtype != torch.float32 or per_item.shape != (B,) or not per_item.is_contiguous():
+            raise ValueError(f"strength: a float or a contiguous fp32 [{B}] tensor, got {per_item.dtype} {tuple(per_item.shape)}")
+    elif not float(strength) >= 0.0:
+        raise ValueError(f"strength: {strength} is negative or NaN")
+    out = torch.empty((B, S), dtype=torch.float32, device=audio.device) if out is None else out
+    _out_like("out", out, torch.float32, (B, S))
+    if B == 0 or S == 0:
+        return out
+    # per hop: 19 / 16 of two 512-point transforms (9 radix passes of ~5 N flops) and the split / shrink / merge of 513 bins
+    _rt._launch("denoise_kernel", B * S / 256.0 * (19.0 / 16.0) * (2 * 5.0 * 512 * 9 + 40.0 * 513), 8.0 * B * S,
+                _rt.lib().ispk_denoise_f32, audio.data_ptr(), audio.stride(0), _rt._ptr(audio_len), tables.data_ptr(),
+                bias.data_ptr(), _rt._ptr(per_item), 0.0 if per_item is not None else float(strength), out.data_ptr(),
+                out.stride(0), B, S, _rt._stream())
     return out
