@@ -1130,6 +1130,52 @@ int32_t ispk_denoise_f32(const float* audio, int64_t ld_audio, const int64_t* au
                          const float* bias, const float* strength_item, float strength, float* out, int64_t ld_out, int32_t B,
                          int32_t S, ispk_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
+ * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both
+ * sides, no centring.  Utterance b has Tb = mel_len[b] frames (NULL: T; a value outside [0, T] counts as 0) and n = 256 Tb
+ * samples.  Audio is a padded mono batch fp32 [B][256 T] at a row stride >= 256 T; the magnitude is fp32 [B][T][513] with
+ * contiguous frame rows (stride 513) and a leading stride ld_mag >= 513 T.
+ *
+ * ispk_griffinlim_tile_samples  output samples of one utterance per workgroup (4096): the tests' tile edges.
+ * ispk_mel_to_linear_f32      mag[b][f][k] = max(sum_m P[k][m] exp(mel[b][m][f]), 0) for f < Tb, the sum in ascending m with
+ *                             fma, accurate expf.  mel fp32 or fp16 (mel_f16 != 0) [B][n_mels][T] at element strides mel_sb,
+ *                             mel_sc, mel_st; pinv_t fp32 [n_mels][513] = P transposed (P the pseudo-inverse of the mel
+ *                             filterbank, made in float64 and rounded once), device memory.  Frames at or past Tb are neither
+ *                             read nor written.  Refused: NULL mel, pinv_t or mag (E_NULL); B > 65535, n_mels outside 1 .. 128,
+ *                             T > 8388575, ld_mag < 513 T (E_SHAPE).  B = 0 or T = 0 is a no-op.
+ * ispk_griffinlim_step_f32    one launch.  With xp[p] = x[p - 384] inside [0, n) and 0 elsewhere:
+ *                               mode ISPK_GRIFFINLIM_STEP (one projection of the iteration, x = audio):
+ *                                 X_f[k] = sum_j xp[256 f + j] w[j] exp(-2 pi i j k / 1024)          f < Tb, k <= 512
+ *                                 Y_f[k] = M_f[k] X_f[k] / |X_f[k]|, M_f[k] where |X_f[k]|^2 = 0 in fp32; M = mag[b][f][k]
+ *                               mode ISPK_GRIFFINLIM_INIT (the initial waveform; audio is not read and may be NULL):
+ *                                 Y_f[k] = M_f[k] exp(2 pi i u), u = (h >> 8) 2^-24, h = drop_hash(mix_seed(seed), 513 f + k)
+ *                                          of csrc/dropout.h (32-bit index), by an accurate sincospif: a function of
+ *                                          (seed, f, k) alone
+ *                               then in both modes
+ *                                 y_f    = irfft_1024(Y_f) (1 / 1024; imaginary parts of bins 0 and 512 dropped)
+ *                                 out[s] = (sum_f w[j] y_f[j]) / (sum_f w[j]^2), j = s + 384 - 256 f, over the frames f < Tb
+ *                                          with 0 <= j < 1024, both sums in ascending f; 0 for n <= s < 256 T
+ *                             IEEE square root and division; M = 0 gives Y = 0 exactly.  The w^2 sum is positive for every
+ *                             s < n and every Tb >= 1.  audio_len (may be NULL): int64 [B] on the device, receives 256 Tb.
+ *                             tables fp32 [5120] = W_2048^m as (re, im), then w, both made in float64 and rounded once
+ *                             (ispk_denoise_f32's).  Nothing at or past n (audio) or Tb (mag) is read.  An utterance's samples
+ *                             depend on that utterance and the seed alone, every sum runs in a fixed order, no atomics: a
+ *                             ragged batch, repeated calls and graph replays are bit-identical.  Scalar loads and stores: no
+ *                             alignment requirement.  Refused: a mode other than the two (E_UNSUP); NULL mag, tables or out,
+ *                             or NULL audio in mode STEP (E_NULL); B > 65535, T > 8388575, a row stride shorter than its
+ *                             row, out == audio in mode STEP (the neighbouring tiles read the halo) (E_SHAPE).  B = 0 or
+ *                             T = 0 is a no-op. */
+#define ISPK_GRIFFINLIM_STEP 0
+#define ISPK_GRIFFINLIM_INIT 1
+int32_t ispk_griffinlim_tile_samples(void);
+int32_t ispk_mel_to_linear_f32(const void* mel, int32_t mel_f16, int64_t mel_sb, int64_t mel_sc, int64_t mel_st,
+                               const int64_t* mel_len, const float* pinv_t, float* mag, int64_t ld_mag, int32_t B,
+                               int32_t n_mels, int32_t T, ispk_stream_t stream);
+int32_t ispk_griffinlim_step_f32(const float* audio, int64_t ld_audio, const float* mag, int64_t ld_mag,
+                                 const int64_t* mel_len, const float* tables, float* out, int64_t ld_out, int64_t* audio_len,
+                                 int32_t B, int32_t T, int32_t mode, uint64_t seed, ispk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

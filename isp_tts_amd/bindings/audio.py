@@ -1,6 +1,6 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
 the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip) with their denoiser
-(csrc/denoise.hip)."""
+(csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip)."""
 from typing import Optional
 
 import torch
@@ -14,7 +14,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "VOCODER_TABLE_FLOATS", "_lengths_ptr", "vocoder_unfold", "dwconv7_ln", "istft_head", "HIFIGAN_TILE_ROWS",
            "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows", "hifigan_conv", "_hifigan_bn",
            "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa", "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT",
-           "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise"]
+           "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
+           "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -465,4 +466,81 @@ def denoise(audio: Tensor, audio_len: Optional[Tensor], tables: Tensor, bias: Te
                 _rt.lib().ispk_denoise_f32, audio.data_ptr(), audio.stride(0), _rt._ptr(audio_len), tables.data_ptr(),
                 bias.data_ptr(), _rt._ptr(per_item), 0.0 if per_item is not None else float(strength), out.data_ptr(),
                 out.stride(0), B, S, _rt._stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- Griffin-Lim mel inversion
+GRIFFINLIM_TILE_SAMPLES = 4096   # ispk_griffinlim_tile_samples(): output samples of one utterance per workgroup
+GRIFFINLIM_N_FFT, GRIFFINLIM_HOP, GRIFFINLIM_PAD = 1024, 256, 384      # the feature extractor's framing
+GRIFFINLIM_STEP, GRIFFINLIM_INIT = 0, 1                                # ISPK_GRIFFINLIM_STEP / _INIT
+
+
+def _magnitude(mag: Tensor, B: int, T: int) -> None:
+    bins = GRIFFINLIM_N_FFT // 2 + 1
+    if (mag.dtype != torch.float32 or tuple(mag.shape) != (B, T, bins) or mag.stride(2) != 1 or mag.stride(1) != bins
+            or (B > 1 and mag.stride(0) < T * bins)):
+        raise ValueError(f"magnitude: fp32 [{B}, {T}, {bins}] with contiguous frame rows, got {mag.dtype} {tuple(mag.shape)} "
+                         f"strides {tuple(mag.stride())}")
+
+
+def mel_to_linear(mel: Tensor, mel_len: Optional[Tensor], pinv_t: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """ispk_mel_to_linear_f32, one launch, no host read: log-mel fp32 / fp16 [B, n_mels, T] (any strides) with int64 lengths [B]
+    (None: all T frames) -> magnitude fp32 [B, T, 513] = max(P exp(mel), 0); frames at or past a length are neither read nor
+    written.  pinv_t fp32 [n_mels, 513]: the transposed pseudo-inverse of the mel filterbank (griffinlim.GriffinLim builds it)."""
+    _rt._dev(mel, mel_len, pinv_t, out)
+    if mel.ndim != 3 or mel.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"mel: fp32 / fp16 [B, n_mels, T], got {mel.dtype} {tuple(mel.shape)}")
+    B, C, T = mel.shape
+    bins = GRIFFINLIM_N_FFT // 2 + 1
+    assert pinv_t.dtype == torch.float32 and tuple(pinv_t.shape) == (C, bins) and pinv_t.is_contiguous()
+    ml = _lengths_ptr(mel_len, B)
+    out = torch.empty((B, T, bins), dtype=torch.float32, device=mel.device) if out is None else out
+    _magnitude(out, B, T)
+    if B == 0 or T == 0:
+        return out
+    _rt._launch(f"mel_to_linear_kernel<{'f16' if mel.dtype == torch.float16 else 'f32'}>", 2.0 * B * T * bins * C,
+                float(mel.numel() * mel.element_size() + 4 * B * T * bins), _rt.lib().ispk_mel_to_linear_f32, mel.data_ptr(),
+                int(mel.dtype == torch.float16), mel.stride(0), mel.stride(1), mel.stride(2), ml, pinv_t.data_ptr(),
+                out.data_ptr(), out.stride(0), B, C, T, _rt._stream())
+    return out
+
+
+def griffinlim_step(audio: Optional[Tensor], mag: Tensor, mel_len: Optional[Tensor], tables: Tensor, out: Tensor,
+                    audio_len: Optional[Tensor] = None, mode: int = GRIFFINLIM_STEP, seed: int = 0) -> Tensor:
+    """ispk_griffinlim_step_f32, one launch, no host read.  mode GRIFFINLIM_STEP: one projection of fp32 audio [B, 256 T] (unit
+    stride on the samples, any row stride) onto the magnitude mag fp32 [B, T, 513] - STFT in the extractor's framing (1024 /
+    256, periodic Hann, 384 zeros on both sides), the magnitude replaced with the phase kept, ISTFT - into out fp32 [B, 256 T],
+    out of place.  mode GRIFFINLIM_INIT: the ISTFT of mag with the phases hashed from (seed, frame, bin); audio is not read
+    (None).  Zeros from 256 mel_len[b] on; audio_len int64 [B], if given, receives 256 mel_len.  tables fp32 [5120] as
+    denoiser.denoise_tables() builds them."""
+    _rt._dev(audio, mag, mel_len, tables, out, audio_len)
+    if mode not in (GRIFFINLIM_STEP, GRIFFINLIM_INIT):
+        raise ValueError(f"mode {mode}: GRIFFINLIM_STEP or GRIFFINLIM_INIT")
+    if mag.ndim != 3:
+        raise ValueError(f"magnitude: fp32 [B, T, 513], got {tuple(mag.shape)}")
+    B, T = mag.shape[:2]
+    _magnitude(mag, B, T)
+    S = T * GRIFFINLIM_HOP
+    if mode == GRIFFINLIM_STEP:
+        if audio is None:
+            raise ValueError("mode GRIFFINLIM_STEP needs the audio to project")
+        _out_like("audio", audio, torch.float32, (B, S))
+    else:
+        audio = None
+    _out_like("out", out, torch.float32, (B, S))
+    ml = _lengths_ptr(mel_len, B)
+    if audio_len is not None:
+        _out_like("audio_len", audio_len, torch.int64, (B,))
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= DENOISE_TABLE_FLOATS
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed {seed}: an unsigned 64-bit value")
+    if B == 0 or T == 0:
+        return out
+    # per hop: 20 / 16 of one (init) or two 512-point transforms (9 radix passes of ~5 N flops) and the projection of 513 bins
+    ffts = 1 if mode == GRIFFINLIM_INIT else 2
+    _rt._launch("griffinlim_kernel<init>" if mode == GRIFFINLIM_INIT else "griffinlim_kernel<step>",
+                B * T * (20.0 / 16.0) * (ffts * 5.0 * 512 * 9 + 40.0 * 513), (4.0 * ffts + 4.0 * 513 / 256) * B * S,
+                _rt.lib().ispk_griffinlim_step_f32, _rt._ptr(audio), 0 if audio is None else audio.stride(0), mag.data_ptr(),
+                mag.stride(0), ml, tables.data_ptr(), out.data_ptr(), out.stride(0), _rt._ptr(audio_len), B, T, mode, int(seed),
+                _rt._stream())
     return out

@@ -1,0 +1,264 @@
+// Griffin-Lim mel inversion (isp_tts_amd/griffinlim.py): the mel -> magnitude product and ONE projection of the iteration per
+// launch - STFT, replace the magnitude with the target and keep the phase, ISTFT - in the framing of the feature extractor
+// (csrc/features.hip): n_fft = win = 1024, hop 256, periodic Hann, 384 zeros on both sides, no centring, so an utterance of
+// T frames has n = 256 T samples (include/ispk.h has the definition).
+//
+//   griffinlim_kernel<kInit>  grid (ceil(256 T / 4096), B), 512 threads = 4 groups of 128: denoise_kernel's geometry (denoise.hip)
+//                    with the extractor's framing.  A workgroup writes 16 hop segments (4096 samples) of ONE utterance.  Sample
+//                    s takes frames floor((s + 384) / 256) - 3 .. floor((s + 384) / 256), so the tile at hop q0 needs the
+//                    up-to-20 frames q0 - 2 .. q0 + 17 within [0, T): the 4 frames it shares with its neighbours are
+//                    transformed by both (no atomics, no second pass, nothing in HBM between analysis and synthesis).  Frames
+//                    run 4 at a time, one per group:
+//                      gather    (step) 1024 samples x[256 f - 384 + j] inside [0, n), zero elsewhere (a select: never an index
+//                                outside the utterance), times the window, as z[m] = x[2m] + i x[2m+1] into the ping buffer;
+//                      forward   (step) 512-point complex Stockham FFT (fft.h) into the frame's 4 KB slot;
+//                      project   per bin pair (k, 512 - k): step: X by real_split, Y = M X / sqrt(|X|^2) (IEEE sqrt and
+//                                division), Y = M where |X|^2 = 0; init: Y = M (cos, sin)(2 pi u), u = (hash >> 8) 2^-24 from
+//                                drop_hash(seed, 513 f + k) by sincospif.  M = 0 gives exactly 0.  Y / 1024 is packed straight into
+//                                the inverse's half-length spectrum Z_k = (Y_k + conj Y_{512-k}) + i (Y_k - conj Y_{512-k})
+//                                conj(W_1024^k) (imaginary parts of bins 0 and 512 dropped, as irfft);
+//                      inverse   512-point FFT back into the slot: the frame's 1024 real samples in order;
+//                    then per output sample the window-weighted overlap-add of its <= 4 frames and the division by the sum of
+//                    their w^2 (positive for every s < n and every T >= 1), both in ascending frame order.  Samples at or past
+//                    n are written as 0.  LDS: 80 KB of frame slots + 16 KB of ping buffers + 8 KB twiddles + 4 KB window.
+//   mel_to_linear_kernel  grid (ceil(T / 8), B), 256 threads.  exp(mel) of 8 frames into LDS, then thread k accumulates
+//                    sum_m P[k][m] exp(mel[m][f]) for the 8 frames in ascending m (P is read transposed: lanes on k), clamps at 0.
+// A frame's arithmetic depends on (n, f, seed) alone and a sample's on (n, s) alone - not on the tile, on B, on T or on the
+// row's neighbours - and there are no atomics: a ragged batch gives each utterance the bits it gets alone, and repeated calls
+// and graph replays repeat theirs.  LDS access patterns are denoise_kernel's (see there).
+//
+// gfx950 resources (csrc/resource_report.py griffinlim.hip; no spills, no scratch):
+//   griffinlim_kernel<false>  72 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
+//   griffinlim_kernel<true>   66 VGPRs, LDS 110,592 B dynamic
+//   mel_to_linear_kernel      60 VGPRs (fp32 and fp16 mel), LDS 4,096 B static
+#include <math.h>
+
+#include "common.h"
+#include "dropout.h"
+#include "fft.h"
+
+namespace {
+
+constexpr int kHop = 256;
+constexpr int kNfft = 1024;
+constexpr int kHalf = kNfft / 2;                   // 512: the complex transform's length
+constexpr int kBins = kHalf + 1;                   // 513
+constexpr int kPad = (kNfft - kHop) / 2;           // 384 zeros on each side, the extractor's pad
+constexpr int kSegs = 16;                          // hop segments written per workgroup
+constexpr int kTile = kSegs * kHop;                // 4096 samples
+constexpr int kSlots = kSegs + 4;                  // frame slots: 20 frames touch a tile
+constexpr int kGroups = 4;                         // transforms side by side
+constexpr int kGT = 128;                           // threads per transform
+constexpr int kThreads = kGroups * kGT;
+constexpr int kTw = 1024;                          // W_1024^m: the 512-point FFT's twiddles and the split's
+constexpr size_t kLds = sizeof(cf) * (kTw + kGroups * kHalf) + sizeof(float) * (kNfft + kSlots * kNfft);
+constexpr int kMaxFrames = (INT32_MAX - 2 * kTile) / kHop;
+
+constexpr int kMelFrames = 8;                      // frames per workgroup of mel_to_linear_kernel
+constexpr int kMelThreads = 256;
+constexpr int kMaxMels = 128;
+
+__device__ __forceinline__ int valid_frames(const int64_t* mel_len, int b, int T) {
+    if (!mel_len) return T;
+    const int64_t l = mel_len[b];
+    return (l >= 0 && l <= T) ? (int)l : 0;
+}
+
+// Y / 1024 of the projection: M X / |X|, M where |X|^2 = 0, exactly 0 for M = 0
+__device__ __forceinline__ cf project(cf X, float M) {
+    if (M == 0.f) return make_float2(0.f, 0.f);
+    const float ms = M * (1.0f / kNfft), m2 = X.x * X.x + X.y * X.y;
+    if (!(m2 > 0.f)) return make_float2(ms, 0.f);
+    const float g = ms / sqrtf(m2);
+    return make_float2(X.x * g, X.y * g);
+}
+
+// Y / 1024 of the initial spectrum: M exp(2 pi i u), u = (hash >> 8) 2^-24 a function of (seed, f, k) alone
+__device__ __forceinline__ cf hashed_phase(float M, uint64_t seed, int f, int k) {
+    if (M == 0.f) return make_float2(0.f, 0.f);
+    const uint32_t h = drop_hash(seed, (uint32_t)f * (uint32_t)kBins + (uint32_t)k);
+    float s, c;
+    sincospif((float)(h >> 8) * (2.0f / 16777216.0f), &s, &c);      // 2 u: exact in fp32
+    const float ms = M * (1.0f / kNfft);
+    return make_float2(ms * c, ms * s);
+}
+
+template <bool kInit>
+__global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __restrict__ audio, int64_t lda,
+                                                              const float* __restrict__ mag, int64_t ldm,
+                                                              const int64_t* __restrict__ mel_len,
+                                                              const float* __restrict__ tables, float* __restrict__ out,
+                                                              int64_t ldo, int64_t* __restrict__ audio_len, int T,
+                                                              uint64_t seed) {
+    extern __shared__ float4 lds_raw[];
+    cf* tw = reinterpret_cast<cf*>(lds_raw);                          // [kTw]
+    cf* ping = tw + kTw;                                              // [kGroups][512]
+    float* win = reinterpret_cast<float*>(ping + kGroups * kHalf);    // [1024]
+    float* frames = win + kNfft;                                      // [kSlots][1024]
+
+    const int b = blockIdx.y, tid = threadIdx.x, g = tid / kGT, lt = tid % kGT;
+    const int Tb = valid_frames(mel_len, b, T), n = Tb * kHop, S = T * kHop;
+    const int m0 = blockIdx.x * kTile, m1 = min(S, m0 + kTile);
+    const int mv = max(m0, min(n, m1));                               // [m0, mv) are the tile's samples inside the utterance
+    const float* xrow = kInit ? nullptr : audio + (int64_t)b * lda;
+    const float* mrow = mag + (int64_t)b * ldm;
+    float* orow = out + (int64_t)b * ldo;
+    if (blockIdx.x == 0 && tid == 0 && audio_len) audio_len[b] = n;
+
+    if (mv > m0) {
+        const int q0 = blockIdx.x * kSegs;
+        const int f_lo = max(0, q0 - 2), f_hi = min(Tb, (mv - 1 + kPad) / kHop + 1), nf = f_hi - f_lo;   // nf <= kSlots
+        const cf* tw2048 = reinterpret_cast<const cf*>(tables);
+        for (int i = tid; i < kTw; i += kThreads) tw[i] = tw2048[2 * i];
+        for (int i = tid; i < kNfft; i += kThreads) win[i] = tables[2 * 2048 + i];
+        __syncthreads();
+        cf* A = ping + g * kHalf;
+        for (int r = 0; r * kGroups < nf; ++r) {
+            const int fs = r * kGroups + g, f = f_lo + fs;            // slot and frame; fs >= nf: transformed, never read
+            const bool live = fs < nf;
+            cf* Bf = reinterpret_cast<cf*>(frames + fs * kNfft);
+            if (!kInit) {
+                const int i0 = f * kHop - kPad;                       // the frame's first sample
+                for (int m = lt; m < kHalf; m += kGT) {
+                    const int ia = i0 + 2 * m, ib = ia + 1;
+                    const float xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
+                    const float xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
+                    A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
+                }
+                __syncthreads();
+                fft<false, kGT, kTw>(A, Bf, kHalf, lt, tw);
+            }
+            const float* mf = mrow + (int64_t)f * kBins;
+            for (int k = lt; k <= 256; k += kGT) {
+                const int m = kHalf - k;
+                const float Mk = live ? mf[k] : 0.f, Mm = live ? mf[m] : 0.f;
+                cf xk, xm;
+                if (kInit) {
+                    xk = hashed_phase(Mk, seed, f, k);
+                    xm = k == 256 ? xk : hashed_phase(Mm, seed, f, m);
+                } else {
+                    xk = project(real_split(Bf, k, kHalf, tw[k]), Mk);
+                    xm = k == 256 ? xk : project(real_split(Bf, m, kHalf, tw[m]), Mm);
+                }
+                if (k == 0) {                                         // irfft drops the imaginary parts of DC and Nyquist
+                    xk.y = 0.f;
+                    xm.y = 0.f;
+                }
+                {   // Z_k
+                    const cf e = make_float2(xk.x + xm.x, xk.y - xm.y), d = make_float2(xk.x - xm.x, xk.y + xm.y);
+                    const cf o = ctw<true>(d, tw[k]);
+                    A[k] = make_float2(e.x - o.y, e.y + o.x);
+                }
+                if (k > 0 && k < 256) {   // Z_{512-k}
+                    const cf e = make_float2(xm.x + xk.x, xm.y - xk.y), d = make_float2(xm.x - xk.x, xm.y + xk.y);
+                    const cf o = ctw<true>(d, tw[m]);
+                    A[m] = make_float2(e.x - o.y, e.y + o.x);
+                }
+            }
+            __syncthreads();
+            fft<true, kGT, kTw>(A, Bf, kHalf, lt, tw);
+        }
+        // ---- window, overlap-add over the utterance's own frames, envelope division (frame order, no atomics)
+        for (int m = m0 + tid; m < mv; m += kThreads) {
+            const int u = m + kPad;                                   // position in the padded signal
+            const int fmin = u >= kNfft ? (u - kNfft) / kHop + 1 : 0, fmax = min(Tb - 1, u / kHop);
+            float acc = 0.f, env = 0.f;
+            for (int f = fmin; f <= fmax; ++f) {
+                const int j = u - f * kHop;
+                const float wj = win[j];
+                acc = fmaf(frames[(f - f_lo) * kNfft + j], wj, acc);
+                env = fmaf(wj, wj, env);
+            }
+            orow[m] = acc / env;
+        }
+    }
+    for (int m = mv + tid; m < m1; m += kThreads) orow[m] = 0.f;
+}
+
+template <typename TM>
+__global__ void __launch_bounds__(kMelThreads) mel_to_linear_kernel(const TM* __restrict__ mel, int64_t sb, int64_t sc, int64_t st,
+                                                                    const int64_t* __restrict__ mel_len,
+                                                                    const float* __restrict__ pinv_t, float* __restrict__ mag,
+                                                                    int64_t ldm, int n_mels, int T) {
+    __shared__ float e[kMaxMels][kMelFrames];
+    const int b = blockIdx.y, t0 = blockIdx.x * kMelFrames, tid = threadIdx.x;
+    const int nv = min(kMelFrames, valid_frames(mel_len, b, T) - t0);
+    if (nv <= 0) return;
+    const TM* mb = mel + (int64_t)b * sb;
+    for (int i = tid; i < n_mels * kMelFrames; i += kMelThreads) {
+        const int c = i / kMelFrames, j = i % kMelFrames;
+        e[c][j] = j < nv ? expf((float)mb[(int64_t)c * sc + (int64_t)(t0 + j) * st]) : 0.f;
+    }
+    __syncthreads();
+    float* ob = mag + (int64_t)b * ldm + (int64_t)t0 * kBins;
+    for (int k = tid; k < kBins; k += kMelThreads) {
+        float acc[kMelFrames];
+#pragma unroll
+        for (int j = 0; j < kMelFrames; ++j) acc[j] = 0.f;
+        for (int c = 0; c < n_mels; ++c) {
+            const float p = pinv_t[c * kBins + k];
+#pragma unroll
+            for (int j = 0; j < kMelFrames; ++j) acc[j] = fmaf(p, e[c][j], acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kMelFrames; ++j)
+            if (j < nv) ob[j * kBins + k] = fmaxf(acc[j], 0.f);
+    }
+}
+
+}  // namespace
+
+extern "C" int32_t ispk_griffinlim_tile_samples(void) { return kTile; }
+
+extern "C" int32_t ispk_mel_to_linear_f32(const void* mel, int32_t mel_f16, int64_t mel_sb, int64_t mel_sc, int64_t mel_st,
+                                          const int64_t* mel_len, const float* pinv_t, float* mag, int64_t ld_mag, int32_t B,
+                                          int32_t n_mels, int32_t T, ispk_stream_t stream) {
+    if (B == 0 || T == 0) return 0;
+    ISPK_REQUIRE(mel && pinv_t && mag, ISPK_E_NULL, "ispk_mel_to_linear_f32: null pointer");
+    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= kMaxFrames && n_mels >= 1 && n_mels <= kMaxMels, ISPK_E_SHAPE,
+                 "ispk_mel_to_linear_f32: bad shape B=%d n_mels=%d T=%d (B <= 65535, n_mels <= 128, T <= %d)", B, n_mels, T,
+                 kMaxFrames);
+    ISPK_REQUIRE(ld_mag >= (int64_t)T * kBins, ISPK_E_SHAPE,
+                 "ispk_mel_to_linear_f32: leading stride ld_mag=%lld shorter than T * 513 = %lld", (long long)ld_mag,
+                 (long long)T * kBins);
+    const dim3 grid((T + kMelFrames - 1) / kMelFrames, B);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (mel_f16)
+        hipLaunchKernelGGL(mel_to_linear_kernel<_Float16>, grid, dim3(kMelThreads), 0, s, static_cast<const _Float16*>(mel),
+                           mel_sb, mel_sc, mel_st, mel_len, pinv_t, mag, ld_mag, n_mels, T);
+    else
+        hipLaunchKernelGGL(mel_to_linear_kernel<float>, grid, dim3(kMelThreads), 0, s, static_cast<const float*>(mel), mel_sb,
+                           mel_sc, mel_st, mel_len, pinv_t, mag, ld_mag, n_mels, T);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_griffinlim_step_f32(const float* audio, int64_t ld_audio, const float* mag, int64_t ld_mag,
+                                            const int64_t* mel_len, const float* tables, float* out, int64_t ld_out,
+                                            int64_t* audio_len, int32_t B, int32_t T, int32_t mode, uint64_t seed,
+                                            ispk_stream_t stream) {
+    ISPK_REQUIRE(mode == ISPK_GRIFFINLIM_STEP || mode == ISPK_GRIFFINLIM_INIT, ISPK_E_UNSUPPORTED,
+                 "ispk_griffinlim_step_f32: mode %d (0 = step, 1 = init)", mode);
+    if (B == 0 || T == 0) return 0;
+    const bool init = mode == ISPK_GRIFFINLIM_INIT;
+    ISPK_REQUIRE((init || audio) && mag && tables && out, ISPK_E_NULL, "ispk_griffinlim_step_f32: null pointer");
+    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= kMaxFrames, ISPK_E_SHAPE,
+                 "ispk_griffinlim_step_f32: bad shape B=%d T=%d (B <= 65535, T <= %d)", B, T, kMaxFrames);
+    const int64_t S = (int64_t)T * kHop;
+    ISPK_REQUIRE((init || ld_audio >= S) && ld_out >= S && ld_mag >= (int64_t)T * kBins, ISPK_E_SHAPE,
+                 "ispk_griffinlim_step_f32: row strides ld_audio=%lld ld_out=%lld ld_mag=%lld shorter than the rows (T=%d)",
+                 (long long)ld_audio, (long long)ld_out, (long long)ld_mag, T);
+    ISPK_REQUIRE(init || out != audio, ISPK_E_SHAPE,
+                 "ispk_griffinlim_step_f32: out may not be audio (neighbouring tiles read the halo)");
+    const dim3 grid((unsigned)((S + kTile - 1) / kTile), B);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (init) {
+        ISPK_RESERVE_LDS(griffinlim_kernel<true>, kLds, "ispk_griffinlim_step_f32");
+        hipLaunchKernelGGL(griffinlim_kernel<true>, grid, dim3(kThreads), kLds, s, audio, ld_audio, mag, ld_mag, mel_len, tables,
+                           out, ld_out, audio_len, T, mix_seed(seed));
+    } else {
+        ISPK_RESERVE_LDS(griffinlim_kernel<false>, kLds, "ispk_griffinlim_step_f32");
+        hipLaunchKernelGGL(griffinlim_kernel<false>, grid, dim3(kThreads), kLds, s, audio, ld_audio, mag, ld_mag, mel_len,
+                           tables, out, ld_out, audio_len, T, mix_seed(seed));
+    }
+    return ispk_launch_status();
+}
