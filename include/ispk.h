@@ -1165,7 +1165,29 @@ int32_t ispk_denoise_f32(const float* audio, int64_t ld_audio, const int64_t* au
  *                             alignment requirement.  Refused: a mode other than the two (E_UNSUP); NULL mag, tables or out,
  *                             or NULL audio in mode STEP (E_NULL); B > 65535, T > 8388575, a row stride shorter than its
  *                             row, out == audio in mode STEP (the neighbouring tiles read the halo) (E_SHAPE).  B = 0 or
- *                             T = 0 is a no-op. */
+ *                             T = 0 is a no-op.
+ * ispk_griffinlim_fast_step_f32  one launch: mode STEP applied to x[i] = fma(-alpha, prev[i], audio[i]) for i in [0, n), the
+ *                             fast (momentum) iteration with alpha = momentum / (1 + momentum).  The textbook form takes the
+ *                             phase of STFT(x_n) - alpha STFT(x_{n-1}); the STFT is linear, so that is STFT(x_n - alpha
+ *                             x_{n-1}) and no spectrum is kept between launches.  prev is a second batch like audio at its own
+ *                             row stride ld_prev; nothing at or past n is read from either.  Everything else, the bit-identity
+ *                             guarantees included, is mode STEP's; ispk_griffinlim_step_f32 itself runs the code it ran
+ *                             before (the difference is a compile-time variant of the kernel).  Refused: NULL audio, prev,
+ *                             mag, tables or out (E_NULL); B > 65535, T > 8388575, a row stride (ld_prev included) shorter
+ *                             than its row, out == audio or out == prev (the neighbouring tiles read the halo), alpha
+ *                             outside [0, 1) or NaN (E_SHAPE).  B = 0 or T = 0 is a no-op.
+ * ispk_griffinlim_error_f32   two launches, no atomics: err[b] = || |X| - M ||_F / || M ||_F over the frames f < Tb and the
+ *                             513 bins, X the analysis of x = audio above (the spectral convergence).  The first launch (16
+ *                             frames per workgroup, each frame in exactly one) writes work[b][f] = (num_f, den_f) =
+ *                             (sum_k (sqrt(|X_f[k]|^2) - M_f[k])^2, sum_k M_f[k]^2) for f < Tb in fp32: per-thread partials over
+ *                             k = t, t + 128, .. in ascending k with fma, then a fixed tree; frames at or past Tb are not
+ *                             written.  The second (one workgroup per utterance) sums work[b][0 .. Tb) in float64 in a fixed
+ *                             order and writes err[b] = (float)sqrt(num / den); Tb = 0 gives 0, den = 0 gives 0 if num = 0
+ *                             and +inf otherwise.  work is fp32 [B][T][2] scratch at a row stride ld_work >= 2 T, err fp32
+ *                             [B], both device memory.  A frame's two numbers depend on (n, f) alone: a ragged batch gives
+ *                             each utterance the bits it gets alone.  Refused: NULL audio, mag, tables, work or err (E_NULL);
+ *                             B > 65535, T > 8388575, a row stride shorter than its row (E_SHAPE).  B = 0 or T = 0 is a
+ *                             no-op (err is not written). */
 #define ISPK_GRIFFINLIM_STEP 0
 #define ISPK_GRIFFINLIM_INIT 1
 int32_t ispk_griffinlim_tile_samples(void);
@@ -1175,6 +1197,12 @@ int32_t ispk_mel_to_linear_f32(const void* mel, int32_t mel_f16, int64_t mel_sb,
 int32_t ispk_griffinlim_step_f32(const float* audio, int64_t ld_audio, const float* mag, int64_t ld_mag,
                                  const int64_t* mel_len, const float* tables, float* out, int64_t ld_out, int64_t* audio_len,
                                  int32_t B, int32_t T, int32_t mode, uint64_t seed, ispk_stream_t stream);
+int32_t ispk_griffinlim_fast_step_f32(const float* audio, int64_t ld_audio, const float* prev, int64_t ld_prev, float alpha,
+                                      const float* mag, int64_t ld_mag, const int64_t* mel_len, const float* tables,
+                                      float* out, int64_t ld_out, int64_t* audio_len, int32_t B, int32_t T, ispk_stream_t stream);
+int32_t ispk_griffinlim_error_f32(const float* audio, int64_t ld_audio, const float* mag, int64_t ld_mag,
+                                  const int64_t* mel_len, const float* tables, float* work, int64_t ld_work, float* err,
+                                  int32_t B, int32_t T, ispk_stream_t stream);
 
 #ifdef __cplusplus
 }

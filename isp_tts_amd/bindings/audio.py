@@ -15,7 +15,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows", "hifigan_conv", "_hifigan_bn",
            "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa", "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT",
            "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
-           "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step"]
+           "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
+           "griffinlim_error"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -543,4 +544,68 @@ def griffinlim_step(audio: Optional[Tensor], mag: Tensor, mel_len: Optional[Tens
                 _rt.lib().ispk_griffinlim_step_f32, _rt._ptr(audio), 0 if audio is None else audio.stride(0), mag.data_ptr(),
                 mag.stride(0), ml, tables.data_ptr(), out.data_ptr(), out.stride(0), _rt._ptr(audio_len), B, T, mode, int(seed),
                 _rt._stream())
+    return out
+
+
+def griffinlim_fast_step(audio: Tensor, prev: Tensor, alpha: float, mag: Tensor, mel_len: Optional[Tensor], tables: Tensor,
+                         out: Tensor, audio_len: Optional[Tensor] = None) -> Tensor:
+    """ispk_griffinlim_fast_step_f32, one launch, no host read: griffinlim_step in mode GRIFFINLIM_STEP applied to audio - alpha
+    prev, the fast (momentum) iteration with alpha = momentum / (1 + momentum) in [0, 1).  The STFT is linear, so this is the
+    phase of STFT(audio) - alpha STFT(prev) without a spectrum in memory.  audio, prev and out are fp32 [B, 256 T] (unit stride
+    on the samples, any row stride), out neither of the inputs; nothing at or past 256 mel_len[b] is read from audio or prev."""
+    _rt._dev(audio, prev, mag, mel_len, tables, out, audio_len)
+    if mag.ndim != 3:
+        raise ValueError(f"magnitude: fp32 [B, T, 513], got {tuple(mag.shape)}")
+    B, T = mag.shape[:2]
+    _magnitude(mag, B, T)
+    S = T * GRIFFINLIM_HOP
+    _out_like("audio", audio, torch.float32, (B, S))
+    _out_like("prev", prev, torch.float32, (B, S))
+    _out_like("out", out, torch.float32, (B, S))
+    ml = _lengths_ptr(mel_len, B)
+    if audio_len is not None:
+        _out_like("audio_len", audio_len, torch.int64, (B,))
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= DENOISE_TABLE_FLOATS
+    if not 0.0 <= float(alpha) < 1.0:
+        raise ValueError(f"alpha {alpha}: momentum / (1 + momentum), in [0, 1)")
+    if B == 0 or T == 0:
+        return out
+    # griffinlim_step's count and bytes, with one more waveform read per sample
+    _rt._launch("griffinlim_kernel<fast>", B * T * (20.0 / 16.0) * (2 * 5.0 * 512 * 9 + 40.0 * 513) + 2.0 * B * S,
+                (12.0 + 4.0 * 513 / 256) * B * S, _rt.lib().ispk_griffinlim_fast_step_f32, audio.data_ptr(), audio.stride(0),
+                prev.data_ptr(), prev.stride(0), float(alpha), mag.data_ptr(), mag.stride(0), ml, tables.data_ptr(),
+                out.data_ptr(), out.stride(0), _rt._ptr(audio_len), B, T, _rt._stream())
+    return out
+
+
+def griffinlim_error(audio: Tensor, mag: Tensor, mel_len: Optional[Tensor], tables: Tensor, out: Optional[Tensor] = None,
+                     work: Optional[Tensor] = None) -> Tensor:
+    """ispk_griffinlim_error_f32, two launches, no host read, no atomics: the spectral convergence || |STFT(audio)| - mag ||_F /
+    || mag ||_F per utterance, over its mel_len[b] frames, in griffinlim_step's framing -> out fp32 [B].  0 for an utterance
+    without frames or with zero magnitude and zero audio, +inf for a zero magnitude under a non-zero spectrum.  work fp32
+    [B, T, 2] (contiguous frame rows): the per-frame sums, scratch."""
+    _rt._dev(audio, mag, mel_len, tables, out, work)
+    if mag.ndim != 3:
+        raise ValueError(f"magnitude: fp32 [B, T, 513], got {tuple(mag.shape)}")
+    B, T = mag.shape[:2]
+    _magnitude(mag, B, T)
+    _out_like("audio", audio, torch.float32, (B, T * GRIFFINLIM_HOP))
+    ml = _lengths_ptr(mel_len, B)
+    out = torch.empty((B,), dtype=torch.float32, device=mag.device) if out is None else out
+    _out_like("out", out, torch.float32, (B,))
+    work = torch.empty((B, T, 2), dtype=torch.float32, device=mag.device) if work is None else work
+    if (work.dtype != torch.float32 or tuple(work.shape) != (B, T, 2) or (T > 0 and tuple(work.stride()[1:]) != (2, 1))
+            or (B > 1 and T > 0 and work.stride(0) < 2 * T)):
+        raise ValueError(f"work: fp32 [{B}, {T}, 2] with contiguous frame rows, got {work.dtype} {tuple(work.shape)} strides "
+                         f"{tuple(work.stride())}")
+    assert tables.dtype == torch.float32 and tables.is_contiguous() and tables.numel() >= DENOISE_TABLE_FLOATS
+    if B == 0:
+        return out
+    if T == 0:
+        return _rt.zero_(out)
+    # per frame: one 512-point transform (9 radix passes of ~5 N flops) and ~20 flops for each of 513 bins; the pair is
+    # labelled by its first kernel (the second reads 8 B per frame)
+    _rt._launch("griffinlim_error_kernel", B * T * (5.0 * 512 * 9 + 20.0 * 513), (4.0 * 256 + 4.0 * 513 + 16.0) * B * T,
+                _rt.lib().ispk_griffinlim_error_f32, audio.data_ptr(), audio.stride(0), mag.data_ptr(), mag.stride(0), ml,
+                tables.data_ptr(), work.data_ptr(), work.stride(0), out.data_ptr(), B, T, _rt._stream())
     return out

@@ -3,7 +3,7 @@
 // (csrc/features.hip): n_fft = win = 1024, hop 256, periodic Hann, 384 zeros on both sides, no centring, so an utterance of
 // T frames has n = 256 T samples (include/ispk.h has the definition).
 //
-//   griffinlim_kernel<kInit>  grid (ceil(256 T / 4096), B), 512 threads = 4 groups of 128: denoise_kernel's geometry (denoise.hip)
+//   griffinlim_kernel<kInit, kFast>  grid (ceil(256 T / 4096), B), 512 threads = 4 groups of 128: denoise.hip's geometry
 //                    with the extractor's framing.  A workgroup writes 16 hop segments (4096 samples) of ONE utterance.  Sample
 //                    s takes frames floor((s + 384) / 256) - 3 .. floor((s + 384) / 256), so the tile at hop q0 needs the
 //                    up-to-20 frames q0 - 2 .. q0 + 17 within [0, T): the 4 frames it shares with its neighbours are
@@ -21,6 +21,19 @@
 //                    then per output sample the window-weighted overlap-add of its <= 4 frames and the division by the sum of
 //                    their w^2 (positive for every s < n and every T >= 1), both in ascending frame order.  Samples at or past
 //                    n are written as 0.  LDS: 80 KB of frame slots + 16 KB of ping buffers + 8 KB twiddles + 4 KB window.
+//                    griffinlim_kernel<false, true> is the fast (momentum) step: the step with a second input row `prev` and
+//                    a scalar alpha = momentum / (1 + momentum); its gather takes fma(-alpha, prev[i], x[i]) under the same
+//                    select and nothing else differs.  The textbook iteration takes the phase of STFT(x_n) - alpha STFT(x_{n-1});
+//                    the STFT is linear, so that is STFT(x_n - alpha x_{n-1}): one more waveform read per sample, no spectrum in
+//                    HBM, still one launch per iteration.  A compile-time variant: <false> and <true> keep their code.
+//   griffinlim_error_kernel  grid (ceil(T / 16), B), 512 threads: the spectral convergence's per-frame sums.  The analysis half of
+//                    the step - gather, window, forward FFT, real_split - of 16 frames, 4 at a time, one per group; a frame
+//                    belongs to one workgroup (no halo).  Thread t of the group accumulates (sqrt(|X[k]|^2) - M[k])^2 and M[k]^2
+//                    over k = t, t + 128, .. <= 512 with fma, then a fixed tree (shuffles within a wave, the group's two waves
+//                    through LDS) gives work[b][f] = (num_f, den_f), fp32, for f < Tb.  LDS: 32 KB ping + pong, 8 KB twiddles,
+//                    4 KB window, 64 B of partials.
+//   griffinlim_error_sum_kernel  grid B, 256 threads: float64 sums of work[b][0 .. Tb) (thread-strided in ascending f, then a
+//                    fixed tree in LDS), err[b] = (float)sqrt(num / den); 0 for Tb = 0, and with den = 0: 0 if num = 0, else +inf.
 //   mel_to_linear_kernel  grid (ceil(T / 8), B), 256 threads.  exp(mel) of 8 frames into LDS, then thread k accumulates
 //                    sum_m P[k][m] exp(mel[m][f]) for the 8 frames in ascending m (P is read transposed: lanes on k), clamps at 0.
 // A frame's arithmetic depends on (n, f, seed) alone and a sample's on (n, s) alone - not on the tile, on B, on T or on the
@@ -28,8 +41,11 @@
 // and graph replays repeat theirs.  LDS access patterns are denoise_kernel's (see there).
 //
 // gfx950 resources (csrc/resource_report.py griffinlim.hip; no spills, no scratch):
-//   griffinlim_kernel<false>  72 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
-//   griffinlim_kernel<true>   66 VGPRs, LDS 110,592 B dynamic
+//   griffinlim_kernel<false>        72 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
+//   griffinlim_kernel<true>         66 VGPRs, LDS 110,592 B dynamic
+//   griffinlim_kernel<false, true>  72 VGPRs, LDS 110,592 B dynamic
+//   griffinlim_error_kernel         58 VGPRs, LDS 45,120 B dynamic
+//   griffinlim_error_sum_kernel     14 VGPRs, LDS 4,096 B static
 //   mel_to_linear_kernel      60 VGPRs (fp32 and fp16 mel), LDS 4,096 B static
 #include <math.h>
 
@@ -83,8 +99,16 @@ __device__ __forceinline__ cf hashed_phase(float M, uint64_t seed, int f, int k)
     return make_float2(ms * c, ms * s);
 }
 
-template <bool kInit>
+// the fast step's sample: x[i] - alpha prev[i] inside [0, n), 0 elsewhere (a select: never an index outside the utterance, in
+// either row)
+__device__ __forceinline__ float fast_sample(const float* __restrict__ xrow, const float* __restrict__ prow, float alpha,
+                                             bool live, int i, int n) {
+    return live && i >= 0 && i < n ? fmaf(-alpha, prow[i], xrow[i]) : 0.f;
+}
+
+template <bool kInit, bool kFast = false>
 __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __restrict__ audio, int64_t lda,
+                                                              const float* __restrict__ prev, int64_t ldp, float alpha,
                                                               const float* __restrict__ mag, int64_t ldm,
                                                               const int64_t* __restrict__ mel_len,
                                                               const float* __restrict__ tables, float* __restrict__ out,
@@ -100,7 +124,9 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
     const int Tb = valid_frames(mel_len, b, T), n = Tb * kHop, S = T * kHop;
     const int m0 = blockIdx.x * kTile, m1 = min(S, m0 + kTile);
     const int mv = max(m0, min(n, m1));                               // [m0, mv) are the tile's samples inside the utterance
+    static_assert(!(kInit && kFast), "the initial waveform reads no audio");
     const float* xrow = kInit ? nullptr : audio + (int64_t)b * lda;
+    const float* prow = kFast ? prev + (int64_t)b * ldp : nullptr;
     const float* mrow = mag + (int64_t)b * ldm;
     float* orow = out + (int64_t)b * ldo;
     if (blockIdx.x == 0 && tid == 0 && audio_len) audio_len[b] = n;
@@ -121,8 +147,14 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
                 const int i0 = f * kHop - kPad;                       // the frame's first sample
                 for (int m = lt; m < kHalf; m += kGT) {
                     const int ia = i0 + 2 * m, ib = ia + 1;
-                    const float xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
-                    const float xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
+                    float xa, xb;
+                    if (kFast) {
+                        xa = fast_sample(xrow, prow, alpha, live, ia, n);
+                        xb = fast_sample(xrow, prow, alpha, live, ib, n);
+                    } else {
+                        xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
+                        xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
+                    }
                     A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
                 }
                 __syncthreads();
@@ -173,6 +205,98 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
         }
     }
     for (int m = mv + tid; m < m1; m += kThreads) orow[m] = 0.f;
+}
+
+// ---- spectral convergence: the analysis half of the step per frame, then one float64 sum per utterance
+constexpr int kErrFrames = 16;                     // frames per workgroup of griffinlim_error_kernel
+constexpr size_t kErrLds = sizeof(cf) * (kTw + 2 * kGroups * kHalf) + sizeof(float) * kNfft + sizeof(float2) * kGroups * 2;
+constexpr int kSumThreads = 256;
+
+__global__ void __launch_bounds__(kThreads) griffinlim_error_kernel(const float* __restrict__ audio, int64_t lda,
+                                                                    const float* __restrict__ mag, int64_t ldm,
+                                                                    const int64_t* __restrict__ mel_len,
+                                                                    const float* __restrict__ tables, float* __restrict__ work,
+                                                                    int64_t ldw, int T) {
+    extern __shared__ float4 lds_raw[];
+    cf* tw = reinterpret_cast<cf*>(lds_raw);                          // [kTw]
+    cf* ping = tw + kTw;                                              // [kGroups][512]
+    cf* pong = ping + kGroups * kHalf;                                // [kGroups][512]
+    float* win = reinterpret_cast<float*>(pong + kGroups * kHalf);    // [1024]
+    float2* part = reinterpret_cast<float2*>(win + kNfft);            // [kGroups][2]: one (num, den) per wave
+
+    const int b = blockIdx.y, tid = threadIdx.x, g = tid / kGT, lt = tid % kGT;
+    const int Tb = valid_frames(mel_len, b, T), n = Tb * kHop, f0 = blockIdx.x * kErrFrames;
+    if (f0 >= Tb) return;
+    const float* xrow = audio + (int64_t)b * lda;
+    const float* mrow = mag + (int64_t)b * ldm;
+    float* wrow = work + (int64_t)b * ldw;
+    const cf* tw2048 = reinterpret_cast<const cf*>(tables);
+    for (int i = tid; i < kTw; i += kThreads) tw[i] = tw2048[2 * i];
+    for (int i = tid; i < kNfft; i += kThreads) win[i] = tables[2 * 2048 + i];
+    __syncthreads();
+    cf *A = ping + g * kHalf, *Bf = pong + g * kHalf;
+    const int nf = min(kErrFrames, Tb - f0);
+    for (int r = 0; r * kGroups < nf; ++r) {
+        const int f = f0 + r * kGroups + g;
+        const bool live = f < Tb;                                     // a group past Tb transforms zeros and writes nothing
+        const int i0 = f * kHop - kPad;
+        for (int m = lt; m < kHalf; m += kGT) {
+            const int ia = i0 + 2 * m, ib = ia + 1;
+            const float xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
+            const float xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
+            A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
+        }
+        __syncthreads();
+        fft<false, kGT, kTw>(A, Bf, kHalf, lt, tw);
+        // thread-strided partials over the 513 bins in ascending k, then a fixed tree: lanes, then the group's two waves
+        const float* mf = mrow + (int64_t)f * kBins;
+        float num = 0.f, den = 0.f;
+        for (int k = lt; k < kBins; k += kGT) {
+            const cf X = real_split(Bf, k, kHalf, tw[k]);
+            const float M = live ? mf[k] : 0.f, d = sqrtf(X.x * X.x + X.y * X.y) - M;
+            num = fmaf(d, d, num);
+            den = fmaf(M, M, den);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            num += __shfl_down(num, off, 64);
+            den += __shfl_down(den, off, 64);
+        }
+        if (lt % 64 == 0) part[g * 2 + lt / 64] = make_float2(num, den);
+        __syncthreads();
+        if (live && lt == 0) {
+            const float2 p0 = part[g * 2], p1 = part[g * 2 + 1];
+            wrow[2 * (int64_t)f] = p0.x + p1.x;
+            wrow[2 * (int64_t)f + 1] = p0.y + p1.y;
+        }
+        // the next round's gather writes A, its barrier precedes the next write of `part`
+    }
+}
+
+__global__ void __launch_bounds__(kSumThreads) griffinlim_error_sum_kernel(const float* __restrict__ work, int64_t ldw,
+                                                                           const int64_t* __restrict__ mel_len,
+                                                                           float* __restrict__ err, int T) {
+    __shared__ double sn[kSumThreads], sd[kSumThreads];
+    const int b = blockIdx.x, tid = threadIdx.x, Tb = valid_frames(mel_len, b, T);
+    const float* wrow = work + (int64_t)b * ldw;
+    double num = 0.0, den = 0.0;
+    for (int f = tid; f < Tb; f += kSumThreads) {                     // ascending f per thread, then a fixed tree
+        num += (double)wrow[2 * (int64_t)f];
+        den += (double)wrow[2 * (int64_t)f + 1];
+    }
+    sn[tid] = num;
+    sd[tid] = den;
+    __syncthreads();
+    for (int s = kSumThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            sn[tid] += sn[tid + s];
+            sd[tid] += sd[tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double nu = sn[0], de = sd[0];
+        err[b] = de > 0.0 ? (float)sqrt(nu / de) : (nu == 0.0 ? 0.f : (float)(nu / de));   // den = 0: 0, or +inf (NaN stays NaN)
+    }
 }
 
 template <typename TM>
@@ -253,12 +377,53 @@ extern "C" int32_t ispk_griffinlim_step_f32(const float* audio, int64_t ld_audio
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (init) {
         ISPK_RESERVE_LDS(griffinlim_kernel<true>, kLds, "ispk_griffinlim_step_f32");
-        hipLaunchKernelGGL(griffinlim_kernel<true>, grid, dim3(kThreads), kLds, s, audio, ld_audio, mag, ld_mag, mel_len, tables,
-                           out, ld_out, audio_len, T, mix_seed(seed));
+        hipLaunchKernelGGL(griffinlim_kernel<true>, grid, dim3(kThreads), kLds, s, audio, ld_audio, (const float*)nullptr,
+                           (int64_t)0, 0.f, mag, ld_mag, mel_len, tables, out, ld_out, audio_len, T, mix_seed(seed));
     } else {
         ISPK_RESERVE_LDS(griffinlim_kernel<false>, kLds, "ispk_griffinlim_step_f32");
-        hipLaunchKernelGGL(griffinlim_kernel<false>, grid, dim3(kThreads), kLds, s, audio, ld_audio, mag, ld_mag, mel_len,
-                           tables, out, ld_out, audio_len, T, mix_seed(seed));
+        hipLaunchKernelGGL(griffinlim_kernel<false>, grid, dim3(kThreads), kLds, s, audio, ld_audio, (const float*)nullptr,
+                           (int64_t)0, 0.f, mag, ld_mag, mel_len, tables, out, ld_out, audio_len, T, mix_seed(seed));
     }
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_griffinlim_fast_step_f32(const float* audio, int64_t ld_audio, const float* prev, int64_t ld_prev,
+                                                 float alpha, const float* mag, int64_t ld_mag, const int64_t* mel_len,
+                                                 const float* tables, float* out, int64_t ld_out, int64_t* audio_len,
+                                                 int32_t B, int32_t T, ispk_stream_t stream) {
+    if (B == 0 || T == 0) return 0;
+    ISPK_REQUIRE(audio && prev && mag && tables && out, ISPK_E_NULL, "ispk_griffinlim_fast_step_f32: null pointer");
+    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= kMaxFrames, ISPK_E_SHAPE,
+                 "ispk_griffinlim_fast_step_f32: bad shape B=%d T=%d (B <= 65535, T <= %d)", B, T, kMaxFrames);
+    const int64_t S = (int64_t)T * kHop;
+    ISPK_REQUIRE(ld_audio >= S && ld_prev >= S && ld_out >= S && ld_mag >= (int64_t)T * kBins, ISPK_E_SHAPE,
+                 "ispk_griffinlim_fast_step_f32: row strides ld_audio=%lld ld_prev=%lld ld_out=%lld ld_mag=%lld shorter than "
+                 "the rows (T=%d)", (long long)ld_audio, (long long)ld_prev, (long long)ld_out, (long long)ld_mag, T);
+    ISPK_REQUIRE(out != audio && out != prev, ISPK_E_SHAPE,
+                 "ispk_griffinlim_fast_step_f32: out may not be audio or prev (neighbouring tiles read the halo)");
+    ISPK_REQUIRE(alpha >= 0.f && alpha < 1.f, ISPK_E_SHAPE, "ispk_griffinlim_fast_step_f32: alpha %g outside [0, 1)",
+                 (double)alpha);
+    const dim3 grid((unsigned)((S + kTile - 1) / kTile), B);
+    auto kernel = griffinlim_kernel<false, true>;
+    ISPK_RESERVE_LDS(kernel, kLds, "ispk_griffinlim_fast_step_f32");
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), kLds, reinterpret_cast<hipStream_t>(stream), audio, ld_audio, prev, ld_prev,
+                       alpha, mag, ld_mag, mel_len, tables, out, ld_out, audio_len, T, (uint64_t)0);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_griffinlim_error_f32(const float* audio, int64_t ld_audio, const float* mag, int64_t ld_mag,
+                                             const int64_t* mel_len, const float* tables, float* work, int64_t ld_work,
+                                             float* err, int32_t B, int32_t T, ispk_stream_t stream) {
+    if (B == 0 || T == 0) return 0;
+    ISPK_REQUIRE(audio && mag && tables && work && err, ISPK_E_NULL, "ispk_griffinlim_error_f32: null pointer");
+    ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= kMaxFrames, ISPK_E_SHAPE,
+                 "ispk_griffinlim_error_f32: bad shape B=%d T=%d (B <= 65535, T <= %d)", B, T, kMaxFrames);
+    ISPK_REQUIRE(ld_audio >= (int64_t)T * kHop && ld_mag >= (int64_t)T * kBins && ld_work >= 2 * (int64_t)T, ISPK_E_SHAPE,
+                 "ispk_griffinlim_error_f32: row strides ld_audio=%lld ld_mag=%lld ld_work=%lld shorter than the rows (T=%d)",
+                 (long long)ld_audio, (long long)ld_mag, (long long)ld_work, T);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(griffinlim_error_kernel, dim3((T + kErrFrames - 1) / kErrFrames, B), dim3(kThreads), kErrLds, s, audio,
+                       ld_audio, mag, ld_mag, mel_len, tables, work, ld_work, T);
+    hipLaunchKernelGGL(griffinlim_error_sum_kernel, dim3(B), dim3(kSumThreads), 0, s, work, ld_work, mel_len, err, T);
     return ispk_launch_status();
 }

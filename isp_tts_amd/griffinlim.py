@@ -16,11 +16,21 @@ the input.  An utterance of T = mel_len[b] frames has n = 256 T samples; with xp
 
 One call is one launch of ispk_mel_to_linear_f32, one of ispk_griffinlim_step_f32 in mode init and n_iter in mode step
 (csrc/griffinlim.hip; analysis, projection and synthesis of a 4,096-sample tile in one launch, nothing in HBM between them):
-no ATen compute, no host read, one stream, capturable with out=, and an utterance's samples do not depend on its batch.  Plain
-Griffin-Lim (momentum 0) is what the single-kernel iteration computes; the fast variant needs the previous complex spectrum.
+no ATen compute, no host read, one stream, capturable with out=, and an utterance's samples do not depend on its batch.
+
+GriffinLim is the plain iteration (momentum 0).  FastGriffinLim is the fast one (torchaudio's and librosa's default, momentum
+0.99): the textbook form keeps tprev = STFT(x_{n-1}) and takes the phase of STFT(x_n) - a tprev, a = momentum / (1 + momentum).
+The STFT is linear, so that is STFT(x_n - a x_{n-1}): the fast iteration is the same single-launch projection applied to
+x_n - a x_{n-1} (ispk_griffinlim_fast_step_f32: one more waveform read per sample, no spectrum in memory, one launch per
+iteration; in float64 the two forms agree to 3e-12 of the peak after 32 iterations).  With x_{-1} = 0 the first iteration is
+the plain step.  spectral_convergence() is || |STFT(x)| - M ||_F / || M ||_F per utterance on the device
+(ispk_griffinlim_error_f32, two launches, no atomics), capturable like the rest.
 
     gl = GriffinLim.from_features(feats).to("cuda")           # or GriffinLim(sample_rate=22050, n_mels=80, ...)
     audio, audio_len = gl(mel, mel_len)
+    fast = FastGriffinLim.from_features(feats, momentum=0.99).to("cuda")
+    audio, audio_len = fast(mel, mel_len)
+    sc = fast.spectral_convergence(audio, fast.magnitude(mel, mel_len), mel_len)      # fp32 [B]
 """
 from __future__ import annotations
 
@@ -49,7 +59,7 @@ def filterbank_pinv(fb) -> np.ndarray:
 class GriffinLim(torch.nn.Module):
     """`GriffinLim(sample_rate=22050, n_mels=80, f_min=0.0, f_max=8000.0, n_iter=32, seed=0)`: the filterbank is
     AcousticFeatures' for the same arguments.  n_fft, hop_length, win_length, window, momentum, mel_scale and norm are accepted
-    for compatibility; only 1024 / 256 / 1024, "hann", 0, "slaney" and "slaney" are built."""
+    for compatibility; only 1024 / 256 / 1024, "hann", 0, "slaney" and "slaney" are built (a momentum: FastGriffinLim)."""
 
     def __init__(self, sample_rate: int = 22050, n_mels: int = 80, f_min: float = 0.0, f_max: Optional[float] = 8000.0,
                  n_iter: int = 32, seed: int = 0, n_fft: int = N_FFT, hop_length: int = HOP, win_length: int = N_FFT,
@@ -62,8 +72,9 @@ class GriffinLim(torch.nn.Module):
                 raise NotImplementedError(f"{name} {got!r}: only {name} {want!r} is built (the feature extractor's STFT, "
                                           f"1024 / 256 / 1024 periodic Hann, and its slaney filterbank)")
         if float(momentum) != 0.0:
-            raise NotImplementedError(f"momentum {momentum}: plain Griffin-Lim (momentum 0) is built; the fast variant needs "
-                                      f"the previous complex spectrum")
+            raise NotImplementedError(f"momentum {momentum}: GriffinLim is the plain iteration (momentum 0); FastGriffinLim "
+                                      f"is the fast one (by linearity of the STFT, the same projection applied to x_n - a "
+                                      f"x_(n-1), a = momentum / (1 + momentum))")
         self.sample_rate, self.n_mels, self.hop_length = int(sample_rate), int(n_mels), HOP
         if not 1 <= self.n_mels <= 128:
             raise NotImplementedError(f"n_mels={n_mels}: 1 .. 128 mel channels are built")
@@ -98,13 +109,9 @@ class GriffinLim(torch.nn.Module):
             raise ValueError(f"mel: fp32 / fp16 [B, {self.n_mels}, T], got {mel.dtype} {tuple(mel.shape)}")
         return runtime.mel_to_linear(mel, mel_len, self.pinv_t, out=out)
 
-    def from_magnitude(self, mag: Tensor, mel_len: Optional[Tensor] = None, init: Optional[Tensor] = None,
-                       n_iter: Optional[int] = None, seed: Optional[int] = None,
-                       out: Optional[tuple[Tensor, Tensor]] = None) -> tuple[Tensor, Tensor]:
-        """The iteration on a given magnitude fp32 [B, T, 513] -> (audio fp32 [B, 256 T], audio_len = 256 mel_len).  `init`: a
-        waveform batch fp32 [B, 256 T] to start from in place of the hashed phase (n_iter >= 1; it is not modified).  The
-        iterations ping-pong between `out` and one scratch batch so that the last lands in `out`, whatever the parity of
-        n_iter; n_iter = 0 returns the initial waveform."""
+    def _iteration(self, mag, mel_len, init, n_iter, seed, out):
+        """from_magnitude's checked arguments -> (n_iter, seed, audio, audio_len); without frames audio_len is zeroed here and
+        nothing remains to launch."""
         self._on_gpu(mag, mel_len, init, *(out or ()))
         n_iter = self.n_iter if n_iter is None else _check_iter(n_iter)
         seed = self.seed if seed is None else _check_seed(seed)
@@ -114,10 +121,20 @@ class GriffinLim(torch.nn.Module):
         audio, audio_len = out if out is not None else self.empty_outputs(B, T, mag.device)
         if init is not None and n_iter == 0:
             raise ValueError("init with n_iter = 0: there is nothing to iterate")
-        if B == 0:
-            return audio, audio_len
-        if T == 0:
+        if B > 0 and T == 0:
             runtime.zero_(audio_len)
+        return n_iter, seed, audio, audio_len
+
+    def from_magnitude(self, mag: Tensor, mel_len: Optional[Tensor] = None, init: Optional[Tensor] = None,
+                       n_iter: Optional[int] = None, seed: Optional[int] = None,
+                       out: Optional[tuple[Tensor, Tensor]] = None) -> tuple[Tensor, Tensor]:
+        """The iteration on a given magnitude fp32 [B, T, 513] -> (audio fp32 [B, 256 T], audio_len = 256 mel_len).  `init`: a
+        waveform batch fp32 [B, 256 T] to start from in place of the hashed phase (n_iter >= 1; it is not modified).  The
+        iterations ping-pong between `out` and one scratch batch so that the last lands in `out`, whatever the parity of
+        n_iter; n_iter = 0 returns the initial waveform."""
+        n_iter, seed, audio, audio_len = self._iteration(mag, mel_len, init, n_iter, seed, out)
+        B, T = mag.shape[:2]
+        if B == 0 or T == 0:
             return audio, audio_len
         scratch = torch.empty((B, T * HOP), dtype=torch.float32, device=mag.device) if n_iter >= 1 else None
         # iterate i (0 = the initial waveform) lives in `audio` when n_iter - i is even
@@ -132,6 +149,14 @@ class GriffinLim(torch.nn.Module):
             cur = nxt
         return audio, audio_len
 
+    def spectral_convergence(self, audio: Tensor, mag: Tensor, mel_len: Optional[Tensor] = None,
+                             out: Optional[Tensor] = None) -> Tensor:
+        """|| |STFT(audio)| - mag ||_F / || mag ||_F per utterance over its mel_len frames, in the iteration's own framing:
+        audio fp32 [B, 256 T], mag fp32 [B, T, 513] -> fp32 [B].  0 for an utterance without frames; with an all-zero
+        magnitude, 0 under silence and +inf otherwise."""
+        self._on_gpu(audio, mag, mel_len, out)
+        return runtime.griffinlim_error(audio, mag, mel_len, self.tables, out=out)
+
     def forward(self, mel: Tensor, mel_len: Optional[Tensor] = None,
                 out: Optional[tuple[Tensor, Tensor]] = None) -> tuple[Tensor, Tensor]:
         """mel fp32 / fp16 [B, n_mels, T] on the GPU -> (audio fp32 [B, 256 T], audio_len int64 [B] = 256 mel_len)."""
@@ -142,6 +167,63 @@ class GriffinLim(torch.nn.Module):
     def infer(self, mel: Tensor) -> Tensor:
         """`gl.infer(mel)`: every utterance has all T frames; audio fp32 [B, 256 T]."""
         return self.forward(mel)[0]
+
+
+class FastGriffinLim(GriffinLim):
+    """`FastGriffinLim(..., momentum=0.99)`: GriffinLim's arguments and call surface, the fast iteration with 0 <= momentum < 1
+    (0: the plain iteration, bit for bit)."""
+
+    def __init__(self, *args, momentum: float = 0.99, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.momentum = _check_momentum(momentum)
+
+    @classmethod
+    def from_features(cls, features, n_iter: int = 32, seed: int = 0, momentum: float = 0.99) -> "FastGriffinLim":
+        return cls(sample_rate=features.sample_rate, n_mels=features.n_mels, n_iter=n_iter, seed=seed, momentum=momentum,
+                   _fb=features.fb)
+
+    def from_magnitude(self, mag: Tensor, mel_len: Optional[Tensor] = None, init: Optional[Tensor] = None,
+                       n_iter: Optional[int] = None, seed: Optional[int] = None,
+                       out: Optional[tuple[Tensor, Tensor]] = None, momentum: Optional[float] = None) -> tuple[Tensor, Tensor]:
+        """GriffinLim.from_magnitude with the fast iteration.  x_0 is the hashed start or `init` (not modified) and x_{-1} = 0:
+        iteration 1 is the plain step, iteration i >= 2 the fast step on (x_{i-1}, x_{i-2}).  The iterates rotate over `out`
+        and two scratch batches so that the last lands in `out` for every n_iter."""
+        momentum = self.momentum if momentum is None else _check_momentum(momentum)
+        if momentum == 0.0:
+            return super().from_magnitude(mag, mel_len, init=init, n_iter=n_iter, seed=seed, out=out)
+        n_iter, seed, audio, audio_len = self._iteration(mag, mel_len, init, n_iter, seed, out)
+        B, T = mag.shape[:2]
+        if B == 0 or T == 0:
+            return audio, audio_len
+        alpha = float(np.float32(momentum / (1.0 + momentum)))         # float64, rounded once
+        ring = [audio, None, None]                                        # iterate i lives in ring[(n_iter - i) % 3]
+
+        def slot(i):
+            j = (n_iter - i) % 3
+            if ring[j] is None:
+                ring[j] = torch.empty((B, T * HOP), dtype=torch.float32, device=mag.device)
+            return ring[j]
+
+        cur, prev = init, None
+        if init is None:
+            cur = slot(0)
+            runtime.griffinlim_step(None, mag, mel_len, self.tables, cur, audio_len=audio_len if n_iter == 0 else None,
+                                    mode=runtime.GRIFFINLIM_INIT, seed=seed)
+        for i in range(1, n_iter + 1):
+            nxt, last = slot(i), audio_len if i == n_iter else None
+            if i == 1:
+                runtime.griffinlim_step(cur, mag, mel_len, self.tables, nxt, audio_len=last)
+            else:
+                runtime.griffinlim_fast_step(cur, prev, alpha, mag, mel_len, self.tables, nxt, audio_len=last)
+            cur, prev = nxt, cur
+        return audio, audio_len
+
+
+def _check_momentum(momentum) -> float:
+    m = float(momentum)
+    if not 0.0 <= m < 1.0:
+        raise ValueError(f"momentum {momentum}: 0 <= momentum < 1")
+    return m
 
 
 def _check_iter(n_iter) -> int:
