@@ -415,6 +415,16 @@ int32_t ispk_infer_features_round_f32(const float* pred, const float* duration_t
                                       const float* pitch_target, const float* energy_target, float duration_factor,
                                       float pitch_factor, float pitch_delta, float energy_factor, float energy_delta,
                                       float* duration, float* features, int32_t B, int32_t L, ispk_stream_t stream);
+/* The same with one control set per utterance, read from the device: controls fp32 [B][5], row b = (duration_factor,
+ * pitch_factor, pitch_delta, energy_factor, energy_delta) of utterance b; `round` != 0 selects the hard-duration rounding.  A
+ * batch whose rows all equal the scalars gives the bits of the two entry points above.  frames_wanted int64 [B] (or NULL):
+ * the decoder length the regulator reports for duration[b][0, L) without a clamp - round == 0: (int64)(s + 0.5f), s the
+ * fp32 sum taken sequentially in token order (ispk_length_regulate_f32's soft path); round != 0: the sum over the row of
+ * (duration + 0.5f) truncated, 0 below 1 (ispk_hard_regulate_f32's repeats).  One workgroup per utterance. */
+int32_t ispk_infer_features_items_f32(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
+                                      const float* pitch_target, const float* energy_target, const float* controls,
+                                      int32_t round, float* duration, float* features, int64_t* frames_wanted, int32_t B,
+                                      int32_t L, ispk_stream_t stream);
 int32_t ispk_flow_mix_f32(const float* x0, const float* x1, const float* t, float sigma, float* x_t, float* flow, int32_t B,
                           int32_t L, int32_t C, ispk_stream_t stream);
 int32_t ispk_flow_finish_f32(const float* pred_raw, const float* flow, const float* x0, const uint8_t* mask, float* pred,
@@ -1129,6 +1139,36 @@ int32_t ispk_denoise_tile_samples(void);
 int32_t ispk_denoise_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables,
                          const float* bias, const float* strength_item, float strength, float* out, int64_t ld_out, int32_t B,
                          int32_t S, ispk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Document join (csrc/join.hip, isp_tts_amd/longform.py): the sentences of a padded batch put back together, per document
+ * and in reading order, with pauses, crossfades and fades - no host read.  All integers, `/` floors:
+ *   len_b = audio_len[b] if 0 <= audio_len[b] <= S else 0; (s_b, e_b) = (0, len_b), or with bounds [B][2] = (start, end):
+ *   s_b = clamp(start, 0, len_b), e_b = clamp(end, s_b, len_b); n_b = e_b - s_b.  Item b is valid when 0 <= doc[b] < D; the
+ *   valid items are ordered by (doc, pos, b), next(b) / prev(b) its neighbours in the same document.
+ *   ov_b = min(-pause[b], n_b / 2, n_next(b) / 2) when pause[b] < 0 and next(b) exists, else 0 (pause NULL: all 0);
+ *   adv_b = n_b + min(pause[b], S_out) when pause[b] >= 0, else n_b - ov_b; off_b = the sum of adv over the items before b
+ *   in its document, wanted_d the sum over all of them, doc_len_d = min(wanted_d, S_out).
+ *   tail t_b = ov_b if ov_b > 0 else min(fade, n_b / 2); head h_b = ov_prev(b) if that is > 0, else min(fade, n_b / 2);
+ *   w_b(i) = head(i) tail(i) in fp32, head(i) = (2 i + 1) / (2 h_b) for i < h_b else 1, tail(i) = (2 (n_b - 1 - i) + 1) /
+ *   (2 t_b) for i >= n_b - t_b else 1.
+ *   out[d][o] = sum over the items of d with off_b <= o < off_b + n_b, in document order (at most two), of
+ *   (g_b w_b(o - off_b)) audio[b][s_b + o - off_b] for o < doc_len_d (g_b = gain[b], 1 for NULL); 0 elsewhere below S_out.
+ * ispk_join_plan        one workgroup: ranks the items by counting, writes item_offset int64 [B] (off_b, -1 for a dropped
+ *                       item), item_len int64 [B] (n_b, 0 for a dropped item), doc_len and wanted_len int64 [D], and the plan
+ *                       (ispk_join_plan_bytes() bytes, 16-byte aligned) that ispk_join_f32 reads.  Integers only, no atomics.
+ *                       1 <= B, D <= 1024, 0 <= S, S_out < 2^31, 0 <= fade < 2^23.
+ * ispk_join_f32         grid (ceil(S_out / ispk_join_tile_samples()), D): gathers out fp32 [D][S_out] at ld_out from audio
+ *                       fp32 [B][S] at ld_audio.  Nothing at or past len_b is read, nothing at or past column S_out written.
+ * Both are pure functions of their inputs: a document's bits do not depend on the other documents or on the order of b. */
+int32_t ispk_join_tile_samples(void);
+int32_t ispk_join_plan_bytes(void);
+int32_t ispk_join_plan(const int64_t* audio_len, const int64_t* doc, const int64_t* pos, const int64_t* pause,
+                       const int64_t* bounds, void* plan, int64_t plan_bytes, int64_t* item_offset, int64_t* item_len,
+                       int64_t* doc_len, int64_t* wanted_len, int32_t B, int32_t S, int32_t D, int32_t S_out, int32_t fade,
+                       ispk_stream_t stream);
+int32_t ispk_join_f32(const float* audio, int64_t ld_audio, const float* gain, const void* plan, const int64_t* doc_len,
+                      float* out, int64_t ld_out, int32_t B, int32_t S, int32_t D, int32_t S_out, ispk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,

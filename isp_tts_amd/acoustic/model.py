@@ -295,8 +295,16 @@ class AcousticModel(nn.Module, Constructor):
               pitch_target: Optional[Tensor] = None, pitch_factor: float = 1.0, pitch_delta: float = 0.,
               pitch_normalize: bool = False, energy_target: Optional[Tensor] = None, steps: int = 4,
               speaker: Optional[Tensor] = None, *, flow_noise: Optional[Tensor] = None,
-              max_dec_len: Optional[int] = None):
-        """model.py:177-238: masks only for batch > 1 (:191-201, :228)."""
+              max_dec_len: Optional[int] = None, controls: Optional[Tensor] = None):
+        """model.py:177-238: masks only for batch > 1 (:191-201, :228).
+
+        `controls` fp32 [B, 5] on the model's device (longform.make_controls): per-utterance (duration_factor, pitch_factor,
+        pitch_delta, energy_factor, energy_delta), read on the device - see `FlowTemporalAdaptor.infer`.  The scalar controls
+        must then be at their defaults; with `pitch_normalize` only `pitch_target` is normalised, the pitch_delta column is
+        taken to be in normalised units already."""
+        if controls is not None and (duration_factor, pitch_factor, pitch_delta) != (1.0, 1.0, 0.0):
+            raise ValueError("infer: with `controls` the scalar controls stay at their defaults, got duration_factor="
+                             f"{duration_factor}, pitch_factor={pitch_factor}, pitch_delta={pitch_delta}")
         batch_infer = input_sequence.shape[0] > 1
         token_emb, enc_mask, handed = self._embed(input_sequence, text_lengths if batch_infer else None, want_mask=batch_infer)
         enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_lengths if batch_infer else None, handed=handed).out
@@ -310,7 +318,8 @@ class AcousticModel(nn.Module, Constructor):
             enc_out=enc_out, enc_mask=enc_mask, duration_target=duration_target, pitch_target=pitch_target,
             energy_target=energy_target, duration_factor=duration_factor, pitch_factor=pitch_factor,
             pitch_delta=pitch_delta, steps=steps, noise=flow_noise, max_dec_len=max_dec_len,
-            enc_len=text_lengths if batch_infer else None, qkv_for=self._decoder_first())
+            enc_len=text_lengths if batch_infer else None, qkv_for=self._decoder_first(),
+            **({} if controls is None else {"controls": controls}))
         dec_mask = adaptor_output.dec_mask if batch_infer else None
         dec_out = self.decoder(adaptor_output.enc_out, mask=dec_mask, key_len=adaptor_output.dec_lengths if batch_infer else None,
                                out_dtype=self.compute_dtype, handed=self._decoder_handed()).out

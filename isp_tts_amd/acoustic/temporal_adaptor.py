@@ -385,10 +385,20 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
               duration_factor: float = 1.0, pitch_target: Optional[Tensor] = None, pitch_factor: float = 1.0,
               pitch_delta: float = 0., energy_target: Optional[Tensor] = None, energy_factor: float = 1.0,
               energy_delta: float = 0., steps: int = 4, *, noise: Optional[Tensor] = None,
-              max_dec_len: Optional[int] = None, enc_len: Optional[Tensor] = None, qkv_for=None) -> TemporalAdaptorOutput:
+              max_dec_len: Optional[int] = None, enc_len: Optional[Tensor] = None, qkv_for=None,
+              controls: Optional[Tensor] = None) -> TemporalAdaptorOutput:
         """temporal_adaptor.py:331-408.  Durations stay fractional with soft_duration (:355-356) and are rounded without it;
         the embedding transformer gets NO mask even when batched (:384).  `max_dec_len` (optional) fixes the decoder length
-        without reading `dec_lens.max()` back to the host."""
+        without reading `dec_lens.max()` back to the host.
+
+        `controls` fp32 [B, 5] on the device: one (duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta) per
+        utterance in place of the scalars, which must then be at their defaults - read by the kernel, so one captured graph
+        serves every mix of them.  `self.frames_wanted` (int64 [B]) is then the decoder length each utterance asks for, while
+        `dec_lengths` is cut to `max_dec_len`: frames_wanted > max_dec_len says that an utterance was truncated."""
+        if controls is not None:
+            return self._infer_items(enc_out, enc_mask, duration_target, pitch_target, energy_target, controls, steps, noise,
+                                     max_dec_len, enc_len, qkv_for,
+                                     (duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta))
         m3 = enc_mask[..., None] if enc_mask is not None else None
         pred = self.predictor.infer(enc_out, mask=m3, steps=steps, noise=noise, key_len=enc_len)
         # :351-381 in ONE kernel: duration = clamp(duration_factor * (exp(pred[..., 0]) - 1), 0) with the given targets
@@ -413,6 +423,38 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
         # :388-397: soft path (generate_soft_path) and length regulation in one kernel
         enc_out, dec_lens = self.length_regulator(enc_out, duration_pred, alignment=None, enc_len=enc_lens,
                                                   frames=max_dec_len, qkv_for=qkv_for)
+        return TemporalAdaptorOutput(enc_out=enc_out, log_duration=None, duration=duration_pred, dec_lengths=dec_lens,
+                                     pitch=pitch.squeeze(-1), energy=energy.squeeze(-1), pitch_target=pitch_target,
+                                     energy_target=energy_target, dec_mask=self.length_regulator.dec_mask)
+
+    frames_wanted: Optional[Tensor] = None      # of the last `infer(controls=...)`, kept as `length_regulator.dec_mask` is
+
+    def _infer_items(self, enc_out, enc_mask, duration_target, pitch_target, energy_target, controls, steps, noise, max_dec_len,
+                     enc_len, qkv_for, scalars) -> TemporalAdaptorOutput:
+        """`infer` with per-utterance controls: ispk_infer_features_items_f32 in place of ispk_infer_features_f32, and the
+        regulators clamp the decoder lengths to `max_dec_len`."""
+        if tuple(float(v) for v in scalars) != (1.0, 1.0, 0.0, 1.0, 0.0):
+            raise ValueError("infer: with `controls` the scalar controls stay at their defaults (duration_factor, pitch_factor, "
+                             f"pitch_delta, energy_factor, energy_delta = 1, 1, 0, 1, 0), got {tuple(scalars)}")
+        if controls.dtype != torch.float32 or tuple(controls.shape) != (enc_out.shape[0], 5):
+            raise ValueError(f"controls: fp32 [{enc_out.shape[0]}, 5], got {controls.dtype} {tuple(controls.shape)}")
+        m3 = enc_mask[..., None] if enc_mask is not None else None
+        pred = self.predictor.infer(enc_out, mask=m3, steps=steps, noise=noise, key_len=enc_len)
+        duration_pred, feats, self.frames_wanted = runtime.infer_features_items(
+            pred, duration_target, pitch_target, energy_target, controls, round_duration=not self.soft_duration)
+        pitch, energy = feats[..., 0:1], feats[..., 1:2]
+        enc_out = self.embedding(feats, residual=enc_out)                                   # no mask, even batched (:384)
+        enc_lens = enc_len
+        if enc_lens is None and enc_mask is not None:
+            enc_lens = enc_mask.sum(dim=1)
+        if not self.soft_duration:
+            enc_out, dec_lens = self.length_regulator(enc_out, duration_pred, max_len=max_dec_len, alignment=None,
+                                                      frames=max_dec_len, hard=True)
+        else:
+            if max_dec_len is None:   # the output shape is data: read the longest decoder length back
+                max_dec_len = int(self.frames_wanted.max().item())
+            enc_out, dec_lens = self.length_regulator(enc_out, duration_pred, max_len=max_dec_len, alignment=None,
+                                                      enc_len=enc_lens, frames=max_dec_len, qkv_for=qkv_for)
         return TemporalAdaptorOutput(enc_out=enc_out, log_duration=None, duration=duration_pred, dec_lengths=dec_lens,
                                      pitch=pitch.squeeze(-1), energy=energy.squeeze(-1), pitch_target=pitch_target,
                                      energy_target=energy_target, dec_mask=self.length_regulator.dec_mask)

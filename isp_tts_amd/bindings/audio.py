@@ -16,7 +16,7 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa", "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT",
            "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
            "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
-           "griffinlim_error"]
+           "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -608,4 +608,49 @@ def griffinlim_error(audio: Tensor, mag: Tensor, mel_len: Optional[Tensor], tabl
     _rt._launch("griffinlim_error_kernel", B * T * (5.0 * 512 * 9 + 20.0 * 513), (4.0 * 256 + 4.0 * 513 + 16.0) * B * T,
                 _rt.lib().ispk_griffinlim_error_f32, audio.data_ptr(), audio.stride(0), mag.data_ptr(), mag.stride(0), ml,
                 tables.data_ptr(), work.data_ptr(), work.stride(0), out.data_ptr(), B, T, _rt._stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------ document join
+JOIN_TILE_SAMPLES = 4096      # ispk_join_tile_samples(): output samples of one document per workgroup
+JOIN_PLAN_BYTES = 36864       # ispk_join_plan_bytes(): what ispk_join_plan hands to ispk_join_f32
+JOIN_MAX = 1024               # items and documents per call
+JOIN_MAX_FADE = 1 << 23
+
+
+def join_plan(audio_len: Tensor, doc: Tensor, pos: Tensor, pause: Optional[Tensor], bounds: Optional[Tensor], plan: Tensor,
+              item_offset: Tensor, item_len: Tensor, doc_len: Tensor, wanted_len: Tensor, S: int, S_out: int, fade: int = 0) -> None:
+    """ispk_join_plan, one launch of one workgroup, no host read: orders the items of a batch by (doc, pos, b) and lays each
+    document out (include/ispk.h has the arithmetic).  int64 [B]: audio_len, doc, pos, pause (None: zeros), item_offset,
+    item_len; bounds int64 [B, 2] or None; int64 [D]: doc_len, wanted_len; plan: JOIN_PLAN_BYTES bytes of any dtype."""
+    _rt._dev(audio_len, doc, pos, pause, bounds, plan, item_offset, item_len, doc_len, wanted_len)
+    B, D = audio_len.shape[0], doc_len.shape[0]
+    for name, t in (("audio_len", audio_len), ("doc", doc), ("pos", pos), ("pause", pause), ("item_offset", item_offset),
+                    ("item_len", item_len)):
+        if t is not None:
+            _rt._out_like(name, t, torch.int64, (B,))
+    if bounds is not None:
+        _rt._out_like("bounds", bounds, torch.int64, (B, 2))
+        if not bounds.is_contiguous():
+            raise ValueError("bounds: contiguous int64 [B, 2]")
+    _rt._out_like("doc_len", doc_len, torch.int64, (D,))
+    _rt._out_like("wanted_len", wanted_len, torch.int64, (D,))
+    if not plan.is_contiguous() or plan.numel() * plan.element_size() < JOIN_PLAN_BYTES:
+        raise ValueError(f"plan: {JOIN_PLAN_BYTES} contiguous bytes, got {plan.numel() * plan.element_size()}")
+    _rt._launch("join_plan_kernel", 0.0, 48.0 * B + JOIN_PLAN_BYTES, _rt.lib().ispk_join_plan, audio_len.data_ptr(), doc.data_ptr(),
+                pos.data_ptr(), _rt._ptr(pause), _rt._ptr(bounds), plan.data_ptr(), plan.numel() * plan.element_size(),
+                item_offset.data_ptr(), item_len.data_ptr(), doc_len.data_ptr(), wanted_len.data_ptr(), B, int(S), D, int(S_out),
+                int(fade), _rt._stream())
+
+
+def join_audio(audio: Tensor, gain: Optional[Tensor], plan: Tensor, doc_len: Tensor, out: Tensor) -> Tensor:
+    """ispk_join_f32, one launch: gathers out fp32 [D, S_out] from audio fp32 [B, S] (unit stride on the samples, any row
+    stride, both) by the plan and document lengths that `join_plan` wrote; gain fp32 [B] or None."""
+    _rt._dev(audio, gain, plan, doc_len, out)
+    B, S = audio.shape
+    D, S_out = out.shape
+    if gain is not None:
+        _rt._out_like("gain", gain, torch.float32, (B,))
+    _rt._launch("join_kernel", 3.0 * D * S_out, 4.0 * (B * S + D * S_out), _rt.lib().ispk_join_f32, audio.data_ptr(), audio.stride(0),
+                _rt._ptr(gain), plan.data_ptr(), doc_len.data_ptr(), out.data_ptr(), out.stride(0), B, S, D, S_out, _rt._stream())
     return out

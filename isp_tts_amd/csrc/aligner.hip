@@ -17,6 +17,7 @@
 //     final mask into one pass, computing Sᵀ = K·Qᵀ on the fp32 MFMA so a lane owns one mel row and the row reductions
 //     are in-register.
 #include "common.h"
+#include "dec_len.h"
 
 namespace {
 
@@ -663,25 +664,85 @@ __global__ __launch_bounds__(256) void flow_euler_kernel(const float* __restrict
 //              reference fills only the negative entries of a target with predictions, :355-362)
 //   features = [ (pitch_target | pred[..., 1]) * pitch_factor + pitch_delta, (energy_target | pred[..., 2]) * ef + ed ]
 // kRound (hard durations, soft_duration off): the prediction is rounded half to even before the clamp, like torch.round (:355-357)
+// One token of both kernels below (one expression, one contraction setting: equal controls give equal bits): writes the two
+// features of token i and returns its duration.
+template <bool kRound>
+__device__ __forceinline__ float infer_features_token(const float* __restrict__ pred, const float* __restrict__ dur_f,
+                                                      const int64_t* __restrict__ dur_i, const float* __restrict__ pitch_t,
+                                                      const float* __restrict__ energy_t, float df, float pf, float pd, float ef,
+                                                      float ed, float* __restrict__ feats, int64_t i) {
+#pragma clang fp contract(off)
+    const float e = expf(pred[3 * i]) - 1.0f;
+    const float scaled = df * e;
+    float d = fmaxf(kRound ? rintf(scaled) : scaled, 0.0f);
+    if (dur_f) { const float t = dur_f[i]; d = t < 0.0f ? d : t; }
+    if (dur_i) { const int64_t t = dur_i[i]; d = t < 0 ? d : (float)t; }
+    const float p = pitch_t ? pitch_t[i] : pred[3 * i + 1], q = energy_t ? energy_t[i] : pred[3 * i + 2];
+    const float pm = p * pf, qm = q * ef;
+    feats[2 * i] = pm + pd;
+    feats[2 * i + 1] = qm + ed;
+    return d;
+}
+
 template <bool kRound>
 __global__ __launch_bounds__(256) void infer_features_kernel(const float* __restrict__ pred, const float* __restrict__ dur_f,
                                                              const int64_t* __restrict__ dur_i, const float* __restrict__ pitch_t,
                                                              const float* __restrict__ energy_t, float df, float pf, float pd,
                                                              float ef, float ed, float* __restrict__ duration,
                                                              float* __restrict__ feats, int64_t n) {
-#pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float e = expf(pred[3 * i]) - 1.0f;
-    const float scaled = df * e;
-    float d = fmaxf(kRound ? rintf(scaled) : scaled, 0.0f);
-    if (dur_f) { const float t = dur_f[i]; d = t < 0.0f ? d : t; }
-    if (dur_i) { const int64_t t = dur_i[i]; d = t < 0 ? d : (float)t; }
-    duration[i] = d;
-    const float p = pitch_t ? pitch_t[i] : pred[3 * i + 1], q = energy_t ? energy_t[i] : pred[3 * i + 2];
-    const float pm = p * pf, qm = q * ef;
-    feats[2 * i] = pm + pd;
-    feats[2 * i + 1] = qm + ed;
+    duration[i] = infer_features_token<kRound>(pred, dur_f, dur_i, pitch_t, energy_t, df, pf, pd, ef, ed, feats, i);
+}
+
+// The same with the five controls read per utterance from controls [B][5] on the device (a captured graph then serves any
+// mix of speeds and pitches), and frames_wanted[b]: the decoder length the regulator will report for these durations when
+// nothing clamps it - the soft regulator's sequential fp32 sum (glue.hip) or the hard one's repeats (hard_duration.hip),
+// through the functions they use (dec_len.h).  grid B, one workgroup per utterance: 256 threads write a chunk of durations
+// (to memory and to LDS), thread 0 continues the row's fp32 sum over the chunk in token order - an order that depends on (b, l)
+// alone; the hard regulator's repeats are integers, so every thread adds its own tokens' and the block adds those.
+// gfx950 (csrc/resource_report.py aligner.hip): 28 VGPRs soft, 26 rounded, LDS 4,096 B static (4,128 B rounded); no spills, no scratch.
+constexpr int kItemsChunk = 1024;
+template <bool kRound>
+__global__ __launch_bounds__(256) void infer_features_items_kernel(const float* __restrict__ pred, const float* __restrict__ dur_f,
+                                                                   const int64_t* __restrict__ dur_i,
+                                                                   const float* __restrict__ pitch_t,
+                                                                   const float* __restrict__ energy_t,
+                                                                   const float* __restrict__ controls, float* __restrict__ duration,
+                                                                   float* __restrict__ feats, int64_t* __restrict__ frames_wanted,
+                                                                   int L) {
+    __shared__ float dur_s[kItemsChunk];
+    __shared__ int64_t reps_s[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* c = controls + (int64_t)b * 5;
+    const float df = c[0], pf = c[1], pd = c[2], ef = c[3], ed = c[4];
+    float s = 0.f;
+    int64_t reps = 0;                                                      // (hard) this thread's share: integers, any order
+    for (int base = 0; base < L; base += kItemsChunk) {
+        const int n = L - base < kItemsChunk ? L - base : kItemsChunk;
+        for (int l = tid; l < n; l += 256) {
+            const int64_t i = (int64_t)b * L + base + l;
+            const float d = infer_features_token<kRound>(pred, dur_f, dur_i, pitch_t, energy_t, df, pf, pd, ef, ed, feats, i);
+            duration[i] = d;
+            dur_s[l] = d;
+            if constexpr (kRound) reps += hd_reps<true>(dur_s, nullptr, l);
+        }
+        if (!kRound && frames_wanted) {                                    // (uniform over the grid)
+            __syncthreads();
+            if (tid == 0) s = soft_dur_sum<false>(dur_s, n, s, nullptr);
+            __syncthreads();                                               // dur_s is rewritten by the next chunk
+        }
+    }
+    if (!frames_wanted) return;
+    if constexpr (kRound) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) reps += __shfl_xor(reps, off, 64);
+        if ((tid & 63) == 0) reps_s[tid >> 6] = reps;
+        __syncthreads();
+        if (tid == 0) frames_wanted[b] = reps_s[0] + reps_s[1] + reps_s[2] + reps_s[3];
+    } else {
+        if (tid == 0) frames_wanted[b] = soft_dec_len(s);
+    }
 }
 
 }  // namespace
@@ -901,4 +962,24 @@ extern "C" int32_t ispk_infer_features_round_f32(const float* pred, const float*
                                                  float* features, int32_t B, int32_t L, ispk_stream_t stream) {
     return infer_features_launch(pred, duration_target_f32, duration_target_i64, pitch_target, energy_target, duration_factor,
                                  pitch_factor, pitch_delta, energy_factor, energy_delta, duration, features, B, L, stream, true);
+}
+
+extern "C" int32_t ispk_infer_features_items_f32(const float* pred, const float* duration_target_f32,
+                                                 const int64_t* duration_target_i64, const float* pitch_target,
+                                                 const float* energy_target, const float* controls, int32_t round, float* duration,
+                                                 float* features, int64_t* frames_wanted, int32_t B, int32_t L,
+                                                 ispk_stream_t stream) {
+    ISPK_REQUIRE(pred && controls && duration && features, ISPK_E_NULL, "infer_features_items: null pointer");
+    ISPK_REQUIRE(!(duration_target_f32 && duration_target_i64), ISPK_E_UNSUPPORTED,
+                 "infer_features_items: one duration target at most");
+    ISPK_REQUIRE(B >= 0 && L >= 1, ISPK_E_SHAPE, "infer_features_items: bad shape B=%d L=%d", B, L);
+    if (B == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (round)
+        hipLaunchKernelGGL(infer_features_items_kernel<true>, dim3(B), dim3(256), 0, s, pred, duration_target_f32,
+                           duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
+    else
+        hipLaunchKernelGGL(infer_features_items_kernel<false>, dim3(B), dim3(256), 0, s, pred, duration_target_f32,
+                           duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
+    return ispk_launch_status();
 }

@@ -3,6 +3,7 @@
 // soft path generated on the fly) with the decoder lengths and mask.  In the reference each is a handful of ATen
 // element-wise launches or a library bmm; here every one is a single launch on the caller's stream.
 #include "common.h"
+#include "dec_len.h"
 
 namespace {
 
@@ -328,19 +329,16 @@ __device__ __forceinline__ void length_regulate_body(const float* __restrict__ a
             for (int t = lane; t < dur_cols; t += 64) s += dur_i[(int64_t)b * dur_cols + t];
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            dl = (int64_t)((float)s + 0.5f);
+            dl = soft_dec_len((float)s);
         } else {
-            // sequential fp32 sum in index order (what a CPU reduction over <= a few hundred values does); lane 0 only
+            // sequential fp32 sum in index order (soft_dur_sum, dec_len.h); lane 0 only
             float s = 0.f;
             if (lane == 0) {
                 cum[0] = 0.f;
-                for (int t = 0; t < L; ++t) {
-                    s += dur_f[(int64_t)b * L + t];
-                    cum[t + 1] = s;
-                }
+                s = soft_dur_sum<true>(dur_f + (int64_t)b * L, L, 0.f, cum);
             }
             s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s)));
-            dl = (int64_t)(s + 0.5f);
+            dl = soft_dec_len(s);
         }
         if (max_len >= 0 && dl > max_len) dl = max_len;
         if (lane == 0) {

@@ -7,27 +7,14 @@
 // All three need the running sums of one utterance's repeats (L <= 512, MAS's limit): every workgroup scans them into LDS for
 // itself - 100 .. 512 integers, cheaper than a launch of its own with a workspace.
 #include "common.h"
+#include "dec_len.h"
 
 namespace {
 
 constexpr int kHdMaxL = 512;
 constexpr int kHdThreads = 256;
 constexpr int kHdRows = 32;                 // frames per workgroup of the regulator: 8 per wave
-constexpr int64_t kHdRepMax = 1 << 30;      // one token's repeats are cut here (sums of 512 of them stay inside int64 by far)
-
-// reps of token l.  kRound: the regulator's (float(dur) + 0.5) truncated (:423); otherwise the plain integer duration (the
-// averager's cumsum, :451).  Negative and NaN durations - outside both operators' domain - count as 0, so that every index
-// derived from the sums stays inside the arrays.
-template <bool kRound>
-__device__ __forceinline__ int64_t hd_reps(const float* __restrict__ dur_f, const int64_t* __restrict__ dur_i, int64_t idx) {
-#pragma clang fp contract(off)
-    if (dur_f || kRound) {
-        const float f = (dur_f ? dur_f[idx] : (float)dur_i[idx]) + (kRound ? 0.5f : 0.0f);
-        return f >= 1.0f ? (int64_t)fminf(f, (float)kHdRepMax) : 0;       // (NaN compares false)
-    }
-    const int64_t d = dur_i[idx];
-    return d < 0 ? 0 : (d > kHdRepMax ? kHdRepMax : d);
-}
+// (kHdRepMax, hd_reps: dec_len.h)
 
 // cum[l] = reps[0] + .. + reps[l] (inclusive), cut at INT32_MAX for the frame searches; returns the full sum.  256 threads,
 // 256 tokens per trip: a shuffle scan inside each wave, the four wave totals through LDS, the carry in a register.

@@ -1,4 +1,8 @@
-"""Prints VGPR / spill / occupancy per kernel (hipcc -Rpass-analysis=kernel-resource-usage), one line each."""
+"""Prints VGPR / spill / occupancy per kernel (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
+
+    python isp_tts_amd/csrc/resource_report.py                          # every .hip file here
+    python isp_tts_amd/csrc/resource_report.py join.hip aligner.hip     # the files named (e.g. the long-form kernels)
+"""
 import os
 import re
 import subprocess

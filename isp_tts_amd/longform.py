@@ -1,0 +1,225 @@
+"""Long-form synthesis: texts longer than one sentence, from the text to 16-bit PCM in ONE captured HIP graph.
+
+The caller splits a text into sentences and buckets them; a bucket runs as a batch sorted for speed, not for reading.  Three
+pieces put the documents back together on the device, with no host read:
+
+    controls = make_controls(B, duration_factor=[1.0, 0.9, ...], pitch_delta=..., device=dev)   # one row per sentence
+    mel, ao = model.infer(text, text_lengths=tl, controls=controls, max_dec_len=M, ...)         # read by the kernel
+    r = join(audio, audio_len, doc, pos, pause, num_docs=D, out_samples=S_out, fade=64)          # r["audio"] fp32 [D, S_out]
+
+and `Synthesizer` captures the whole chain - infer, vocoder, optional denoiser and trim, join, optional document loudness,
+PCM16 - over static buffers.  The join (csrc/join.hip; include/ispk.h has the arithmetic) orders the valid items by
+(doc, pos, b), puts `pause[b]` samples of silence behind item b or - negative - crossfades it with its successor over
+min(-pause, n / 2, n_next / 2) samples with weights that add up to one, and fades the remaining edges over `fade` samples.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Union
+
+import torch
+from torch import Tensor
+
+from . import graph, runtime
+from .data.condition import AudioConditioner, to_pcm16
+
+CONTROL_NAMES = ("duration_factor", "pitch_factor", "pitch_delta", "energy_factor", "energy_delta")
+
+
+def make_controls(B: int, duration_factor: Union[float, Sequence[float]] = 1.0, pitch_factor: Union[float, Sequence[float]] = 1.0,
+                  pitch_delta: Union[float, Sequence[float]] = 0.0, energy_factor: Union[float, Sequence[float]] = 1.0,
+                  energy_delta: Union[float, Sequence[float]] = 0.0, *, pitch_std: Optional[float] = None, device=None) -> Tensor:
+    """fp32 [B, 5] for `infer(controls=)`: each argument a scalar or a sequence of B values.  `pitch_std` divides the
+    pitch_delta column, as `infer(pitch_normalize=True)` does for the scalar."""
+    cols = []
+    for name, v in zip(CONTROL_NAMES, (duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta)):
+        col = torch.as_tensor(v, dtype=torch.float64).detach().cpu()
+        if col.ndim == 0:
+            col = col.expand(B)
+        if tuple(col.shape) != (B,):
+            raise ValueError(f"{name}: a scalar or {B} values, got shape {tuple(col.shape)}")
+        cols.append(col)
+    if pitch_std is not None:
+        cols[2] = cols[2] / float(pitch_std)
+    return torch.stack(cols, dim=1).to(dtype=torch.float32, device=device)
+
+
+def join_outputs(num_docs: int, out_samples: int, B: int, device) -> dict:
+    """The tensors `join` fills, for a caller that keeps them (a graph capture)."""
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)      # noqa: E731
+    return dict(audio=e((num_docs, out_samples), torch.float32), audio_len=e((num_docs,), torch.int64),
+                wanted_len=e((num_docs,), torch.int64), item_offset=e((B,), torch.int64), item_len=e((B,), torch.int64),
+                plan=e((runtime.JOIN_PLAN_BYTES // 8,), torch.int64))
+
+
+def join(audio: Tensor, audio_len: Tensor, doc: Tensor, pos: Tensor, pause: Optional[Tensor] = None, *, num_docs: int,
+         out_samples: int, bounds: Optional[Tensor] = None, gain: Optional[Tensor] = None, fade: int = 0,
+         out: Optional[dict] = None) -> dict:
+    """Two launches (ispk_join_plan, ispk_join_f32), no ATen compute op, no host read.  On the device: audio fp32 [B, S] (unit
+    stride on S, any row stride), int64 [B] audio_len, doc (document of each item; outside [0, num_docs) drops the item), pos
+    (reading position inside the document) and pause (samples behind the item, negative: overlap with the next one; None: 0);
+    optional bounds int64 [B, 2] and gain fp32 [B] (an AudioConditioner's).  1 <= B, num_docs <= 1024, 0 <= fade < 2^23.
+    -> dict(audio fp32 [num_docs, out_samples], audio_len, wanted_len int64 [num_docs], item_offset (-1: dropped), item_len
+    int64 [B]); `out` (join_outputs) supplies them.  wanted_len > out_samples says that a document was cut."""
+    for t in (audio, audio_len, doc, pos, pause, bounds, gain):
+        if t is not None and not t.is_cuda:
+            raise runtime.IspkError("join needs GPU tensors; there is no CPU fallback")
+    if audio.ndim != 2 or audio.dtype != torch.float32 or (audio.shape[1] > 1 and audio.stride(1) != 1):
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    D, S_out = int(num_docs), int(out_samples)
+    if not (1 <= B <= runtime.JOIN_MAX and 1 <= D <= runtime.JOIN_MAX):
+        raise ValueError(f"join: 1 .. {runtime.JOIN_MAX} items and documents per call, got B={B}, num_docs={D}")
+    if not (0 <= S < 2 ** 31 and 0 <= S_out < 2 ** 31):
+        raise ValueError(f"join: S={S}, out_samples={S_out}: both below 2^31")
+    if int(fade) != fade or not 0 <= fade < runtime.JOIN_MAX_FADE:
+        raise ValueError(f"fade is an integer in [0, 2^23), got {fade!r}")
+    if B > 1 and audio.stride(0) < S:
+        raise ValueError(f"audio: rows overlap (row stride {audio.stride(0)} < {S})")
+    if out is None:
+        out = join_outputs(D, S_out, B, audio.device)
+    if out["audio"].ndim != 2:
+        raise ValueError(f"out['audio']: fp32 [{D}, {S_out}], got {tuple(out['audio'].shape)}")
+    runtime._out_like("out['audio']", out["audio"], torch.float32, (D, S_out))
+    if D > 1 and out["audio"].stride(0) < S_out:
+        raise ValueError(f"out['audio']: rows overlap (row stride {out['audio'].stride(0)} < {S_out})")
+    runtime.join_plan(audio_len, doc, pos, pause, bounds, out["plan"], out["item_offset"], out["item_len"], out["audio_len"],
+                      out["wanted_len"], S, S_out, int(fade))
+    runtime.join_audio(audio, gain, out["plan"], out["audio_len"], out["audio"])
+    return out
+
+
+class SynthesisResult(dict):
+    """The static outputs of a `Synthesizer` call (overwritten by the next one), and `truncated`: frames_wanted > frames, a
+    device comparison made when it is read - not part of the graph."""
+
+    def __init__(self, values: dict, frames: int):
+        super().__init__(values)
+        self._frames = frames
+
+    def __getitem__(self, key):
+        if key == "truncated":
+            return self["frames_wanted"] > self._frames
+        return super().__getitem__(key)
+
+    @property
+    def truncated(self) -> Tensor:
+        return self["truncated"]
+
+
+class Synthesizer:
+    """Text to PCM16 documents as ONE captured HIP graph over static buffers:
+
+        syn = Synthesizer(model, vocoder, batch=B, tokens=L, frames=M, docs=D, doc_samples=S_out, fade=64)
+        r = syn(text, text_len, doc, pos, pause, controls)      # r["pcm"] int16 [D, S_out], r["audio_len"], r["truncated"], ...
+
+    Stages: model.infer(controls=, max_dec_len=M) -> vocoder(mel, dec_lengths) -> denoiser (optional) -> the measure pass of
+    `item_conditioner` (optional: its bounds and gain go straight into the join, the per-item apply pass is not run) -> join ->
+    `doc_conditioner` on the joined documents (optional: document-level loudness) -> to_pcm16.  A call copies its arguments
+    into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
+    one Synthesizer serves one bucket shape (B sentences of L tokens into D documents of S_out samples)."""
+
+    def __init__(self, model, vocoder, *, batch: int, tokens: int, frames: int, docs: int, doc_samples: int, steps: int = 4,
+                 denoiser=None, item_conditioner: Optional[AudioConditioner] = None,
+                 doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0):
+        B, L, M, D, S_out = int(batch), int(tokens), int(frames), int(docs), int(doc_samples)
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise runtime.IspkError("Synthesizer needs the model on the GPU; there is no CPU fallback")
+        if not (1 <= B <= runtime.JOIN_MAX and 1 <= D <= runtime.JOIN_MAX and L >= 1 and M >= 1 and 1 <= S_out < 2 ** 31):
+            raise ValueError(f"Synthesizer: batch={B}, tokens={L}, frames={M}, docs={D}, doc_samples={S_out}")
+        self.model, self.vocoder, self.denoiser = model, vocoder, denoiser
+        self.item_conditioner, self.doc_conditioner = item_conditioner, doc_conditioner
+        self.batch, self.tokens, self.frames, self.docs, self.doc_samples, self.steps = B, L, M, D, S_out, int(steps)
+        self.fade, self.dither, self.seed = int(fade), bool(dither), int(seed)
+        self.multi_speaker = getattr(model, "speaker_embedding", None) is not None
+        i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)      # noqa: E731
+        self.static = {"text": i64(B, L), "text_len": torch.full((B,), L, dtype=torch.int64, device=dev), "doc": i64(B),
+                       "pos": torch.arange(B, dtype=torch.int64, device=dev), "pause": i64(B),
+                       "controls": make_controls(B, device=dev), "flow_noise": torch.randn(B, L, 3, device=dev)}
+        if self.multi_speaker:
+            self.static["speaker"] = i64(B)
+        self._wav = vocoder.empty_outputs(B, M, dev)
+        S = self._wav[0].shape[1]
+        self._clean = torch.empty_like(self._wav[0]) if denoiser is not None else None
+        self._item = None
+        if item_conditioner is not None:
+            self._item = dict(bounds=torch.empty((B, 2), dtype=torch.int64, device=dev),
+                              loudness=torch.empty((B,), dtype=torch.float64, device=dev),
+                              peak=torch.empty((B,), dtype=torch.float32, device=dev),
+                              gain=torch.empty((B,), dtype=torch.float32, device=dev))
+            item_conditioner.device_tables(dev)
+        self._joined = join_outputs(D, S_out, B, dev)
+        self._doc = None
+        if doc_conditioner is not None:
+            self._doc = doc_conditioner.empty_outputs(D, S_out, dev)
+            doc_conditioner.device_tables(dev)
+        self._pcm = torch.empty((D, S_out), dtype=torch.int16, device=dev)
+        self._graph = graph.GraphedCall(self._chain)
+        self.out = self._graph.out
+
+    def _chain(self) -> dict:
+        """One eager pass over the static buffers: what the graph replays (and what a test compares a replay against)."""
+        s = self.static
+        with torch.no_grad():
+            mel, ao = self.model.infer(s["text"], text_lengths=s["text_len"], steps=self.steps, speaker=s.get("speaker"),
+                                       flow_noise=s["flow_noise"], max_dec_len=self.frames, controls=s["controls"])
+            frames_wanted = self.model.temporal_adaptor.frames_wanted
+            audio, audio_len = self.vocoder(mel, ao.dec_lengths, out=self._wav)
+            if self.denoiser is not None:
+                audio, _ = self.denoiser(audio, audio_len, out=self._clean)
+            bounds = gain = None
+            if self.item_conditioner is not None:
+                c, o = self.item_conditioner, self._item
+                runtime.audio_measure(audio, audio_len, c.device_tables(audio.device), c.sample_rate, c.trim_mode, c.trim_threshold,
+                                      c.pad_frames, int(c.target_lufs is not None), c.target_lufs if c.target_lufs is not None else 0.0,
+                                      c.peak_limit, o["bounds"], o["loudness"], o["peak"], o["gain"])
+                bounds, gain = o["bounds"], o["gain"]
+            j = join(audio, audio_len, s["doc"], s["pos"], s["pause"], num_docs=self.docs, out_samples=self.doc_samples,
+                     bounds=bounds, gain=gain, fade=self.fade, out=self._joined)
+            doc_audio, doc_len = j["audio"], j["audio_len"]
+            if self.doc_conditioner is not None:
+                r = self.doc_conditioner(doc_audio, doc_len, out=self._doc)
+                doc_audio, doc_len = r["audio"], r["audio_len"]
+            pcm = to_pcm16(doc_audio, doc_len, dither=self.dither, seed=self.seed, out=self._pcm)
+        return dict(pcm=pcm, audio=doc_audio, audio_len=doc_len, wanted_len=j["wanted_len"], item_offset=j["item_offset"],
+                    item_len=j["item_len"], frames_wanted=frames_wanted, dec_lengths=ao.dec_lengths)
+
+    def _checked(self, name: str, t: Tensor) -> Tensor:
+        want = self.static[name]
+        if not isinstance(t, Tensor):
+            raise ValueError(f"{name}: a tensor {tuple(want.shape)} {want.dtype}")
+        if not t.is_cuda:
+            raise runtime.IspkError(f"Synthesizer needs GPU tensors ({name} is on the CPU); there is no CPU fallback")
+        if tuple(t.shape) != tuple(want.shape) or t.dtype != want.dtype:
+            raise ValueError(f"{name}: the captured bucket takes {want.dtype} {tuple(want.shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    def __call__(self, text: Tensor, text_len: Tensor, doc: Tensor, pos: Tensor, pause: Optional[Tensor] = None,
+                 controls: Optional[Tensor] = None, speaker: Optional[Tensor] = None,
+                 flow_noise: Optional[Tensor] = None) -> SynthesisResult:
+        given = {"text": text, "text_len": text_len, "doc": doc, "pos": pos}
+        for name, t in (("pause", pause), ("controls", controls), ("flow_noise", flow_noise)):
+            if t is not None:
+                given[name] = t
+        if speaker is not None:
+            if not self.multi_speaker:
+                raise ValueError("speaker: the model has no speaker table")
+            given["speaker"] = speaker
+        for name, t in given.items():
+            self._checked(name, t)
+        for name, t in given.items():
+            self.static[name].copy_(t)
+        if pause is None:
+            self.static["pause"].zero_()
+        if controls is None:
+            self.static["controls"].copy_(self._default_controls())
+        if flow_noise is None:
+            self.static["flow_noise"].normal_()
+        return SynthesisResult(self._graph.replay(), self.frames)
+
+    def _default_controls(self) -> Tensor:
+        d = getattr(self, "_defaults", None)
+        if d is None:
+            d = self._defaults = make_controls(self.batch, device=self.static["controls"].device)
+        return d
