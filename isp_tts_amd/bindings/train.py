@@ -163,16 +163,23 @@ def masked_instnorm_bwd(y: Tensor, d_out: Tensor, weight: Tensor, lengths: Tenso
     return d_y, dw, db
 
 
-def soft_average_bwd(attn_soft: Tensor, pitch: Tensor, energy: Tensor, d_feats: Tensor, text_len: Tensor) -> Tensor:
-    """ispk_soft_average_bwd_f32 -> d attn_soft [B, M, L]."""
-    _rt._dev(attn_soft, pitch, energy, d_feats, text_len)
+def soft_average_bwd(attn_soft: Tensor, pitch: Tensor, energy: Tensor, d_feats: Tensor, text_len: Tensor,
+                     out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """ispk_soft_average_bwd_f32 -> d attn_soft [B, M, L].  `out`: written in place (contiguous fp32 [B, M, L]); with `accumulate`
+    the gradient is added to what `out` holds."""
+    _rt._dev(attn_soft, pitch, energy, d_feats, text_len, out)
     B, M, L = attn_soft.shape
-    d = torch.empty_like(attn_soft)
+    if out is None:
+        assert not accumulate, "soft_average_bwd: accumulate needs `out`"
+        d = torch.empty_like(attn_soft)
+    else:
+        assert out.shape == (B, M, L) and out.dtype == torch.float32 and out.is_contiguous()
+        d = out
     ws = _rt.workspace(attn_soft.device, 3 * B * L)
     _rt._launch("soft_average_bwd_kernels", 0.0, 4.0 * attn_soft.numel() * 3, _rt.lib().ispk_soft_average_bwd_f32,
                 attn_soft.contiguous().data_ptr(), pitch.float().contiguous().data_ptr(), energy.float().contiguous().data_ptr(),
                 d_feats.float().contiguous().data_ptr(), _rt._i64(text_len).data_ptr(), ws.data_ptr(), ws.numel(),
-                d.data_ptr(), 0, B, M, L, _rt._stream())
+                d.data_ptr(), int(bool(accumulate)), B, M, L, _rt._stream())
     return d
 
 
