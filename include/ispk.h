@@ -1170,6 +1170,44 @@ int32_t ispk_join_plan(const int64_t* audio_len, const int64_t* doc, const int64
 int32_t ispk_join_f32(const float* audio, int64_t ld_audio, const float* gain, const void* plan, const int64_t* doc_len,
                       float* out, int64_t ld_out, int32_t B, int32_t S, int32_t D, int32_t S_out, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Speech marks (csrc/marks.hip, isp_tts_amd/longform.py): where every token and word of item b lies, in samples of the item's
+ * own audio or - with the join group - of its joined document.  One launch, one workgroup per item, integers out, no host read.
+ * duration fp32 [B][L] at row stride ld_duration >= L (what the regulator consumed); n = text_len[b] valid tokens (NULL: L; a
+ * value outside [0, L] counts as 0); len = audio_len[b] (a value outside [0, S] counts as 0, as in ispk_join_plan); hop =
+ * samples per frame.  clamp(v, lo, hi) = lo if v < lo, else hi if v > hi, else v.  The boundary m_t before token t, t in [0, n]:
+ *   1. round != 0 (hard durations): r_t = hd_reps<true> of csrc/dec_len.h = (d_t + 0.5f) truncated, 0 below 1 (and for NaN),
+ *      cut at 2^30; C_t = r_0 + .. + r_{t-1} in int64; m_t = hop C_t.
+ *   2. round == 0 (soft durations): s_0 = 0, s_{t+1} = s_t + d'_t in fp32, sequentially in token order, d'_t = d_t if d_t > 0
+ *      else 0 (NaN: 0); v = (double)s_t hop + 0.5; m_t = len where v >= len + 1, else floor(v).  For durations >= 0 the s_t
+ *      are soft_dur_sum's sequence bit for bit, so (int64)(s_n + 0.5f) is the frames_wanted of ispk_infer_features_items_f32;
+ *      a boundary is where the soft path hands the weight from one token to the next.
+ *   3. m_t = clamp(m_t, 0, len).
+ *   4. bounds int64 [B][2] (may be NULL: (0, len)): s_b = clamp(start, 0, len), e_b = clamp(end, s_b, len) as in the join;
+ *      m_t = clamp(m_t, s_b, e_b) - s_b.
+ *   5. the join group item_offset int64 [B], doc int64 [B], doc_len int64 [D] (all given or all NULL): an item with
+ *      item_offset[b] < 0 or doc[b] outside [0, D) is dropped and every mark of it is -1; else with d = doc[b] and
+ *      dl = max(doc_len[d], 0): m_t = clamp(m_t + item_offset[b], 0, dl)  (item_offset below 2^62).
+ *   6. doc_bounds int64 [D][2] (may be NULL, only with the join group): ds = clamp(start_d, 0, dl), de = clamp(end_d, ds, dl);
+ *      m_t = clamp(m_t, ds, de) - ds.
+ *   token_marks int64 [B][L][2] = (m_t, m_{t+1}) for t < n and (-1, -1) for n <= t < L.
+ *   word_marks int64 [B][W][2] (NULL allowed when W == 0): over the tokens t < n whose word_id[b][t] = w lies in [0, W),
+ *   (min m_t, max m_{t+1}); (-1, -1) for a word without a token; any other word_id is ignored (word_id int64 [B][L]
+ *   contiguous, NULL: no words).
+ * Starts are at most ends, consecutive tokens tile ([m_t, m_{t+1}) then [m_{t+1}, m_{t+2})), and without a join an item's first
+ * start is 0.  Under a crossfade an item begins before its predecessor ends, so the marks of neighbouring ITEMS overlap there by
+ * the overlap of their audio: that is where both are heard, and it is left so.  The fp32 sum of the soft mode is one thread's
+ * loop - its order is the contract with the regulator; the hard sums are integers (a block scan).  Plain vector stores, no
+ * global atomics; a pure function of its inputs: repeated calls and graph replays give identical bits.
+ * Refused: NULL duration, audio_len or token_marks, a partial join group, doc_bounds without the join group, W > 0 (with or
+ * without word_id) but no word_marks (E_NULL); L > 4096, W outside [0, 1024], B > 65535, hop outside [1, 2^20], S outside [0, 2^31),
+ * ld_duration < L, D outside [1, 1024] with the join group (E_SHAPE).  B = 0 or L = 0 is a no-op. */
+int32_t ispk_speech_marks(const float* duration, int64_t ld_duration, const int64_t* text_len, const int64_t* audio_len,
+                          const int64_t* bounds, const int64_t* item_offset, const int64_t* doc, const int64_t* doc_len,
+                          const int64_t* doc_bounds, const int64_t* word_id, int64_t* token_marks, int64_t* word_marks,
+                          int32_t hop, int32_t round, int32_t B, int32_t L, int32_t S, int32_t D, int32_t W,
+                          ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

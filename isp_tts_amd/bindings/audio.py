@@ -16,7 +16,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa", "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT",
            "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
            "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
-           "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio"]
+           "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio",
+           "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -654,3 +655,50 @@ def join_audio(audio: Tensor, gain: Optional[Tensor], plan: Tensor, doc_len: Ten
     _rt._launch("join_kernel", 3.0 * D * S_out, 4.0 * (B * S + D * S_out), _rt.lib().ispk_join_f32, audio.data_ptr(), audio.stride(0),
                 _rt._ptr(gain), plan.data_ptr(), doc_len.data_ptr(), out.data_ptr(), out.stride(0), B, S, D, S_out, _rt._stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ speech marks
+MARKS_MAX_TOKENS = 4096       # tokens per item (L)
+MARKS_MAX_WORDS = 1024        # words per item (W)
+
+
+def speech_marks(duration: Tensor, text_len: Optional[Tensor], audio_len: Tensor, token_marks: Tensor,
+                 word_marks: Optional[Tensor], hop: int, S: int, hard: bool = False, bounds: Optional[Tensor] = None,
+                 item_offset: Optional[Tensor] = None, doc: Optional[Tensor] = None, doc_len: Optional[Tensor] = None,
+                 doc_bounds: Optional[Tensor] = None, word_id: Optional[Tensor] = None) -> None:
+    """ispk_speech_marks, one launch of one workgroup per item, no host read: the sample range of every token and word
+    (include/ispk.h has the arithmetic).  duration fp32 [B, L] (unit stride on L, any row stride); int64 [B]: text_len (None:
+    L tokens each), audio_len, item_offset, doc; bounds int64 [B, 2]; doc_len int64 [D]; doc_bounds int64 [D, 2]; word_id int64
+    [B, L]; token_marks int64 [B, L, 2]; word_marks int64 [B, W, 2] or None (no words).  The join group (item_offset, doc,
+    doc_len) is given whole or not at all."""
+    _rt._dev(duration, text_len, audio_len, token_marks, word_marks, bounds, item_offset, doc, doc_len, doc_bounds, word_id)
+    if duration.ndim != 2 or duration.dtype != torch.float32 or (duration.shape[1] > 1 and duration.stride(1) != 1):
+        raise ValueError(f"duration: fp32 [B, L] with unit stride on L, got {duration.dtype} {tuple(duration.shape)} strides "
+                         f"{tuple(duration.stride())}")
+    B, L = duration.shape
+    if B > 1 and duration.stride(0) < L:
+        raise ValueError(f"duration: rows overlap (row stride {duration.stride(0)} < {L})")
+    for name, t in (("text_len", text_len), ("audio_len", audio_len), ("item_offset", item_offset), ("doc", doc)):
+        if t is not None:
+            _rt._out_like(name, t, torch.int64, (B,))
+    joined = [t is not None for t in (item_offset, doc, doc_len)]
+    if any(joined) and not all(joined):
+        raise ValueError("speech_marks: item_offset, doc and doc_len are given together or not at all")
+    if doc_bounds is not None and not all(joined):
+        raise ValueError("speech_marks: doc_bounds only together with item_offset, doc and doc_len")
+    D = doc_len.shape[0] if doc_len is not None else 0
+    W = word_marks.shape[1] if word_marks is not None and word_marks.ndim == 3 else 0
+    for name, t, shape in (("bounds", bounds, (B, 2)), ("doc_len", doc_len, (D,)), ("doc_bounds", doc_bounds, (D, 2)),
+                           ("word_id", word_id, (B, L)), ("token_marks", token_marks, (B, L, 2)), ("word_marks", word_marks, (B, W, 2))):
+        if t is not None:
+            _rt._out_like(name, t, torch.int64, shape)
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: contiguous int64 {list(shape)}")
+    if B == 0 or L == 0:
+        return
+    # read: the durations, word ids and the per-item / per-document scalars; written: both mark tensors
+    nbytes = 4.0 * B * L + (8.0 * B * L if word_id is not None else 0.0) + 8.0 * (5 * B + 3 * D) + 16.0 * B * (L + W)
+    _rt._launch("speech_marks_kernel", 2.0 * B * L, nbytes, _rt.lib().ispk_speech_marks, duration.data_ptr(),
+                duration.stride(0) if B > 1 else max(duration.stride(0), L), _rt._ptr(text_len), audio_len.data_ptr(), _rt._ptr(bounds),
+                _rt._ptr(item_offset), _rt._ptr(doc), _rt._ptr(doc_len), _rt._ptr(doc_bounds), _rt._ptr(word_id),
+                token_marks.data_ptr(), _rt._ptr(word_marks) if W else None, int(hop), int(bool(hard)), B, L, int(S), D, W, _rt._stream())

@@ -8,7 +8,8 @@ pieces put the documents back together on the device, with no host read:
     r = join(audio, audio_len, doc, pos, pause, num_docs=D, out_samples=S_out, fade=64)          # r["audio"] fp32 [D, S_out]
 
 and `Synthesizer` captures the whole chain - infer, vocoder, optional denoiser and trim, join, optional document loudness,
-PCM16 - over static buffers.  The join (csrc/join.hip; include/ispk.h has the arithmetic) orders the valid items by
+PCM16, optional speech marks - over static buffers.  `speech_marks` (csrc/marks.hip) says where every token and word lies in
+an item or in its joined document; `cues` and `webvtt` turn word marks into subtitles on the host.  The join (csrc/join.hip; include/ispk.h has the arithmetic) orders the valid items by
 (doc, pos, b), puts `pause[b]` samples of silence behind item b or - negative - crossfades it with its successor over
 min(-pause, n / 2, n_next / 2) samples with weights that add up to one, and fades the remaining edges over `fade` samples.
 """
@@ -89,6 +90,101 @@ def join(audio: Tensor, audio_len: Tensor, doc: Tensor, pos: Tensor, pause: Opti
     return out
 
 
+def marks_outputs(B: int, L: int, words: int, device) -> dict:
+    """The tensors `speech_marks` fills, for a caller that keeps them (a graph capture)."""
+    e = lambda shape: torch.empty(shape, dtype=torch.int64, device=device)      # noqa: E731
+    return dict(token_marks=e((B, L, 2)), word_marks=e((B, int(words), 2)))
+
+
+def speech_marks(duration: Tensor, text_len: Optional[Tensor], audio_len: Tensor, *, samples_per_frame: int, hard: bool = False,
+                 bounds: Optional[Tensor] = None, joined: Optional[dict] = None, doc: Optional[Tensor] = None,
+                 doc_bounds: Optional[Tensor] = None, word_id: Optional[Tensor] = None, words: int = 0,
+                 out: Optional[dict] = None) -> dict:
+    """Speech marks ("timepoints"): where every token and word lies, in samples.  One launch (ispk_speech_marks), no ATen
+    compute op, no host read, integers that a numpy restatement of include/ispk.h's arithmetic reproduces exactly.  On the device:
+
+      duration   fp32 [B, L] (unit stride on L, any row stride): what the regulator consumed - `ao.duration` of `model.infer`,
+                 or the aligner's `attn_hard_duration` of a teacher-forced forward as fp32 with hard=True (forced alignment)
+      text_len   int64 [B] valid tokens (None: L each);  audio_len  int64 [B] samples of the items BEFORE any trimming
+      samples_per_frame   the vocoder's hop;  hard: the durations are repeats, (d + 0.5) truncated (the hard regulator's), not
+                 fractional frames (the soft regulator's running fp32 sum)
+      bounds     int64 [B, 2], an item conditioner's: the marks move with the trim and stay inside what is kept
+      joined     the dict `join` returned (its item_offset and audio_len are used) with `doc` int64 [B], the argument `join`
+                 got: the marks are then samples of the joined document; every mark of a dropped item is -1
+      doc_bounds int64 [D, 2], a document conditioner's bounds on the joined documents (only with `joined`)
+      word_id    int64 [B, L]: the word of each token, 0 <= id < words <= 1024; other ids (punctuation, padding) belong to no word
+
+    -> dict(token_marks int64 [B, L, 2], word_marks int64 [B, words, 2]): (start, end) sample ranges, end exclusive; (-1, -1) for
+    a token at or past text_len and for a word without a token.  Tokens of one item tile its audio.  Under a crossfade an item
+    begins before its predecessor ends, so the last marks of one item and the first of the next overlap there - both are
+    heard.  `out` (marks_outputs) supplies the tensors."""
+    if duration.ndim != 2 or duration.dtype != torch.float32 or (duration.shape[1] > 1 and duration.stride(1) != 1):
+        raise ValueError(f"duration: fp32 [B, L] with unit stride on L, got {duration.dtype} {tuple(duration.shape)} strides "
+                         f"{tuple(duration.stride())}")
+    B, L = duration.shape
+    W, hop = int(words), int(samples_per_frame)
+    if not (B <= 65535 and L <= runtime.MARKS_MAX_TOKENS and 0 <= W <= runtime.MARKS_MAX_WORDS):
+        raise ValueError(f"speech_marks: B={B} (<= 65535), L={L} (<= {runtime.MARKS_MAX_TOKENS}), words={W} (<= {runtime.MARKS_MAX_WORDS})")
+    if hop != samples_per_frame or not 1 <= hop <= 2 ** 20:
+        raise ValueError(f"samples_per_frame is an integer in [1, 2^20], got {samples_per_frame!r}")
+    if (joined is None) != (doc is None):
+        raise ValueError("speech_marks: `joined` (what join returned) and `doc` (what join was given) go together")
+    if doc_bounds is not None and joined is None:
+        raise ValueError("speech_marks: doc_bounds only together with `joined` and `doc`")
+    if word_id is not None and W == 0:
+        raise ValueError("speech_marks: word_id needs words >= 1")
+    for t in (duration, text_len, audio_len, bounds, doc, doc_bounds, word_id, *((joined or {}).get(k) for k in ("item_offset", "audio_len"))):
+        if t is not None and not t.is_cuda:
+            raise runtime.IspkError("speech_marks needs GPU tensors; there is no CPU fallback")
+    if out is None:
+        out = marks_outputs(B, L, W, duration.device)
+    S = 2 ** 31 - 1          # the lengths are the vocoder's: nothing to hold them to but the ABI's range
+    item_offset = doc_len = None
+    if joined is not None:
+        item_offset, doc_len = joined["item_offset"], joined["audio_len"]
+        if not 1 <= doc_len.shape[0] <= runtime.JOIN_MAX:
+            raise ValueError(f"speech_marks: 1 .. {runtime.JOIN_MAX} documents, got {doc_len.shape[0]}")
+    runtime.speech_marks(duration, text_len, audio_len, out["token_marks"], out["word_marks"] if W else None, hop, S, bool(hard),
+                         bounds, item_offset, doc, doc_len, doc_bounds, word_id)
+    return out
+
+
+def cues(word_marks: Tensor, doc: Tensor, labels: Sequence[Sequence[str]], sample_rate: float) -> list:
+    """Host helper, run after the graph: ONE device read (word_marks and doc are copied to the host here).  word_marks int64
+    [B, W, 2] of `speech_marks(joined=...)`, doc int64 [B], labels[b][w] the text of word w of item b (shorter rows: the rest
+    has no cue) -> [(doc, start_seconds, end_seconds, label)] sorted by (doc, start, end, item, word): document order.  Words
+    without marks (-1: absent, or of a dropped item) are skipped."""
+    if sample_rate <= 0:
+        raise ValueError(f"sample_rate > 0, got {sample_rate!r}")
+    wm, dc = word_marks.detach().cpu().tolist(), doc.detach().cpu().tolist()
+    if len(labels) != len(wm) or len(dc) != len(wm):
+        raise ValueError(f"cues: {len(wm)} items of marks, {len(dc)} of doc, {len(labels)} of labels")
+    rows = []
+    for b, (item, names) in enumerate(zip(wm, labels)):
+        for w, ((start, end), name) in enumerate(zip(item, names)):
+            if start >= 0:
+                rows.append((dc[b], start, end, b, w, name))
+    rows.sort(key=lambda r: r[:5])
+    return [(d, start / sample_rate, end / sample_rate, name) for d, start, end, _, _, name in rows]
+
+
+def _vtt_time(seconds: float) -> str:
+    ms = int(round(seconds * 1000.0))
+    return f"{ms // 3600000:02d}:{ms // 60000 % 60:02d}:{ms // 1000 % 60:02d}.{ms % 1000:03d}"
+
+
+def webvtt(cues_of_one_document: Sequence[tuple]) -> str:
+    """The cues of ONE document ((doc, start_seconds, end_seconds, label), as `cues` returns them) as a WebVTT file."""
+    docs = {c[0] for c in cues_of_one_document}
+    if len(docs) > 1:
+        raise ValueError(f"webvtt: the cues of one document, got documents {sorted(docs)}")
+    lines = ["WEBVTT", ""]
+    for i, (_, start, end, label) in enumerate(cues_of_one_document, 1):
+        text = str(label).replace("&", "&amp;").replace("<", "&lt;").replace(">", "&gt;").replace("\n", " ")
+        lines += [str(i), f"{_vtt_time(start)} --> {_vtt_time(end)}", text, ""]
+    return "\n".join(lines)
+
+
 class SynthesisResult(dict):
     """The static outputs of a `Synthesizer` call (overwritten by the next one), and `truncated`: frames_wanted > frames, a
     device comparison made when it is read - not part of the graph."""
@@ -115,13 +211,17 @@ class Synthesizer:
 
     Stages: model.infer(controls=, max_dec_len=M) -> vocoder(mel, dec_lengths) -> denoiser (optional) -> the measure pass of
     `item_conditioner` (optional: its bounds and gain go straight into the join, the per-item apply pass is not run) -> join ->
-    `doc_conditioner` on the joined documents (optional: document-level loudness) -> to_pcm16.  A call copies its arguments
-    into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
+    `doc_conditioner` on the joined documents (optional: document-level loudness) -> to_pcm16 -> with `marks=True` the speech
+    marks (one more launch: r["token_marks"] int64 [B, L, 2] and r["word_marks"] int64 [B, words, 2], sample ranges inside the
+    final documents; `word_id` int64 [B, L] of a call names each token's word, none when it is not given; the launch's other
+    inputs come along as r["duration"], r["item_audio_len"], r["item_bounds"], r["joined_len"], r["doc_bounds"]).  A call copies
+    its arguments into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
     one Synthesizer serves one bucket shape (B sentences of L tokens into D documents of S_out samples)."""
 
     def __init__(self, model, vocoder, *, batch: int, tokens: int, frames: int, docs: int, doc_samples: int, steps: int = 4,
                  denoiser=None, item_conditioner: Optional[AudioConditioner] = None,
-                 doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0):
+                 doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0,
+                 marks: bool = False, words: int = 0):
         B, L, M, D, S_out = int(batch), int(tokens), int(frames), int(docs), int(doc_samples)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -132,6 +232,11 @@ class Synthesizer:
         self.item_conditioner, self.doc_conditioner = item_conditioner, doc_conditioner
         self.batch, self.tokens, self.frames, self.docs, self.doc_samples, self.steps = B, L, M, D, S_out, int(steps)
         self.fade, self.dither, self.seed = int(fade), bool(dither), int(seed)
+        self.marks, self.words = bool(marks), int(words)
+        if not 0 <= self.words <= runtime.MARKS_MAX_WORDS or (self.words and not self.marks):
+            raise ValueError(f"Synthesizer: words={words} (0 .. {runtime.MARKS_MAX_WORDS}, only with marks=True)")
+        if self.marks and L > runtime.MARKS_MAX_TOKENS:
+            raise ValueError(f"Synthesizer: marks serve at most {runtime.MARKS_MAX_TOKENS} tokens, got {L}")
         self.multi_speaker = getattr(model, "speaker_embedding", None) is not None
         i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)      # noqa: E731
         self.static = {"text": i64(B, L), "text_len": torch.full((B,), L, dtype=torch.int64, device=dev), "doc": i64(B),
@@ -155,6 +260,13 @@ class Synthesizer:
             self._doc = doc_conditioner.empty_outputs(D, S_out, dev)
             doc_conditioner.device_tables(dev)
         self._pcm = torch.empty((D, S_out), dtype=torch.int16, device=dev)
+        self._marks = None
+        if self.marks:
+            if S % M:
+                raise ValueError(f"Synthesizer: marks need a vocoder with a whole hop, got {S} samples for {M} frames")
+            self._hop = S // M
+            self.static["word_id"] = torch.full((B, L), -1, dtype=torch.int64, device=dev)
+            self._marks = marks_outputs(B, L, self.words, dev)
         self._graph = graph.GraphedCall(self._chain)
         self.out = self._graph.out
 
@@ -182,8 +294,17 @@ class Synthesizer:
                 r = self.doc_conditioner(doc_audio, doc_len, out=self._doc)
                 doc_audio, doc_len = r["audio"], r["audio_len"]
             pcm = to_pcm16(doc_audio, doc_len, dither=self.dither, seed=self.seed, out=self._pcm)
-        return dict(pcm=pcm, audio=doc_audio, audio_len=doc_len, wanted_len=j["wanted_len"], item_offset=j["item_offset"],
-                    item_len=j["item_len"], frames_wanted=frames_wanted, dec_lengths=ao.dec_lengths)
+        out = dict(pcm=pcm, audio=doc_audio, audio_len=doc_len, wanted_len=j["wanted_len"], item_offset=j["item_offset"],
+                   item_len=j["item_len"], frames_wanted=frames_wanted, dec_lengths=ao.dec_lengths)
+        if self.marks:
+            # the last launch of the chain, fed by what the stages above consumed and wrote; its inputs are handed out too
+            m, doc_bounds = self._marks, self._doc["bounds"] if self._doc is not None else None
+            runtime.speech_marks(ao.duration, s["text_len"], audio_len, m["token_marks"], m["word_marks"] if self.words else None,
+                                 self._hop, audio.shape[1], not self.model.temporal_adaptor.soft_duration, bounds, j["item_offset"],
+                                 s["doc"], j["audio_len"], doc_bounds, s["word_id"] if self.words else None)
+            out.update(token_marks=m["token_marks"], word_marks=m["word_marks"], duration=ao.duration, item_audio_len=audio_len,
+                       item_bounds=bounds, joined_len=j["audio_len"], doc_bounds=doc_bounds)
+        return out
 
     def _checked(self, name: str, t: Tensor) -> Tensor:
         want = self.static[name]
@@ -197,8 +318,12 @@ class Synthesizer:
 
     def __call__(self, text: Tensor, text_len: Tensor, doc: Tensor, pos: Tensor, pause: Optional[Tensor] = None,
                  controls: Optional[Tensor] = None, speaker: Optional[Tensor] = None,
-                 flow_noise: Optional[Tensor] = None) -> SynthesisResult:
+                 flow_noise: Optional[Tensor] = None, word_id: Optional[Tensor] = None) -> SynthesisResult:
         given = {"text": text, "text_len": text_len, "doc": doc, "pos": pos}
+        if word_id is not None:
+            if not self.words:
+                raise ValueError("word_id: the Synthesizer was built without words (marks=True, words=W)")
+            given["word_id"] = word_id
         for name, t in (("pause", pause), ("controls", controls), ("flow_noise", flow_noise)):
             if t is not None:
                 given[name] = t
@@ -216,6 +341,8 @@ class Synthesizer:
             self.static["controls"].copy_(self._default_controls())
         if flow_noise is None:
             self.static["flow_noise"].normal_()
+        if self.marks and word_id is None:
+            self.static["word_id"].fill_(-1)
         return SynthesisResult(self._graph.replay(), self.frames)
 
     def _default_controls(self) -> Tensor:
