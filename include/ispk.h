@@ -425,6 +425,15 @@ int32_t ispk_infer_features_items_f32(const float* pred, const float* duration_t
                                       const float* pitch_target, const float* energy_target, const float* controls,
                                       int32_t round, float* duration, float* features, int64_t* frames_wanted, int32_t B,
                                       int32_t L, ispk_stream_t stream);
+/* The same with one control set per TOKEN (word-level prosody): controls fp32 [B][L][5], row (b, l) = (duration_factor,
+ * pitch_factor, pitch_delta, energy_factor, energy_delta) of token l of utterance b.  The same per-token expression under the
+ * same contraction setting, the same frames_wanted (the sequential fp32 sum, or the integer repeats with round != 0), the same
+ * refusals and the same no-op at B = 0.  If every row of an utterance equals that utterance's [5] row, duration, features and
+ * frames_wanted have the bits of ispk_infer_features_items_f32. */
+int32_t ispk_infer_features_tokens_f32(const float* pred, const float* duration_target_f32, const int64_t* duration_target_i64,
+                                       const float* pitch_target, const float* energy_target, const float* controls,
+                                       int32_t round, float* duration, float* features, int64_t* frames_wanted, int32_t B,
+                                       int32_t L, ispk_stream_t stream);
 int32_t ispk_flow_mix_f32(const float* x0, const float* x1, const float* t, float sigma, float* x_t, float* flow, int32_t B,
                           int32_t L, int32_t C, ispk_stream_t stream);
 int32_t ispk_flow_finish_f32(const float* pred_raw, const float* flow, const float* x0, const uint8_t* mask, float* pred,
@@ -1207,6 +1216,33 @@ int32_t ispk_speech_marks(const float* duration, int64_t ld_duration, const int6
                           const int64_t* doc_bounds, const int64_t* word_id, int64_t* token_marks, int64_t* word_marks,
                           int32_t hop, int32_t round, int32_t B, int32_t L, int32_t S, int32_t D, int32_t W,
                           ispk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Gain envelope (csrc/prosody.hip, isp_tts_amd/longform.py): a linear gain per token on the items' waveforms, with short
+ * linear ramps at the token boundaries - the volume part of word-level prosody.  One launch, no atomics, no host read.
+ * audio fp32 [B][S] at ld_audio; len = audio_len[b] (a value outside [0, S] counts as 0); token_marks int64 [B][L][2] as
+ * ispk_speech_marks writes them in ITEM coordinates (no bounds, no join group); token_gain fp32 [B][L], linear; ramp in samples.
+ *   A token with a negative start or end (the marks' -1) is dead.  The others have start and end clamped to [0, len] and are
+ *   live when start < end then (a token cut to nothing holds no sample and lends nothing).  The live tokens in index order
+ *   tile [0, E), E <= len: each starts where its live predecessor ends, which is how the kernel finds its start.
+ *   tok(n) = the live token that holds n; for n >= E the last live token; without a live token e[n] = 1.
+ *   At every boundary p between consecutive live tokens j < k: h = min(ramp, (end_j - start_j) / 2, (end_k - start_k) / 2),
+ *   `/` floors.  For n in [p - h, p + h), in fp32 without contraction: i = n - p + h, w = (float)(2 i + 1) / (float)(4 h),
+ *   e[n] = g_j + (g_k - g_j) w.  Elsewhere e[n] = g_tok(n).  A token lends at most half of itself to each side, so ramps never
+ *   overlap, and h = 0 is a step.
+ *   out[b][n] = audio[b][n] e[n] for n < len, 0 for len <= n < S  (out fp32 [B][S] at ld_out).
+ * Nothing at or past len is read.  Marks that do not tile may give any finite envelope and never cause an access outside the
+ * item's rows.  out may be exactly audio (same base, same row stride); otherwise the two must not overlap.  An item's bits
+ * depend on that item alone; repeated calls and graph replays repeat theirs.  With all gains equal to g, out has the bits of
+ * audio g below len.  Grid (ceil(S / ispk_gain_envelope_tile_samples()), B); 16 bytes per lane when both bases are 16-byte
+ * aligned and both strides multiples of four floats.
+ * Refused: NULL audio, audio_len, token_marks, token_gain or out (E_NULL); L outside [1, 4096], B > 65535, S outside [0, 2^31),
+ * a row stride below S, ramp outside [0, 2^22), out overlapping audio without being audio (E_SHAPE).  B = 0 (or S = 0) is a
+ * no-op. */
+int32_t ispk_gain_envelope_tile_samples(void);
+int32_t ispk_gain_envelope_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const int64_t* token_marks,
+                               const float* token_gain, int32_t ramp, float* out, int64_t ld_out, int32_t B, int32_t L,
+                               int32_t S, ispk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,

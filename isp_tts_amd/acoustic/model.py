@@ -301,10 +301,15 @@ class AcousticModel(nn.Module, Constructor):
         `controls` fp32 [B, 5] on the model's device (longform.make_controls): per-utterance (duration_factor, pitch_factor,
         pitch_delta, energy_factor, energy_delta), read on the device - see `FlowTemporalAdaptor.infer`.  The scalar controls
         must then be at their defaults; with `pitch_normalize` only `pitch_target` is normalised, the pitch_delta column is
-        taken to be in normalised units already."""
+        taken to be in normalised units already.  A 3-D `controls` fp32 [B, L, 5] (longform.prosody_spans) has one such row
+        per token."""
         if controls is not None and (duration_factor, pitch_factor, pitch_delta) != (1.0, 1.0, 0.0):
             raise ValueError("infer: with `controls` the scalar controls stay at their defaults, got duration_factor="
                              f"{duration_factor}, pitch_factor={pitch_factor}, pitch_delta={pitch_delta}")
+        if controls is not None and controls.ndim == 3:      # (before any launch; the [B, 5] form is checked by the adaptor)
+            B, L = input_sequence.shape
+            if controls.dtype != torch.float32 or tuple(controls.shape) != (B, L, 5):
+                raise ValueError(f"controls: fp32 [{B}, {L}, 5], got {controls.dtype} {tuple(controls.shape)}")
         batch_infer = input_sequence.shape[0] > 1
         token_emb, enc_mask, handed = self._embed(input_sequence, text_lengths if batch_infer else None, want_mask=batch_infer)
         enc_out = self.encoder(token_emb, mask=enc_mask, key_len=text_lengths if batch_infer else None, handed=handed).out

@@ -394,7 +394,9 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
         `controls` fp32 [B, 5] on the device: one (duration_factor, pitch_factor, pitch_delta, energy_factor, energy_delta) per
         utterance in place of the scalars, which must then be at their defaults - read by the kernel, so one captured graph
         serves every mix of them.  `self.frames_wanted` (int64 [B]) is then the decoder length each utterance asks for, while
-        `dec_lengths` is cut to `max_dec_len`: frames_wanted > max_dec_len says that an utterance was truncated."""
+        `dec_lengths` is cut to `max_dec_len`: frames_wanted > max_dec_len says that an utterance was truncated.  A 3-D
+        `controls` fp32 [B, L, 5] carries one such row per TOKEN (longform.prosody_spans builds it): the same kernel reading a
+        row per token, so rows that are constant over an utterance give the bits of the [B, 5] form."""
         if controls is not None:
             return self._infer_items(enc_out, enc_mask, duration_target, pitch_target, energy_target, controls, steps, noise,
                                      max_dec_len, enc_len, qkv_for,
@@ -431,16 +433,22 @@ class FlowTemporalAdaptor(nn.Module, Constructor):
 
     def _infer_items(self, enc_out, enc_mask, duration_target, pitch_target, energy_target, controls, steps, noise, max_dec_len,
                      enc_len, qkv_for, scalars) -> TemporalAdaptorOutput:
-        """`infer` with per-utterance controls: ispk_infer_features_items_f32 in place of ispk_infer_features_f32, and the
-        regulators clamp the decoder lengths to `max_dec_len`."""
+        """`infer` with per-utterance controls: ispk_infer_features_items_f32 (per-token controls: ispk_infer_features_tokens_f32)
+        in place of ispk_infer_features_f32, and the regulators clamp the decoder lengths to `max_dec_len`."""
         if tuple(float(v) for v in scalars) != (1.0, 1.0, 0.0, 1.0, 0.0):
             raise ValueError("infer: with `controls` the scalar controls stay at their defaults (duration_factor, pitch_factor, "
                              f"pitch_delta, energy_factor, energy_delta = 1, 1, 0, 1, 0), got {tuple(scalars)}")
-        if controls.dtype != torch.float32 or tuple(controls.shape) != (enc_out.shape[0], 5):
+        per_token = controls.ndim == 3          # [B, L, 5]: one row per token (word-level prosody)
+        if per_token:
+            B, L = enc_out.shape[:2]
+            if controls.dtype != torch.float32 or tuple(controls.shape) != (B, L, 5):
+                raise ValueError(f"controls: fp32 [{B}, {L}, 5], got {controls.dtype} {tuple(controls.shape)}")
+        elif controls.dtype != torch.float32 or tuple(controls.shape) != (enc_out.shape[0], 5):
             raise ValueError(f"controls: fp32 [{enc_out.shape[0]}, 5], got {controls.dtype} {tuple(controls.shape)}")
         m3 = enc_mask[..., None] if enc_mask is not None else None
         pred = self.predictor.infer(enc_out, mask=m3, steps=steps, noise=noise, key_len=enc_len)
-        duration_pred, feats, self.frames_wanted = runtime.infer_features_items(
+        entry = runtime.infer_features_tokens if per_token else runtime.infer_features_items
+        duration_pred, feats, self.frames_wanted = entry(
             pred, duration_target, pitch_target, energy_target, controls, round_duration=not self.soft_duration)
         pitch, energy = feats[..., 0:1], feats[..., 1:2]
         enc_out = self.embedding(feats, residual=enc_out)                                   # no mask, even batched (:384)

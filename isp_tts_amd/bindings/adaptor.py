@@ -7,7 +7,7 @@ from torch import Tensor
 from .. import runtime as _rt
 
 __all__ = ["mas", "pad_rows", "conv5_padded", "masked_instnorm", "aligner_scores", "soft_average", "flow_mix", "flow_finish",
-           "flow_head", "flow_euler", "infer_features", "infer_features_items", "embed_tokens", "embed_tokens_qkv", "_speaker_ids", "add_speaker_",
+           "flow_head", "flow_euler", "infer_features", "infer_features_items", "infer_features_tokens", "embed_tokens", "embed_tokens_qkv", "_speaker_ids", "add_speaker_",
            "add_speaker", "speaker_grad", "time_embedding", "length_regulate", "_hard_durations", "hard_regulate",
            "hard_regulate_bwd", "hard_average"]
 
@@ -243,6 +243,37 @@ def infer_features_items(pred: Tensor, duration_target: Optional[Tensor], pitch_
         return duration, feats, frames
     _rt._launch("infer_features_items_kernel<round>" if round_duration else "infer_features_items_kernel", 0.0, 24.0 * B * L,
                 _rt.lib().ispk_infer_features_items_f32, pc.data_ptr(), _rt._ptr(dur_f), _rt._ptr(dur_i), _rt._ptr(pt), _rt._ptr(et),
+                cc.data_ptr(), int(bool(round_duration)), duration.data_ptr(), feats.data_ptr(), _rt._ptr(frames), B, L, _rt._stream())
+    return duration, feats, frames
+
+
+def infer_features_tokens(pred: Tensor, duration_target: Optional[Tensor], pitch_target: Optional[Tensor],
+                          energy_target: Optional[Tensor], controls: Tensor, round_duration: bool = False,
+                          want_frames: bool = True):
+    """ispk_infer_features_tokens_f32: `infer_features_items` with one control row per TOKEN, controls fp32 [B, L, 5] on the
+    device.  Rows that are constant over an utterance give the bits of `infer_features_items`."""
+    _rt._dev(pred, duration_target, pitch_target, energy_target, controls)
+    B, L, C = pred.shape
+    assert C == 3 and pred.dtype == torch.float32
+    if controls.dtype != torch.float32 or tuple(controls.shape) != (B, L, 5):
+        raise ValueError(f"controls: fp32 [{B}, {L}, 5], got {controls.dtype} {tuple(controls.shape)}")
+    pc, cc = pred.contiguous(), controls.contiguous()
+    dur_f = dur_i = None
+    if duration_target is not None:
+        assert duration_target.shape == (B, L)
+        if duration_target.dtype == torch.int64:
+            dur_i = duration_target.contiguous()
+        else:
+            dur_f = duration_target.float().contiguous()
+    pt = None if pitch_target is None else pitch_target.float().reshape(B, L).contiguous()
+    et = None if energy_target is None else energy_target.float().reshape(B, L).contiguous()
+    duration = torch.empty((B, L), dtype=torch.float32, device=pred.device)
+    feats = torch.empty((B, L, 2), dtype=torch.float32, device=pred.device)
+    frames = torch.empty((B,), dtype=torch.int64, device=pred.device) if want_frames else None
+    if B == 0:      # (NULL data_ptr() of an empty tensor: see soft_average)
+        return duration, feats, frames
+    _rt._launch("infer_features_tokens_kernel<round>" if round_duration else "infer_features_tokens_kernel", 0.0, 44.0 * B * L,
+                _rt.lib().ispk_infer_features_tokens_f32, pc.data_ptr(), _rt._ptr(dur_f), _rt._ptr(dur_i), _rt._ptr(pt), _rt._ptr(et),
                 cc.data_ptr(), int(bool(round_duration)), duration.data_ptr(), feats.data_ptr(), _rt._ptr(frames), B, L, _rt._stream())
     return duration, feats, frames
 

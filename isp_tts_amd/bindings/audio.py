@@ -17,7 +17,7 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
            "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
            "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio",
-           "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks"]
+           "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -702,3 +702,44 @@ def speech_marks(duration: Tensor, text_len: Optional[Tensor], audio_len: Tensor
                 duration.stride(0) if B > 1 else max(duration.stride(0), L), _rt._ptr(text_len), audio_len.data_ptr(), _rt._ptr(bounds),
                 _rt._ptr(item_offset), _rt._ptr(doc), _rt._ptr(doc_len), _rt._ptr(doc_bounds), _rt._ptr(word_id),
                 token_marks.data_ptr(), _rt._ptr(word_marks) if W else None, int(hop), int(bool(hard)), B, L, int(S), D, W, _rt._stream())
+
+
+# ------------------------------------------------------------------------------------------------------ gain envelope
+GAIN_TILE_SAMPLES = 4096      # ispk_gain_envelope_tile_samples(): samples of one item per workgroup
+GAIN_MAX_RAMP = 1 << 22
+
+
+def gain_envelope(audio: Tensor, audio_len: Tensor, token_marks: Tensor, token_gain: Tensor, ramp: int, out: Tensor) -> Tensor:
+    """ispk_gain_envelope_f32, one launch, no host read: out[b] = audio[b] * e, e the per-token gains token_gain fp32 [B, L]
+    over the item-coordinate token_marks int64 [B, L, 2] with linear ramps of at most `ramp` samples on each side of a token
+    boundary (include/ispk.h has the arithmetic).  audio and out fp32 [B, S] (unit stride on S, any row stride); out may be
+    audio itself, otherwise the two do not overlap.  audio_len int64 [B]."""
+    _rt._dev(audio, audio_len, token_marks, token_gain, out)
+    if audio.dtype != torch.float32 or audio.ndim != 2 or (audio.shape[1] > 1 and audio.stride(1) != 1):
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    if B > 65535 or S >= 2 ** 31:
+        raise ValueError(f"audio: at most 65535 items of fewer than 2^31 samples, got {tuple(audio.shape)}")
+    _out_like("audio_len", audio_len, torch.int64, (B,))
+    if token_marks.ndim != 3:
+        raise ValueError(f"token_marks: int64 [{B}, L, 2], got {tuple(token_marks.shape)}")
+    L = token_marks.shape[1]
+    _out_like("token_marks", token_marks, torch.int64, (B, L, 2))
+    _out_like("token_gain", token_gain, torch.float32, (B, L))
+    if not token_marks.is_contiguous() or not token_gain.is_contiguous():
+        raise ValueError("token_marks and token_gain: contiguous")
+    if not 1 <= L <= MARKS_MAX_TOKENS:
+        raise ValueError(f"gain_envelope: 1 .. {MARKS_MAX_TOKENS} tokens, got {L}")
+    if int(ramp) != ramp or not 0 <= ramp < GAIN_MAX_RAMP:
+        raise ValueError(f"ramp is an integer in [0, 2^22), got {ramp!r}")
+    _out_like("out", out, torch.float32, (B, S))
+    if B > 1 and (audio.stride(0) < S or out.stride(0) < S):
+        raise ValueError(f"audio / out: rows overlap (row strides {audio.stride(0)}, {out.stride(0)} < {S})")
+    if B == 0 or S == 0:
+        return out
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), S)      # noqa: E731
+    _rt._launch("gain_envelope_kernel", 4.0 * B * S, 8.0 * B * S + 20.0 * B * L, _rt.lib().ispk_gain_envelope_f32, audio.data_ptr(),
+                ld(audio), audio_len.data_ptr(), token_marks.data_ptr(), token_gain.data_ptr(), int(ramp), out.data_ptr(), ld(out), B,
+                L, S, _rt._stream())
+    return out

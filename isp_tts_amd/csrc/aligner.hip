@@ -702,8 +702,10 @@ __global__ __launch_bounds__(256) void infer_features_kernel(const float* __rest
 // (to memory and to LDS), thread 0 continues the row's fp32 sum over the chunk in token order - an order that depends on (b, l)
 // alone; the hard regulator's repeats are integers, so every thread adds its own tokens' and the block adds those.
 // gfx950 (csrc/resource_report.py aligner.hip): 28 VGPRs soft, 26 rounded, LDS 4,096 B static (4,128 B rounded); no spills, no scratch.
+// kTokens: controls [B][L][5], one row per TOKEN (word-level prosody) - the row is read where the token is computed and nothing
+// else differs, so rows that are constant over an item give the bits of the per-item form.  36 VGPRs soft, 34 rounded, same LDS.
 constexpr int kItemsChunk = 1024;
-template <bool kRound>
+template <bool kRound, bool kTokens = false>
 __global__ __launch_bounds__(256) void infer_features_items_kernel(const float* __restrict__ pred, const float* __restrict__ dur_f,
                                                                    const int64_t* __restrict__ dur_i,
                                                                    const float* __restrict__ pitch_t,
@@ -714,14 +716,21 @@ __global__ __launch_bounds__(256) void infer_features_items_kernel(const float* 
     __shared__ float dur_s[kItemsChunk];
     __shared__ int64_t reps_s[4];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* c = controls + (int64_t)b * 5;
-    const float df = c[0], pf = c[1], pd = c[2], ef = c[3], ed = c[4];
+    float df = 0.f, pf = 0.f, pd = 0.f, ef = 0.f, ed = 0.f;
+    if constexpr (!kTokens) {
+        const float* c = controls + (int64_t)b * 5;
+        df = c[0]; pf = c[1]; pd = c[2]; ef = c[3]; ed = c[4];
+    }
     float s = 0.f;
     int64_t reps = 0;                                                      // (hard) this thread's share: integers, any order
     for (int base = 0; base < L; base += kItemsChunk) {
         const int n = L - base < kItemsChunk ? L - base : kItemsChunk;
         for (int l = tid; l < n; l += 256) {
             const int64_t i = (int64_t)b * L + base + l;
+            if constexpr (kTokens) {
+                const float* c = controls + i * 5;
+                df = c[0]; pf = c[1]; pd = c[2]; ef = c[3]; ed = c[4];
+            }
             const float d = infer_features_token<kRound>(pred, dur_f, dur_i, pitch_t, energy_t, df, pf, pd, ef, ed, feats, i);
             duration[i] = d;
             dur_s[l] = d;
@@ -980,6 +989,26 @@ extern "C" int32_t ispk_infer_features_items_f32(const float* pred, const float*
                            duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
     else
         hipLaunchKernelGGL(infer_features_items_kernel<false>, dim3(B), dim3(256), 0, s, pred, duration_target_f32,
+                           duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
+    return ispk_launch_status();
+}
+
+extern "C" int32_t ispk_infer_features_tokens_f32(const float* pred, const float* duration_target_f32,
+                                                  const int64_t* duration_target_i64, const float* pitch_target,
+                                                  const float* energy_target, const float* controls, int32_t round, float* duration,
+                                                  float* features, int64_t* frames_wanted, int32_t B, int32_t L,
+                                                  ispk_stream_t stream) {
+    ISPK_REQUIRE(pred && controls && duration && features, ISPK_E_NULL, "infer_features_tokens: null pointer");
+    ISPK_REQUIRE(!(duration_target_f32 && duration_target_i64), ISPK_E_UNSUPPORTED,
+                 "infer_features_tokens: one duration target at most");
+    ISPK_REQUIRE(B >= 0 && L >= 1, ISPK_E_SHAPE, "infer_features_tokens: bad shape B=%d L=%d", B, L);
+    if (B == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (round)
+        hipLaunchKernelGGL((infer_features_items_kernel<true, true>), dim3(B), dim3(256), 0, s, pred, duration_target_f32,
+                           duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
+    else
+        hipLaunchKernelGGL((infer_features_items_kernel<false, true>), dim3(B), dim3(256), 0, s, pred, duration_target_f32,
                            duration_target_i64, pitch_target, energy_target, controls, duration, features, frames_wanted, L);
     return ispk_launch_status();
 }

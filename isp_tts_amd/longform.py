@@ -12,6 +12,10 @@ PCM16, optional speech marks - over static buffers.  `speech_marks` (csrc/marks.
 an item or in its joined document; `cues` and `webvtt` turn word marks into subtitles on the host.  The join (csrc/join.hip; include/ispk.h has the arithmetic) orders the valid items by
 (doc, pos, b), puts `pause[b]` samples of silence behind item b or - negative - crossfades it with its successor over
 min(-pause, n / 2, n_next / 2) samples with weights that add up to one, and fades the remaining edges over `fade` samples.
+
+Word-level prosody steers single words: `prosody_spans` turns SSML-like spans into per-token controls fp32 [B, L, 5] for
+`infer(controls=)` and linear gains [B, L] for `gain_envelope` (csrc/prosody.hip), which scales every token's samples with short
+linear ramps at the token boundaries; `Synthesizer(prosody=True)` has both in its captured chain.
 """
 from __future__ import annotations
 
@@ -149,6 +153,93 @@ def speech_marks(duration: Tensor, text_len: Optional[Tensor], audio_len: Tensor
     return out
 
 
+def gain_envelope(audio: Tensor, audio_len: Tensor, token_marks: Tensor, token_gain: Tensor, *, ramp: int = 128,
+                  out: Optional[Tensor] = None) -> Tensor:
+    """The volume part of word-level prosody: out[b] = audio[b] * e, e the linear gain token_gain[b, l] over token l's samples
+    with linear ramps of at most `ramp` samples (and at most half a token) on each side of a boundary between two tokens.  One
+    launch (ispk_gain_envelope_f32; include/ispk.h has the arithmetic), no ATen compute op, no host read.  On the device:
+    audio fp32 [B, S] (unit stride on S, any row stride), audio_len int64 [B], token_marks int64 [B, L, 2] in ITEM coordinates
+    (`speech_marks` without bounds and without `joined`), token_gain fp32 [B, L] (`prosody_spans` builds it).  Samples at and
+    past audio_len are 0 in the result.  `out` fp32 [B, S] may be `audio` itself (in place); None allocates."""
+    for t in (audio, audio_len, token_marks, token_gain, out):
+        if t is not None and not t.is_cuda:
+            raise runtime.IspkError("gain_envelope needs GPU tensors; there is no CPU fallback")
+    if audio.ndim != 2 or audio.dtype != torch.float32:
+        raise ValueError(f"audio: fp32 [B, S], got {audio.dtype} {tuple(audio.shape)}")
+    if out is None:
+        out = torch.empty(tuple(audio.shape), dtype=torch.float32, device=audio.device)
+    return runtime.gain_envelope(audio, audio_len, token_marks, token_gain, ramp, out)
+
+
+PROSODY_KEYS = CONTROL_NAMES + ("gain_db",)
+
+
+def prosody_spans(B: int, L: int, spans: Sequence[dict], *, base: Optional[Tensor] = None, word_id: Optional[Tensor] = None,
+                  pitch_std: float = 1.0, device=None):
+    """Host helper: per-token controls and gains from SSML-like spans -> (controls fp32 [B, L, 5] for `infer(controls=)`,
+    gain fp32 [B, L] linear, for `gain_envelope` / `Synthesizer(prosody=True)`).
+
+    Every row of item b starts as `base[b]` (a `make_controls` result; None: neutral) and every gain at 0 dB.  A span is a
+    dict with `item=b`, then either `tokens=(first, stop)` or `words=(first, stop)` (half-open; `words` selects the tokens whose
+    `word_id[b, l]` lies in the range and needs `word_id` int64 [B, L]), and any of duration_factor, pitch_factor, pitch_delta,
+    energy_factor, energy_delta, gain_db.  Spans apply in order, in float64: factors multiply, deltas add (pitch_delta divided
+    by `pitch_std`, as `make_controls(pitch_std=)` does), decibels add; the cast to fp32 - and gain = 10^(dB / 20) - comes last."""
+    B, L = int(B), int(L)
+    if base is None:
+        rows = torch.tensor([1.0, 1.0, 0.0, 1.0, 0.0], dtype=torch.float64).repeat(B, 1)
+    else:
+        if not isinstance(base, Tensor) or tuple(base.shape) != (B, 5):
+            raise ValueError(f"base: a make_controls result [{B}, 5], got {tuple(getattr(base, 'shape', ()))}")
+        rows = base.detach().cpu().to(torch.float64)
+    c = rows[:, None, :].repeat(1, L, 1)
+    db = torch.zeros((B, L), dtype=torch.float64)
+    wid = None
+    if word_id is not None:
+        wid = word_id.detach().cpu()
+        if tuple(wid.shape) != (B, L):
+            raise ValueError(f"word_id: [{B}, {L}], got {tuple(wid.shape)}")
+    for n, span in enumerate(spans):
+        unknown = [k for k in span if k not in PROSODY_KEYS + ("item", "tokens", "words")]
+        if unknown:
+            raise ValueError(f"span {n}: unknown key {unknown[0]!r} (item, tokens | words, {', '.join(PROSODY_KEYS)})")
+        if "item" not in span:
+            raise ValueError(f"span {n}: `item` is missing")
+        b = span["item"]
+        if int(b) != b or not 0 <= b < B:
+            raise ValueError(f"span {n}: item {b!r} outside the batch of {B}")
+        if ("tokens" in span) == ("words" in span):
+            raise ValueError(f"span {n}: exactly one of `tokens` and `words`")
+        key = "tokens" if "tokens" in span else "words"
+        first, stop = span[key]
+        if int(first) != first or int(stop) != stop or not 0 <= first <= stop:
+            raise ValueError(f"span {n}: {key} range {span[key]!r} is not 0 <= first <= stop")
+        if key == "tokens":
+            if stop > L:
+                raise ValueError(f"span {n}: tokens range {span[key]!r} outside the {L} tokens")
+            sel = torch.zeros(L, dtype=torch.bool)
+            sel[int(first):int(stop)] = True
+        else:
+            if wid is None:
+                raise ValueError(f"span {n}: `words` needs word_id")
+            if stop > runtime.MARKS_MAX_WORDS:
+                raise ValueError(f"span {n}: words range {span[key]!r} outside the {runtime.MARKS_MAX_WORDS} words")
+            sel = (wid[int(b)] >= int(first)) & (wid[int(b)] < int(stop))
+        for k, v in span.items():
+            if k not in PROSODY_KEYS:
+                continue
+            v = float(v)
+            if k == "gain_db":
+                db[int(b), sel] += v
+                continue
+            col = CONTROL_NAMES.index(k)
+            if k.endswith("_factor"):
+                c[int(b), sel, col] *= v
+            else:
+                c[int(b), sel, col] += v / float(pitch_std) if k == "pitch_delta" else v
+    gain = torch.pow(torch.tensor(10.0, dtype=torch.float64), db / 20.0)
+    return c.to(dtype=torch.float32, device=device), gain.to(dtype=torch.float32, device=device)
+
+
 def cues(word_marks: Tensor, doc: Tensor, labels: Sequence[Sequence[str]], sample_rate: float) -> list:
     """Host helper, run after the graph: ONE device read (word_marks and doc are copied to the host here).  word_marks int64
     [B, W, 2] of `speech_marks(joined=...)`, doc int64 [B], labels[b][w] the text of word w of item b (shorter rows: the rest
@@ -215,13 +306,17 @@ class Synthesizer:
     marks (one more launch: r["token_marks"] int64 [B, L, 2] and r["word_marks"] int64 [B, words, 2], sample ranges inside the
     final documents; `word_id` int64 [B, L] of a call names each token's word, none when it is not given; the launch's other
     inputs come along as r["duration"], r["item_audio_len"], r["item_bounds"], r["joined_len"], r["doc_bounds"]).  A call copies
+    With `prosody=True` (word-level prosody; `prosody_spans` builds both inputs) `controls` has one row per TOKEN - a call takes
+    fp32 [B, L, 5], or [B, 5] which is copied to every token of an item - and `gain` fp32 [B, L] (None: ones) is a linear gain
+    per token: behind the denoiser one `ispk_speech_marks` launch in item coordinates (r["item_token_marks"]) and one
+    `gain_envelope` launch with ramps of `ramp` samples, into a buffer of its own, in front of the item conditioner.  A call copies
     its arguments into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
     one Synthesizer serves one bucket shape (B sentences of L tokens into D documents of S_out samples)."""
 
     def __init__(self, model, vocoder, *, batch: int, tokens: int, frames: int, docs: int, doc_samples: int, steps: int = 4,
                  denoiser=None, item_conditioner: Optional[AudioConditioner] = None,
                  doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0,
-                 marks: bool = False, words: int = 0):
+                 marks: bool = False, words: int = 0, prosody: bool = False, ramp: int = 128):
         B, L, M, D, S_out = int(batch), int(tokens), int(frames), int(docs), int(doc_samples)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -237,6 +332,11 @@ class Synthesizer:
             raise ValueError(f"Synthesizer: words={words} (0 .. {runtime.MARKS_MAX_WORDS}, only with marks=True)")
         if self.marks and L > runtime.MARKS_MAX_TOKENS:
             raise ValueError(f"Synthesizer: marks serve at most {runtime.MARKS_MAX_TOKENS} tokens, got {L}")
+        self.prosody, self.ramp = bool(prosody), int(ramp)
+        if self.prosody and L > runtime.MARKS_MAX_TOKENS:
+            raise ValueError(f"Synthesizer: prosody serves at most {runtime.MARKS_MAX_TOKENS} tokens, got {L}")
+        if self.prosody and (self.ramp != ramp or not 0 <= self.ramp < runtime.GAIN_MAX_RAMP):
+            raise ValueError(f"Synthesizer: ramp is an integer in [0, 2^22), got {ramp!r}")
         self.multi_speaker = getattr(model, "speaker_embedding", None) is not None
         i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64, device=dev)      # noqa: E731
         self.static = {"text": i64(B, L), "text_len": torch.full((B,), L, dtype=torch.int64, device=dev), "doc": i64(B),
@@ -261,10 +361,17 @@ class Synthesizer:
             doc_conditioner.device_tables(dev)
         self._pcm = torch.empty((D, S_out), dtype=torch.int16, device=dev)
         self._marks = None
-        if self.marks:
+        if self.marks or self.prosody:
             if S % M:
-                raise ValueError(f"Synthesizer: marks need a vocoder with a whole hop, got {S} samples for {M} frames")
+                raise ValueError(f"Synthesizer: marks and prosody need a vocoder with a whole hop, got {S} samples for {M} frames")
             self._hop = S // M
+        self._shaped = self._item_marks = None
+        if self.prosody:      # one control row and one gain per token; the envelope writes a buffer of its own
+            self.static["controls"] = self.static["controls"][:, None, :].repeat(1, L, 1)
+            self.static["gain"] = torch.ones((B, L), dtype=torch.float32, device=dev)
+            self._item_marks = torch.empty((B, L, 2), dtype=torch.int64, device=dev)
+            self._shaped = torch.empty_like(self._wav[0])
+        if self.marks:
             self.static["word_id"] = torch.full((B, L), -1, dtype=torch.int64, device=dev)
             self._marks = marks_outputs(B, L, self.words, dev)
         self._graph = graph.GraphedCall(self._chain)
@@ -280,6 +387,11 @@ class Synthesizer:
             audio, audio_len = self.vocoder(mel, ao.dec_lengths, out=self._wav)
             if self.denoiser is not None:
                 audio, _ = self.denoiser(audio, audio_len, out=self._clean)
+            if self.prosody:
+                # where every token lies in its own item (no bounds, no join), then the per-token gains over those ranges
+                runtime.speech_marks(ao.duration, s["text_len"], audio_len, self._item_marks, None, self._hop, audio.shape[1],
+                                     not self.model.temporal_adaptor.soft_duration)
+                audio = runtime.gain_envelope(audio, audio_len, self._item_marks, s["gain"], self.ramp, self._shaped)
             bounds = gain = None
             if self.item_conditioner is not None:
                 c, o = self.item_conditioner, self._item
@@ -296,6 +408,8 @@ class Synthesizer:
             pcm = to_pcm16(doc_audio, doc_len, dither=self.dither, seed=self.seed, out=self._pcm)
         out = dict(pcm=pcm, audio=doc_audio, audio_len=doc_len, wanted_len=j["wanted_len"], item_offset=j["item_offset"],
                    item_len=j["item_len"], frames_wanted=frames_wanted, dec_lengths=ao.dec_lengths)
+        if self.prosody:
+            out["item_token_marks"] = self._item_marks
         if self.marks:
             # the last launch of the chain, fed by what the stages above consumed and wrote; its inputs are handed out too
             m, doc_bounds = self._marks, self._doc["bounds"] if self._doc is not None else None
@@ -308,6 +422,8 @@ class Synthesizer:
 
     def _checked(self, name: str, t: Tensor) -> Tensor:
         want = self.static[name]
+        if name == "controls" and self.prosody and isinstance(t, Tensor) and t.ndim == 2:
+            want = want[:, 0]                         # [B, 5]: one row per item, copied to all of its tokens
         if not isinstance(t, Tensor):
             raise ValueError(f"{name}: a tensor {tuple(want.shape)} {want.dtype}")
         if not t.is_cuda:
@@ -318,8 +434,13 @@ class Synthesizer:
 
     def __call__(self, text: Tensor, text_len: Tensor, doc: Tensor, pos: Tensor, pause: Optional[Tensor] = None,
                  controls: Optional[Tensor] = None, speaker: Optional[Tensor] = None,
-                 flow_noise: Optional[Tensor] = None, word_id: Optional[Tensor] = None) -> SynthesisResult:
+                 flow_noise: Optional[Tensor] = None, word_id: Optional[Tensor] = None,
+                 gain: Optional[Tensor] = None) -> SynthesisResult:
         given = {"text": text, "text_len": text_len, "doc": doc, "pos": pos}
+        if gain is not None:
+            if not self.prosody:
+                raise ValueError("gain: the Synthesizer was built without prosody (prosody=True)")
+            given["gain"] = gain
         if word_id is not None:
             if not self.words:
                 raise ValueError("word_id: the Synthesizer was built without words (marks=True, words=W)")
@@ -334,11 +455,14 @@ class Synthesizer:
         for name, t in given.items():
             self._checked(name, t)
         for name, t in given.items():
-            self.static[name].copy_(t)
+            self.static[name].copy_(t[:, None, :] if t.ndim + 1 == self.static[name].ndim else t)
         if pause is None:
             self.static["pause"].zero_()
         if controls is None:
-            self.static["controls"].copy_(self._default_controls())
+            d = self._default_controls()
+            self.static["controls"].copy_(d[:, None, :] if self.prosody else d)
+        if self.prosody and gain is None:
+            self.static["gain"].fill_(1.0)
         if flow_noise is None:
             self.static["flow_noise"].normal_()
         if self.marks and word_id is None:
