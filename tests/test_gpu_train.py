@@ -1,10 +1,12 @@
 """Training-step kernels (first cut) against the oracle: torch autograd over the oracle's functions for the
 gradients, torch.optim.AdamW + clip_grad_norm_ in the reference's grouping for the optimizer.  Tolerances are written per
 test (floating point: fp32 kernels against an fp32 / fp64 CPU computation)."""
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import dropout_reference as dr
 from isp_tts_amd import runtime, synth, train
 from isp_tts_amd.modules.transformer import Transformer
 from oracle import acoustic_oracle as orc
@@ -1038,7 +1040,13 @@ def test_dropout_seed_source_changes_the_masks_at_run_time():
     again = runtime.gelu(u, 0.3, 77)
     assert torch.equal(a1, a1b) and torch.equal(again, base)
     assert not torch.equal(a1, a2) and not torch.equal(a1, base) and not torch.equal(o2, o3)
-    assert torch.equal(d1 == 0, a1 == 0) or ((d1 == 0) ^ (a1 == 0)).float().mean() < 1e-3     # same mask forward and backward
+    # same mask forward and backward, exactly: the host mirror's for (seed 77, word 1).  Dropped -> 0; kept -> nonzero wherever
+    # the float64 value exceeds the fp32 pair's bars (test_gelu_forward_backward), so that it cannot have rounded to 0
+    kept = torch.from_numpy(dr.keep_mask(77, u.numel(), 0.3, word=1)).view_as(u)
+    u64, s = u.double().cpu().numpy(), dr.inv_keep(0.3)
+    for got, ref, bar in ((a1, dr.gelu(u64) * s, 1e-6 * s * np.maximum(np.abs(u64), 1.0)), (d1, dr.gelu_grad(u64) * s, 2e-6 * s)):
+        zero = (got == 0).cpu()
+        assert bool(zero[~kept].all()) and not bool(zero[kept & torch.from_numpy(np.abs(ref) > bar)].any())
     keep = (a2 != 0).float().mean().item()
     assert abs(keep - 0.7) < 0.02
 
@@ -1182,8 +1190,12 @@ def test_gelu_bf16_forms_match_the_fp32_forms():
         err = (got16.float() - want32).abs()
         bound = want32.abs() * 2.0 ** -8 + 1e-6
         assert bool((err <= bound).all()), f"{what}: {float((err - bound).max()):.3e} over one bf16 rounding"
-        assert torch.equal(got16 == 0, want32.to(torch.bfloat16) == 0) or ((got16 == 0) ^ (want32 == 0)).float().mean() < 1e-3   # (far negative inputs: 0 vs a denormal-sized value)
+        # the zero pattern, exactly: dropped by the host mirror -> 0 in both; kept and over the bound -> nonzero (far negative
+        # inputs give 0 in one form and a denormal-sized value in the other: both are under the bound)
+        assert not bool(got16[~kept].any()) and not bool(want32[~kept].any()), f"{what}: a dropped element is not 0"
+        assert bool((got16[kept & (want32.abs() > bound)] != 0).all()), f"{what}: a kept element over the bound is 0"
     for p, seed in ((0.0, 0), (0.1, 1234)):
+        kept = torch.from_numpy(dr.keep_mask(seed, u.numel(), p)).view_as(u).to(DEV)
         a32 = runtime.gelu(u, p, seed)
         one_ulp(runtime.gelu(u, p, seed, out_dtype=torch.bfloat16), a32, "gelu -> bf16")
         da16 = da.to(torch.bfloat16)
