@@ -1244,6 +1244,36 @@ int32_t ispk_gain_envelope_f32(const float* audio, int64_t ld_audio, const int64
                                const float* token_gain, int32_t ramp, float* out, int64_t ld_out, int32_t B, int32_t L,
                                int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * True-peak look-ahead limiter (csrc/limiter.hip, isp_tts_amd/data/condition.py): the last fp32 stage in front of ispk_pcm16.
+ * One kernel launch behind two 32-bit memsets of true_peak and reduction on the stream; no host read.
+ * audio fp32 [B][S] at ld_audio.  len = audio_len[b] (NULL: S; a value outside [0, S] counts as 0).  With bounds int64 [B][2]
+ * the kept samples are x[0, n) = audio[b][start, min(end, len)) (a pair that is not 0 <= start <= end <= S keeps nothing),
+ * without them audio[b][0, len).  Samples outside count as zero; nothing outside the kept range is read.  g = gain[b] (NULL: 1),
+ * c = ceiling > 0 (linear), L = lookahead in samples.  taps fp32 [4][12], made in float64 by the host (data.true_peak_taps):
+ *   h[p][k] = sinc(t) cos^2(pi t / 12) for |t| < 6, else 0, with t = k - p / 4, k = -5 .. 6 (column k + 5); phase 0 is the identity.
+ *   y[4 i + p] = sum_k h[p][k] fp32(g x[i + k]), fp32 FMAs in the order k = -5 .. 6;  e[i] = max_p |y[4 i + p]|
+ *   r[i] = c / e[i] where e[i] > c, else 1; 1 outside [0, n)
+ *   m[j] = min over |k| <= L of r[j + k], j in [-L, n + L)   (the minimum itself is extended, not padded with ones: a padded m
+ *          lets the gain rise above r within L samples of an item's edges)
+ *   s[i] = 1 - sum over |k| <= L of w[k] (1 - m[i + k]), w[k] = cos^2(pi k / (2 (L + 1))) / (L + 1), which sum to 1; the sum
+ *          runs in float64.  s is exactly 1 where no r < 1 lies within 2 L samples, and s[i] <= r[i] everywhere.
+ *   out[b][i] = clamp(fp32(fp32(g x[i]) s[i]), -c, c) for i < n, 0 for n <= i < S  (out fp32 [B][S] at ld_out); out_len[b] = n
+ *   true_peak[b] = max_i e[i], of the gained input, 0 for an empty item;  reduction[b] = fp32(min_i s[i]), 1 when untouched or empty
+ * Where s[i] is 1 the output has the bits of ispk_audio_apply_f32 with the same bounds and gain.  out NULL (then out_len NULL
+ * too): the launch only measures; with reduction NULL as well it stops behind the envelope.  Both per-item results are folded
+ * across an item's tiles with integer atomic max / min on the bit patterns of non-negative floats: the order does not matter,
+ * an item's bits depend on that item alone, repeated calls and graph replays repeat theirs.  Grid (ceil(S /
+ * ispk_limit_tile_samples()), B); 16-byte loads for an item whose first kept sample is 16-byte aligned (base, row stride and
+ * start), 16-byte stores when out's base is and its stride is a multiple of four floats.
+ * Refused: B > 65535, S outside [0, 2^24], lookahead outside 1 .. 256, a ceiling that is not positive and finite, a row stride
+ * below S, out overlapping audio (E_SHAPE); NULL audio, taps or true_peak, out without reduction, out_len without out (E_NULL);
+ * true_peak or reduction off a 4-byte boundary (E_ALIGN).  B = 0 is a no-op. */
+int32_t ispk_limit_tile_samples(void);
+int32_t ispk_limit_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const int64_t* bounds, const float* gain,
+                       const float* taps, float ceiling, int32_t lookahead, float* out, int64_t ld_out, int64_t* out_len,
+                       float* true_peak, float* reduction, int32_t B, int32_t S, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

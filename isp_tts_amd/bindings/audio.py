@@ -1,6 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
 the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip) with their denoiser
-(csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip)."""
+(csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip); the document join, speech marks, gain envelope and true-peak limiter
+(csrc/join.hip, marks.hip, prosody.hip, limiter.hip)."""
 from typing import Optional
 
 import torch
@@ -17,7 +18,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES", "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP",
            "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
            "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio",
-           "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope"]
+           "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope",
+           "LIMIT_TILE_SAMPLES", "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -743,3 +745,62 @@ def gain_envelope(audio: Tensor, audio_len: Tensor, token_marks: Tensor, token_g
                 ld(audio), audio_len.data_ptr(), token_marks.data_ptr(), token_gain.data_ptr(), int(ramp), out.data_ptr(), ld(out), B,
                 L, S, _rt._stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ true-peak limiter
+LIMIT_TILE_SAMPLES = 4096     # ispk_limit_tile_samples(): output samples of one item per workgroup
+LIMIT_MAX_LOOKAHEAD = 256     # samples
+LIMIT_TAPS = (4, 12)          # the interpolator: four phases of twelve taps
+
+
+def limit(audio: Tensor, audio_len: Optional[Tensor], taps: Tensor, ceiling: float, lookahead: int, gain: Optional[Tensor] = None,
+          bounds: Optional[Tensor] = None, out: Optional[Tensor] = None, out_len: Optional[Tensor] = None,
+          true_peak: Optional[Tensor] = None, reduction: Optional[Tensor] = None, measure_only: bool = False):
+    """ispk_limit_f32, one launch, no host read: the look-ahead limiter with a 4x oversampled (true-peak) detector on fp32 audio
+    [B, S] (unit stride on S, any row stride) with int64 lengths [B] (None: S each), optional bounds int64 [B, 2] and gain fp32
+    [B] (an AudioConditioner's), the interpolator taps fp32 [4, 12] (data.true_peak_taps), the linear ceiling and the look-ahead
+    in samples (include/ispk.h has the arithmetic) -> (out fp32 [B, S], out_len int64 [B], true_peak fp32 [B], reduction fp32
+    [B]).  `out` may not overlap `audio`.  measure_only: nothing but true_peak is computed or written -> (None, None, true_peak,
+    None)."""
+    _rt._dev(audio, audio_len, taps, gain, bounds, out, out_len, true_peak, reduction)
+    B, S = _mono_batch(audio, audio_len)
+    if taps.dtype != torch.float32 or tuple(taps.shape) != LIMIT_TAPS or not taps.is_contiguous():
+        raise ValueError(f"taps: contiguous fp32 {list(LIMIT_TAPS)}, got {taps.dtype} {tuple(taps.shape)}")
+    if int(lookahead) != lookahead or not 1 <= lookahead <= LIMIT_MAX_LOOKAHEAD:
+        raise ValueError(f"lookahead is an integer in [1, {LIMIT_MAX_LOOKAHEAD}] samples, got {lookahead!r}")
+    if not 0.0 < float(ceiling) < float("inf"):
+        raise ValueError(f"ceiling is positive and finite (linear), got {ceiling!r}")
+    if gain is not None:
+        _out_like("gain", gain, torch.float32, (B,))
+    if bounds is not None:
+        _out_like("bounds", bounds, torch.int64, (B, 2))
+        if not bounds.is_contiguous():
+            raise ValueError("bounds: contiguous int64 [B, 2]")
+    dev = audio.device
+    true_peak = torch.empty((B,), dtype=torch.float32, device=dev) if true_peak is None else true_peak
+    _out_like("true_peak", true_peak, torch.float32, (B,))
+    if measure_only:
+        if out is not None or out_len is not None or reduction is not None:
+            raise ValueError("measure_only writes true_peak alone: out, out_len and reduction stay None")
+    else:
+        out = torch.empty((B, S), dtype=torch.float32, device=dev) if out is None else out
+        out_len = torch.empty((B,), dtype=torch.int64, device=dev) if out_len is None else out_len
+        reduction = torch.empty((B,), dtype=torch.float32, device=dev) if reduction is None else reduction
+        if out.ndim != 2:
+            raise ValueError(f"out: fp32 [{B}, {S}], got {tuple(out.shape)}")
+        _out_like("out", out, torch.float32, (B, S))
+        _out_like("out_len", out_len, torch.int64, (B,))
+        _out_like("reduction", reduction, torch.float32, (B,))
+        if B > 1 and out.stride(0) < S:
+            raise ValueError(f"out: rows overlap (row stride {out.stride(0)} < {S})")
+    if B > 1 and audio.stride(0) < S:
+        raise ValueError(f"audio: rows overlap (row stride {audio.stride(0)} < {S})")
+    if B == 0:
+        return out, out_len, true_peak, reduction
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), S)      # noqa: E731
+    # the envelope's 36 FMAs a sample; the smoothing sum only runs in tiles that hold a limited sample
+    _rt._launch("limit_kernel", 72.0 * B * S, (4.0 if measure_only else 8.0) * B * S, _rt.lib().ispk_limit_f32, audio.data_ptr(),
+                ld(audio), _rt._ptr(audio_len), _rt._ptr(bounds), _rt._ptr(gain), taps.data_ptr(), float(ceiling), int(lookahead),
+                _rt._ptr(out), 0 if out is None else ld(out), _rt._ptr(out_len), true_peak.data_ptr(), _rt._ptr(reduction), B, S,
+                _rt._stream())
+    return out, out_len, true_peak, reduction

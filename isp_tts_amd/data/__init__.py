@@ -1,5 +1,5 @@
 from .features import (AcousticFeatures, collate_audio, melscale_fbanks, pack_filterbank, pitch_frames,  # noqa: F401
                        twiddles, yin_lags)
-from .condition import AudioConditioner, k_weighting, meter_table, to_pcm16  # noqa: F401
+from .condition import AudioConditioner, Limiter, k_weighting, meter_table, to_pcm16, true_peak_taps  # noqa: F401
 from .resample import AudioFrontEnd, Resampler, compact_taps, resampled_length, sinc_hann_taps  # noqa: F401
 from .stats import DatasetStats, DatasetStatsResult, FeatureStats  # noqa: F401

@@ -65,11 +65,98 @@ def meter_table(sample_rate: int) -> np.ndarray:
     return t
 
 
+def true_peak_taps() -> np.ndarray:
+    """float64 [4, 12]: the 4x interpolator of the true-peak detector.  Row p, column k + 5 holds h[p][k] = sinc(t) cos^2(pi t /
+    12) for |t| < 6, else 0, with t = k - p / 4, k = -5 .. 6: a windowed sinc of six samples to each side.  Row 0 is exactly
+    the identity; rows 1 and 3 mirror each other.  The kernel takes the table as fp32."""
+    t = np.arange(-5, 7, dtype=np.float64)[None, :] - np.arange(4, dtype=np.float64)[:, None] / 4.0
+    h = np.where(np.abs(t) < 6.0, np.sinc(t) * np.cos(np.pi * t / 12.0) ** 2, 0.0)
+    h[0] = 0.0
+    h[0, 5] = 1.0            # sinc of a non-zero integer is zero up to an ulp of pi: made exact
+    return h
+
+
+class Limiter:
+    """A look-ahead limiter with a true-peak (4x oversampled) detector, one launch of ispk_limit_f32 (csrc/limiter.hip) with
+    no ATen compute op and no host read: the gain is pulled down, smoothly and ahead of time, only over the stretches whose
+    inter-sample peak would exceed the ceiling; everything else keeps its bits.
+
+    lim = Limiter(sample_rate, ceiling_db=-1.0, lookahead_ms=1.5)
+    r = lim(audio, audio_len, gain=None, bounds=None)
+      audio, audio_len   fp32 [B, S] (unit stride on S, any row stride) and int64 [B] on the GPU; a length outside [0, S] counts as 0
+      gain, bounds       fp32 [B] and int64 [B, 2], an AudioConditioner's: the item is audio[start, end) times gain
+      r["audio"]         fp32 [B, S]: clamp(gain x s, -ceiling, ceiling), zeros behind the item;  r["audio_len"] int64 [B]
+      r["true_peak"]     fp32 [B]: the largest 4x interpolated magnitude of gain x, BEFORE limiting (0 for an empty item)
+      r["reduction"]     fp32 [B]: the smallest gain s applied (1.0: untouched)
+    With e[i] the largest magnitude among sample i and its three interpolated successors, r = ceiling / e where e exceeds the
+    ceiling (else 1), m the minimum of r over +-lookahead samples and s = 1 - sum w (1 - m) over another +-lookahead with a
+    raised-cosine w that sums to one (include/ispk.h has it in full): s <= r at every sample, so no output SAMPLE exceeds the
+    ceiling, and s is exactly 1 further than 2 lookahead from anything limited.  `.lookahead` is the rounded sample count
+    (1 .. 256), `.ceiling` the linear ceiling as the kernel takes it (rounded to fp32)."""
+
+    def __init__(self, sample_rate: int, ceiling_db: float = -1.0, lookahead_ms: float = 1.5):
+        if int(sample_rate) != sample_rate or sample_rate <= 0:
+            raise ValueError(f"sample_rate is a positive integer, got {sample_rate!r}")
+        if not math.isfinite(ceiling_db):
+            raise ValueError(f"ceiling_db is finite, got {ceiling_db!r}")
+        if not (lookahead_ms > 0 and math.isfinite(lookahead_ms)):
+            raise ValueError(f"lookahead_ms > 0, got {lookahead_ms!r}")
+        self.sample_rate, self.ceiling_db, self.lookahead_ms = int(sample_rate), float(ceiling_db), float(lookahead_ms)
+        self.ceiling = float(np.float32(10.0 ** (self.ceiling_db / 20.0)))
+        if not (self.ceiling > 0 and math.isfinite(self.ceiling)):
+            raise ValueError(f"ceiling_db {ceiling_db!r} is not a positive finite fp32 ceiling")
+        self.lookahead = int(round(self.lookahead_ms * 1e-3 * self.sample_rate))
+        if not 1 <= self.lookahead <= runtime.LIMIT_MAX_LOOKAHEAD:
+            raise ValueError(f"lookahead_ms {lookahead_ms!r} is {self.lookahead} samples at {self.sample_rate} Hz: 1 .. "
+                             f"{runtime.LIMIT_MAX_LOOKAHEAD}")
+        self.taps = torch.from_numpy(true_peak_taps().astype(np.float32))
+        self._on: dict = {}
+
+    def device_tables(self, device) -> Tensor:
+        """The interpolator taps (fp32 [4, 12]) on `device`, copied once per device (before, not inside, a graph capture)."""
+        device = torch.device(device)
+        t = self._on.get(device)
+        if t is None:
+            t = self._on[device] = self.taps.to(device)
+        return t
+
+    def empty_outputs(self, B: int, S: int, device) -> dict:
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)      # noqa: E731
+        return dict(audio=e((B, S), torch.float32), audio_len=e((B,), torch.int64), true_peak=e((B,), torch.float32),
+                    reduction=e((B,), torch.float32))
+
+    def _checked(self, audio: Tensor, audio_len: Tensor, gain: Optional[Tensor], bounds: Optional[Tensor]) -> None:
+        if audio.ndim != 2 or audio.dtype != torch.float32 or audio.stride(-1) != 1:
+            raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                             f"{tuple(audio.stride())}")
+        if audio_len.dtype != torch.int64 or audio_len.shape != (audio.shape[0],):
+            raise ValueError(f"audio_len: int64 [{audio.shape[0]}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+        for t in (audio, audio_len, gain, bounds):
+            if t is not None and not t.is_cuda:
+                raise runtime.IspkError("Limiter needs GPU tensors; there is no CPU fallback")
+
+    def __call__(self, audio: Tensor, audio_len: Tensor, gain: Optional[Tensor] = None, bounds: Optional[Tensor] = None,
+                 out: Optional[dict] = None) -> dict:
+        self._checked(audio, audio_len, gain, bounds)
+        if out is None:
+            out = self.empty_outputs(audio.shape[0], audio.shape[1], audio.device)
+        runtime.limit(audio, audio_len, self.device_tables(audio.device), self.ceiling, self.lookahead, gain, bounds, out["audio"],
+                      out["audio_len"], out["true_peak"], out["reduction"])
+        return out
+
+    def true_peak(self, audio: Tensor, audio_len: Tensor, gain: Optional[Tensor] = None) -> Tensor:
+        """fp32 [B]: the true peak of gain * audio - the same launch without an output; no audio is written."""
+        self._checked(audio, audio_len, gain, None)
+        return runtime.limit(audio, audio_len, self.device_tables(audio.device), self.ceiling, self.lookahead, gain,
+                             measure_only=True)[2]
+
+
 class AudioConditioner:
     """Trim, measure and normalise a padded mono batch in four launches (three of ispk_audio_measure_f64, one of
     ispk_audio_apply_f32), with no ATen compute op and no host read.
 
-    cond = AudioConditioner(sample_rate, target_lufs=-23.0, peak_limit=10 ** (-1 / 20), top_db=60.0, pad_frames=0, ref="max")
+    cond = AudioConditioner(sample_rate, target_lufs=-23.0, peak_limit=10 ** (-1 / 20), top_db=60.0, pad_frames=0, ref="max",
+                            limiter=None)
     r = cond(audio, audio_len)
       audio      fp32 [B, S] on the GPU (unit stride on S, any row stride); nothing at or past audio_len[b] is read
       audio_len  int64 [B] on the GPU; a length below 0 or above S counts as 0
@@ -83,10 +170,18 @@ class AudioConditioner:
                       target_lufs=None (the shift alone).
       r["audio"]      fp32 [B, S]: gain * audio[start + i] for i < end - start, then zeros; r["audio_len"] int64 [B] = end - start.
     Filter state, block sums and gates are float64; an item's results do not depend on the batch it is in, and repeated
-    calls and graph replays are bit-identical.  8 kHz <= sample_rate <= 768 kHz, a multiple of 10 (the 100 ms step)."""
+    calls and graph replays are bit-identical.  8 kHz <= sample_rate <= 768 kHz, a multiple of 10 (the 100 ms step).
+
+    With `limiter=Limiter(...)` the loudness gain is not capped by the sample peak (peak_limit is not used): r["gain"] is
+    10^((target_lufs - loudness) / 20) itself, and one ispk_limit_f32 launch with the bounds and that gain takes the place of
+    ispk_audio_apply_f32 - still four launches.  r["audio"] is then the limited audio, and r gains r["true_peak"] (fp32 [B], of
+    the gained item before limiting) and r["reduction"] (fp32 [B], the smallest limiter gain; 1.0: untouched).  r["loudness"]
+    stays the measured INPUT loudness; limiting lowers the loudness that is achieved slightly below the target wherever it
+    acts, and nothing iterates on that.  limiter=None is the conditioner as it was, bit for bit."""
 
     def __init__(self, sample_rate: int, target_lufs: Optional[float] = -23.0, peak_limit: float = 10 ** (-1 / 20),
-                 top_db: Optional[float] = 60.0, pad_frames: int = 0, ref: Union[str, float] = "max"):
+                 top_db: Optional[float] = 60.0, pad_frames: int = 0, ref: Union[str, float] = "max",
+                 limiter: Optional[Limiter] = None):
         if int(sample_rate) != sample_rate or sample_rate <= 0:
             raise ValueError(f"sample_rate is a positive integer, got {sample_rate!r}")
         if sample_rate % 10:
@@ -114,6 +209,11 @@ class AudioConditioner:
             self.trim_mode, self.trim_threshold = 1, 10.0 ** (-self.top_db / 10.0)
         else:
             self.trim_mode, self.trim_threshold = 2, self.ref * 10.0 ** (-self.top_db / 10.0)
+        if limiter is not None and not isinstance(limiter, Limiter):
+            raise ValueError(f"limiter is a Limiter or None, got {type(limiter).__name__}")
+        if limiter is not None and limiter.sample_rate != self.sample_rate:
+            raise ValueError(f"limiter: built for {limiter.sample_rate} Hz, the conditioner for {self.sample_rate} Hz")
+        self.limiter = limiter
         self.table = torch.from_numpy(meter_table(self.sample_rate))
         self._on: dict = {}
 
@@ -123,12 +223,17 @@ class AudioConditioner:
         t = self._on.get(device)
         if t is None:
             t = self._on[device] = self.table.to(device)
+        if self.limiter is not None:
+            self.limiter.device_tables(device)
         return t
 
     def empty_outputs(self, B: int, S: int, device) -> dict:
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
-        return dict(audio=e((B, S), torch.float32), audio_len=e((B,), torch.int64), bounds=e((B, 2), torch.int64),
-                    loudness=e((B,), torch.float64), peak=e((B,), torch.float32), gain=e((B,), torch.float32))
+        out = dict(audio=e((B, S), torch.float32), audio_len=e((B,), torch.int64), bounds=e((B, 2), torch.int64),
+                   loudness=e((B,), torch.float64), peak=e((B,), torch.float32), gain=e((B,), torch.float32))
+        if self.limiter is not None:
+            out.update(true_peak=e((B,), torch.float32), reduction=e((B,), torch.float32))
+        return out
 
     def __call__(self, audio: Tensor, audio_len: Tensor, out: Optional[dict] = None) -> dict:
         if audio.ndim != 2 or audio.dtype != torch.float32 or audio.stride(-1) != 1:
@@ -143,8 +248,14 @@ class AudioConditioner:
         table = self.device_tables(audio.device)
         runtime.audio_measure(audio, audio_len, table, self.sample_rate, self.trim_mode, self.trim_threshold, self.pad_frames,
                               int(self.target_lufs is not None), self.target_lufs if self.target_lufs is not None else 0.0,
-                              self.peak_limit, out["bounds"], out["loudness"], out["peak"], out["gain"])
-        runtime.audio_apply(audio, out["bounds"], out["gain"], out["audio"], out["audio_len"])
+                              self.peak_limit if self.limiter is None else math.inf, out["bounds"], out["loudness"], out["peak"],
+                              out["gain"])
+        if self.limiter is None:
+            runtime.audio_apply(audio, out["bounds"], out["gain"], out["audio"], out["audio_len"])
+        else:      # the gain uncapped (no peak limit binds), then only the stretches over the ceiling pulled down
+            lim = self.limiter
+            runtime.limit(audio, audio_len, lim.device_tables(audio.device), lim.ceiling, lim.lookahead, out["gain"], out["bounds"],
+                          out["audio"], out["audio_len"], out["true_peak"], out["reduction"])
         return out
 
 

@@ -25,7 +25,7 @@ import torch
 from torch import Tensor
 
 from . import graph, runtime
-from .data.condition import AudioConditioner, to_pcm16
+from .data.condition import AudioConditioner, Limiter, to_pcm16
 
 CONTROL_NAMES = ("duration_factor", "pitch_factor", "pitch_delta", "energy_factor", "energy_delta")
 
@@ -309,14 +309,18 @@ class Synthesizer:
     With `prosody=True` (word-level prosody; `prosody_spans` builds both inputs) `controls` has one row per TOKEN - a call takes
     fp32 [B, L, 5], or [B, 5] which is copied to every token of an item - and `gain` fp32 [B, L] (None: ones) is a linear gain
     per token: behind the denoiser one `ispk_speech_marks` launch in item coordinates (r["item_token_marks"]) and one
-    `gain_envelope` launch with ramps of `ramp` samples, into a buffer of its own, in front of the item conditioner.  A call copies
+    `gain_envelope` launch with ramps of `ramp` samples, into a buffer of its own, in front of the item conditioner.
+    With `limiter=Limiter(...)` (data.condition) one ispk_limit_f32 launch on the final documents, behind `doc_conditioner` and in
+    front of to_pcm16, pulls down what crossfades, gains and the document loudness pushed over the ceiling instead of leaving it
+    to PCM16's clamp: r["audio"] is the limited audio, r["true_peak"] and r["reduction"] fp32 [D] say per document what came in
+    and how far the gain went down; lengths and marks do not change.  A call copies
     its arguments into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
     one Synthesizer serves one bucket shape (B sentences of L tokens into D documents of S_out samples)."""
 
     def __init__(self, model, vocoder, *, batch: int, tokens: int, frames: int, docs: int, doc_samples: int, steps: int = 4,
                  denoiser=None, item_conditioner: Optional[AudioConditioner] = None,
                  doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0,
-                 marks: bool = False, words: int = 0, prosody: bool = False, ramp: int = 128):
+                 marks: bool = False, words: int = 0, prosody: bool = False, ramp: int = 128, limiter: Optional[Limiter] = None):
         B, L, M, D, S_out = int(batch), int(tokens), int(frames), int(docs), int(doc_samples)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -359,6 +363,12 @@ class Synthesizer:
         if doc_conditioner is not None:
             self._doc = doc_conditioner.empty_outputs(D, S_out, dev)
             doc_conditioner.device_tables(dev)
+        if limiter is not None and not isinstance(limiter, Limiter):
+            raise ValueError(f"Synthesizer: limiter is a data.Limiter or None, got {type(limiter).__name__}")
+        self.limiter, self._limited = limiter, None
+        if limiter is not None:      # the last fp32 stage, into a buffer of its own
+            self._limited = limiter.empty_outputs(D, S_out, dev)
+            limiter.device_tables(dev)
         self._pcm = torch.empty((D, S_out), dtype=torch.int16, device=dev)
         self._marks = None
         if self.marks or self.prosody:
@@ -405,9 +415,16 @@ class Synthesizer:
             if self.doc_conditioner is not None:
                 r = self.doc_conditioner(doc_audio, doc_len, out=self._doc)
                 doc_audio, doc_len = r["audio"], r["audio_len"]
+            limited = None
+            if self.limiter is not None:
+                # the lengths do not change (no bounds here), so the marks below stay where they are
+                limited = self.limiter(doc_audio, doc_len, out=self._limited)
+                doc_audio = limited["audio"]
             pcm = to_pcm16(doc_audio, doc_len, dither=self.dither, seed=self.seed, out=self._pcm)
         out = dict(pcm=pcm, audio=doc_audio, audio_len=doc_len, wanted_len=j["wanted_len"], item_offset=j["item_offset"],
                    item_len=j["item_len"], frames_wanted=frames_wanted, dec_lengths=ao.dec_lengths)
+        if limited is not None:
+            out.update(true_peak=limited["true_peak"], reduction=limited["reduction"])
         if self.prosody:
             out["item_token_marks"] = self._item_marks
         if self.marks:
