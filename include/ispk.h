@@ -1274,6 +1274,40 @@ int32_t ispk_limit_f32(const float* audio, int64_t ld_audio, const int64_t* audi
                        const float* taps, float ceiling, int32_t lookahead, float* out, int64_t ld_out, int64_t* out_len,
                        float* true_peak, float* reduction, int32_t B, int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Equalizer (csrc/equalizer.hip, isp_tts_amd/data/equalize.py): a cascade of 1 <= N <= 8 biquads in float64, the stage of the
+ * audio chain that changes the spectrum.  At most two kernel launches, no atomics, no host read.
+ * audio fp32 [B][S], unit stride on S, row stride ld_audio >= S.  len = audio_len[b], int64; a length below 0 or above S
+ * counts as 0.  sos float64 [N][5] = (b0, b1, b2, a1, a2) with a0 = 1.  Each section is transposed direct form II in float64:
+ *   y  = fma(b0, x, s0)
+ *   s0 = fma(-a1, y, fma(b1, x, s1))
+ *   s1 = fma(-a2, y, b2 * x)
+ * All states are zero at sample 0 of every item; the sections run in order; values between sections stay float64.
+ *   out[b][i] = fp32(y_N[i]) for i < len, exactly 0 for len <= i < S  (out fp32 [B][S] at ld_out >= S)
+ *   out_len[b] = len (out_len may be NULL): the ringing past the end is cut.  Nothing at or past len is read.
+ * table float64 [40 N + 4 N^2], made by the host (data.equalize.equalizer_table):
+ *   [0, 8 N)             section k's b0, b1, b2, a1, a2 at 8 k, three unused
+ *   [8 N, 40 N)          A_k^(32 2^j), j = 0 .. 7, row-major 2 x 2 at 8 N + 4 (8 k + j); A_k = [[-a1, 1], [-a2, 0]] is the
+ *                        section's state transition s' = A_k s + B_k x
+ *   [40 N, 40 N + 4 N^2) the joint A^8192, row-major 2 N x 2 N over (s0, s1) of section 0, then of section 1, ...: block
+ *                        lower-triangular, read off the update above with x = 0
+ * The recurrence runs as a chunked scan on a grid fixed to sample 0: a chunk is 32 samples (one lane), a segment
+ * ispk_equalize_segment_samples() = 8192 samples (one workgroup), W = max(1, ceil(S / 8192)).  The first launch (grid (W - 1, B),
+ * skipped when W = 1) writes every segment's final joint state from zero entry into workspace (float64 [B][W][2 N]); the second
+ * (grid (W, B)) folds the earlier segments' states in segment order with the joint matrix, reruns its segment and stores fp32,
+ * 16 bytes at a time when out's base and row stride allow - the same values either way.  Every sum and scan runs in an order
+ * that is a function of the sample index alone: an item's bits depend on that item alone, not on B, the row strides or the
+ * alignment; repeated calls and graph replays repeat theirs.  A section with a1 = a2 = 0 (FIR) has nilpotent matrices whose
+ * powers are exactly zero: its output is fp32 of the serial float64 recurrence, bit for bit.
+ * out may be exactly audio (same base, same row stride); otherwise the two must not overlap.
+ * Refused before any launch: B > 65535, S outside [0, 2^24], sections outside 1 .. 8, a table of another size, a row stride
+ * below S, out overlapping audio without being audio (E_SHAPE); NULL audio, audio_len, table, out or workspace (E_NULL); a
+ * workspace below B W 2 N doubles or off an 8-byte boundary (E_ALIGN).  B = 0 is a no-op. */
+int32_t ispk_equalize_segment_samples(void);
+int32_t ispk_equalize_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const double* table,
+                          int64_t table_doubles, int32_t sections, float* out, int64_t ld_out, int64_t* out_len,
+                          double* workspace, int64_t workspace_doubles, int32_t B, int32_t S, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

@@ -1,7 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip), and
 the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip, csrc/bigvgan.hip) with their denoiser
 (csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip); the document join, speech marks, gain envelope and true-peak limiter
-(csrc/join.hip, marks.hip, prosody.hip, limiter.hip)."""
+(csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the equalizer (csrc/equalizer.hip)."""
 from typing import Optional
 
 import torch
@@ -19,7 +19,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear", "griffinlim_step", "griffinlim_fast_step",
            "griffinlim_error", "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio",
            "MARKS_MAX_TOKENS", "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope",
-           "LIMIT_TILE_SAMPLES", "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit"]
+           "LIMIT_TILE_SAMPLES", "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit", "EQ_MAX_SECTIONS", "EQ_SEGMENT_SAMPLES",
+           "EQ_CHUNK_SAMPLES", "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -804,3 +805,58 @@ def limit(audio: Tensor, audio_len: Optional[Tensor], taps: Tensor, ceiling: flo
                 _rt._ptr(out), 0 if out is None else ld(out), _rt._ptr(out_len), true_peak.data_ptr(), _rt._ptr(reduction), B, S,
                 _rt._stream())
     return out, out_len, true_peak, reduction
+
+
+# ------------------------------------------------------------------------------------------------------ equalizer
+EQ_MAX_SECTIONS = 8           # biquads in one cascade
+EQ_SEGMENT_SAMPLES = 8192     # ispk_equalize_segment_samples(): samples of one item per workgroup, 256 chunks
+EQ_CHUNK_SAMPLES = 32         # samples per lane; the table holds every section's A^(32 2^j), j = 0 .. 7
+
+
+def EQ_TABLE_DOUBLES(sections: int) -> int:
+    """Doubles of ispk_equalize_f32's table: per section 8 for the coefficients and eight 2 x 2 powers, then the joint
+    2 N x 2 N A^8192 (include/ispk.h has the layout)."""
+    return 40 * sections + 4 * sections * sections
+
+
+def equalize_workspace_doubles(B: int, S: int, sections: int) -> int:
+    """ispk_equalize_f32: the final joint state (2 N doubles) of every 8,192-sample segment of every item."""
+    return B * max(1, -(-S // EQ_SEGMENT_SAMPLES)) * 2 * sections
+
+
+def equalize(audio: Tensor, audio_len: Tensor, table: Tensor, sections: int, out: Optional[Tensor] = None,
+             out_len: Optional[Tensor] = None, work: Optional[Tensor] = None):
+    """ispk_equalize_f32, at most two launches, no host read: a cascade of `sections` (1 .. 8) float64 biquads over fp32 audio
+    [B, S] (unit stride on S, any row stride) with int64 lengths [B] -> (out fp32 [B, S], zeros from each length on, out_len
+    int64 [B] = the lengths).  `table` float64 [EQ_TABLE_DOUBLES(sections)] as include/ispk.h lays it out (data.Equalizer
+    builds it); `work` float64, at least equalize_workspace_doubles(B, S, sections), scratch.  `out` may be `audio` itself (same
+    base and row stride); any other overlap is refused."""
+    _rt._dev(audio, audio_len, table, out, out_len, work)
+    B, S = _mono_batch(audio, audio_len)
+    if int(sections) != sections or not 1 <= sections <= EQ_MAX_SECTIONS:
+        raise ValueError(f"sections is an integer in [1, {EQ_MAX_SECTIONS}], got {sections!r}")
+    sections = int(sections)
+    if table.dtype != torch.float64 or tuple(table.shape) != (EQ_TABLE_DOUBLES(sections),) or not table.is_contiguous():
+        raise ValueError(f"table: contiguous float64 [{EQ_TABLE_DOUBLES(sections)}] for {sections} sections, got {table.dtype} "
+                         f"{tuple(table.shape)}")
+    dev = audio.device
+    out = torch.empty((B, S), dtype=torch.float32, device=dev) if out is None else out
+    out_len = torch.empty((B,), dtype=torch.int64, device=dev) if out_len is None else out_len
+    if out.ndim != 2:
+        raise ValueError(f"out: fp32 [{B}, {S}], got {tuple(out.shape)}")
+    _out_like("out", out, torch.float32, (B, S))
+    _out_like("out_len", out_len, torch.int64, (B,))
+    if B > 1 and (audio.stride(0) < S or out.stride(0) < S):
+        raise ValueError(f"audio / out: rows overlap (row strides {audio.stride(0)}, {out.stride(0)} < {S})")
+    need = equalize_workspace_doubles(B, S, sections)
+    work = torch.empty((max(need, 1),), dtype=torch.float64, device=dev) if work is None else work
+    if work.dtype != torch.float64 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous float64 of at least {need} elements, got {work.dtype} {tuple(work.shape)}")
+    if B == 0:
+        return out, out_len
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), S)      # noqa: E731
+    # per sample and section two runs of three FMAs, in both launches; read twice, written once
+    _rt._launch("equalize_kernels", 24.0 * sections * B * S, 12.0 * B * S, _rt.lib().ispk_equalize_f32, audio.data_ptr(), ld(audio),
+                audio_len.data_ptr(), table.data_ptr(), table.numel(), sections, out.data_ptr(), ld(out), out_len.data_ptr(),
+                work.data_ptr(), work.numel(), B, S, _rt._stream())
+    return out, out_len

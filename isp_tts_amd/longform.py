@@ -26,6 +26,7 @@ from torch import Tensor
 
 from . import graph, runtime
 from .data.condition import AudioConditioner, Limiter, to_pcm16
+from .data.equalize import Equalizer
 
 CONTROL_NAMES = ("duration_factor", "pitch_factor", "pitch_delta", "energy_factor", "energy_delta")
 
@@ -313,14 +314,18 @@ class Synthesizer:
     With `limiter=Limiter(...)` (data.condition) one ispk_limit_f32 launch on the final documents, behind `doc_conditioner` and in
     front of to_pcm16, pulls down what crossfades, gains and the document loudness pushed over the ceiling instead of leaving it
     to PCM16's clamp: r["audio"] is the limited audio, r["true_peak"] and r["reduction"] fp32 [D] say per document what came in
-    and how far the gain went down; lengths and marks do not change.  A call copies
+    and how far the gain went down; lengths and marks do not change.
+    With `equalizer=Equalizer(...)` (data.equalize) one ispk_equalize_f32 call (two launches) on the item audio, behind the
+    denoiser and the gain envelope and in front of `item_conditioner`'s measure pass - loudness is measured on what is heard -
+    into a buffer of its own; lengths, marks and bounds do not change.  A call copies
     its arguments into the static inputs and replays; `flow_noise=None` draws new noise.  Text splitting and bucketing stay with the caller:
     one Synthesizer serves one bucket shape (B sentences of L tokens into D documents of S_out samples)."""
 
     def __init__(self, model, vocoder, *, batch: int, tokens: int, frames: int, docs: int, doc_samples: int, steps: int = 4,
                  denoiser=None, item_conditioner: Optional[AudioConditioner] = None,
                  doc_conditioner: Optional[AudioConditioner] = None, fade: int = 0, dither: bool = False, seed: int = 0,
-                 marks: bool = False, words: int = 0, prosody: bool = False, ramp: int = 128, limiter: Optional[Limiter] = None):
+                 marks: bool = False, words: int = 0, prosody: bool = False, ramp: int = 128, limiter: Optional[Limiter] = None,
+                 equalizer: Optional[Equalizer] = None):
         B, L, M, D, S_out = int(batch), int(tokens), int(frames), int(docs), int(doc_samples)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -369,6 +374,12 @@ class Synthesizer:
         if limiter is not None:      # the last fp32 stage, into a buffer of its own
             self._limited = limiter.empty_outputs(D, S_out, dev)
             limiter.device_tables(dev)
+        if equalizer is not None and not isinstance(equalizer, Equalizer):
+            raise ValueError(f"Synthesizer: equalizer is a data.Equalizer or None, got {type(equalizer).__name__}")
+        self.equalizer, self._equalized = equalizer, None
+        if equalizer is not None:    # on the item audio, into a buffer of its own
+            self._equalized = equalizer.empty_outputs(B, S, dev)
+            equalizer.device_tables(dev)
         self._pcm = torch.empty((D, S_out), dtype=torch.int16, device=dev)
         self._marks = None
         if self.marks or self.prosody:
@@ -402,6 +413,9 @@ class Synthesizer:
                 runtime.speech_marks(ao.duration, s["text_len"], audio_len, self._item_marks, None, self._hop, audio.shape[1],
                                      not self.model.temporal_adaptor.soft_duration)
                 audio = runtime.gain_envelope(audio, audio_len, self._item_marks, s["gain"], self.ramp, self._shaped)
+            if self.equalizer is not None:
+                # the lengths do not change, so marks and bounds stay where they are; audio_len itself goes on
+                audio = self.equalizer(audio, audio_len, out=self._equalized)["audio"]
             bounds = gain = None
             if self.item_conditioner is not None:
                 c, o = self.item_conditioner, self._item
