@@ -208,3 +208,4 @@ from .bindings.util import *       # noqa: E402,F401,F403
 from .bindings.train import *      # noqa: E402,F401,F403
 from .bindings.evaluate import *   # noqa: E402,F401,F403
 from .bindings.audio import *      # noqa: E402,F401,F403
+from .bindings.vocoders import *   # noqa: E402,F401,F403

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .config import AcousticDims
+from .hifigan import CONFIGS as _HIFIGAN_CONFIGS
 
 SEED = 23  # recipe seed (recipes/acoustic/core.yaml:5)
 
@@ -329,14 +330,60 @@ def make_vocoder_mel(B: int, n_mels: int, T: int, seed: int = SEED) -> torch.Ten
     return torch.from_numpy((x - 4.5 + np.linspace(1.5, -1.5, n_mels)[None, :, None]).astype(np.float32))
 
 
-# ---------------------------------------------------------------------------------------------------- HiFi-GAN generators
-# name -> generator configuration (hifigan.HifiGan's constructor arguments).  "odd": stage lengths that are no powers of two,
-# unequal taps per phase (k 7, stride 3) and the 25-row halo of k 11, dilation 5.
+# ------------------------------------------------------------------------------------- HiFi-GAN and BigVGAN generators
+def _make_generator(tag: str, dims: dict, seed: int, weight_norm: Optional[str], s_pre: float, s_up: float, s_unit: dict,
+                    s_post: float, up_key: str = "ups.{i}", act=None, post_bias: bool = True) -> dict[str, torch.Tensor]:
+    """The walk over conv_pre, stages, blocks, units and conv_post that both generator families share, on the streams
+    `<tag>/<name>.w|.f|.b`.  Convolution weights are N(0, s^2 / fan_in): s_pre, s_up (fan_in C_in k / stride), s_unit[type] per
+    convolution of a unit, s_post; biases N(0, 0.05^2).  `act(sd, name, C)`, if given, adds the activation that precedes each
+    unit convolution (after the unit's weights) and activation_post.  weight_norm None: plain `weight`; "g_v": `weight_g` +
+    `weight_v`; "parametrized": `parametrizations.weight.original0` + `original1`.  v is the plain weight times a per-slice
+    factor in [0.5, 2] and g the plain weight's norm, so g != ||v|| and g v / ||v|| is the plain weight."""
+    if weight_norm not in (None, "g_v", "parametrized"):
+        raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
+    C0, rates, up_k = dims["upsample_initial_channel"], dims["upsample_rates"], dims["upsample_kernel_sizes"]
+    sd: dict[str, torch.Tensor] = {}
+
+    def put(name: str, shape, fan: float, s: float, bias: bool = True):
+        w = _normal(f"{tag}/{name}.w", shape, s / math.sqrt(fan), seed=seed)
+        if weight_norm is None:
+            sd[name + ".weight"] = w
+        else:
+            gk, vk = (".weight_g", ".weight_v") if weight_norm == "g_v" else (".parametrizations.weight.original0",
+                                                                             ".parametrizations.weight.original1")
+            ones = [1] * (len(shape) - 1)
+            f = torch.from_numpy(_rng(f"{tag}/{name}.f", seed).uniform(0.5, 2.0, size=(shape[0], *ones)).astype(np.float32))
+            sd[name + gk] = w.double().flatten(1).norm(dim=1).reshape(shape[0], *ones).float()
+            sd[name + vk] = w * f
+        if bias:
+            sd[name + ".bias"] = _normal(f"{tag}/{name}.b", (shape[0] if not name.startswith("ups.") else shape[1],), 0.05, seed=seed)
+
+    put("conv_pre", (C0, dims["n_mels"], 7), dims["n_mels"] * 7, s_pre)
+    J = len(dims["resblock_kernel_sizes"])
+    convs = ("convs1", "convs2") if str(dims["resblock"]) == "1" else ("convs",)
+    for i, (u, k) in enumerate(zip(rates, up_k)):
+        C = C0 >> i
+        put(up_key.format(i=i), (C, C // 2, k), C * k / u, s_up)
+        for j, (r, D) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
+            n = i * J + j
+            for m in range(len(D)):
+                for name, s in zip(convs, s_unit[str(dims["resblock"])]):
+                    put(f"resblocks.{n}.{name}.{m}", (C // 2, C // 2, r), C // 2 * r, s)
+                if act:
+                    for l in range(len(convs) * m, len(convs) * (m + 1)):
+                        act(sd, f"resblocks.{n}.activations.{l}", C // 2)
+    C = C0 >> len(rates)
+    if act:
+        act(sd, "activation_post", C)
+    put("conv_post", (1, C, 7), C * 7, s_post, bias=post_bias)
+    return sd
+
+
+# name -> generator configuration (hifigan.HifiGan's constructor arguments); "v1" and "v3" are hifigan.CONFIGS' own.  "odd":
+# stage lengths that are no powers of two, unequal taps per phase (k 7, stride 3) and the 25-row halo of k 11, dilation 5.
 HIFIGAN_DIMS = {
-    "v1": dict(n_mels=80, upsample_initial_channel=512, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4),
-               resblock="1", resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5),) * 3),
-    "v3": dict(n_mels=80, upsample_initial_channel=256, upsample_rates=(8, 8, 4), upsample_kernel_sizes=(16, 16, 8),
-               resblock="2", resblock_kernel_sizes=(3, 5, 7), resblock_dilation_sizes=((1, 2), (2, 6), (3, 12))),
+    "v1": _HIFIGAN_CONFIGS["v1"],
+    "v3": _HIFIGAN_CONFIGS["v3"],
     "odd": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
                 resblock="1", resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3, 5),) * 2),
 }
@@ -346,45 +393,10 @@ def make_hifigan_state_dict(dims=HIFIGAN_DIMS["v1"], seed: int = SEED, weight_no
     """Synthetic HiFi-GAN generator weights in the official state-dict layout, from keyed streams.  Convolution weights are
     N(0, s^2 / (C_in k)) with s = 1.4 (first convolution of a type "1" unit), 0.5 (second), 0.7 (type "2"), up-convolutions
     N(0, 1.4^2 / (C_in k / stride)), conv_post s = 0.1, biases N(0, 0.05^2): on make_vocoder_mel the output peaks at
-    0.16 - 0.9, inside tanh's curved part.  weight_norm None: plain `weight`; "g_v": `weight_g` + `weight_v`; "parametrized":
-    `parametrizations.weight.original0` + `original1`.  v is the plain weight times a per-slice factor in [0.5, 2] and g the
-    plain weight's norm, so g != ||v|| and g v / ||v|| is the plain weight."""
-    if weight_norm not in (None, "g_v", "parametrized"):
-        raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
-    C0, rates, up_k = dims["upsample_initial_channel"], dims["upsample_rates"], dims["upsample_kernel_sizes"]
-    sd: dict[str, torch.Tensor] = {}
-
-    def put(name: str, shape, fan: float, s: float):
-        w = _normal(f"hfg/{name}.w", shape, s / math.sqrt(fan), seed=seed)
-        if weight_norm is None:
-            sd[name + ".weight"] = w
-        else:
-            gk, vk = (".weight_g", ".weight_v") if weight_norm == "g_v" else (".parametrizations.weight.original0",
-                                                                             ".parametrizations.weight.original1")
-            ones = [1] * (len(shape) - 1)
-            f = torch.from_numpy(_rng(f"hfg/{name}.f", seed).uniform(0.5, 2.0, size=(shape[0], *ones)).astype(np.float32))
-            sd[name + gk] = w.double().flatten(1).norm(dim=1).reshape(shape[0], *ones).float()
-            sd[name + vk] = w * f
-        sd[name + ".bias"] = _normal(f"hfg/{name}.b", (shape[0] if not name.startswith("ups.") else shape[1],), 0.05, seed=seed)
-
-    put("conv_pre", (C0, dims["n_mels"], 7), dims["n_mels"] * 7, 1.0)
-    J = len(dims["resblock_kernel_sizes"])
-    for i, (u, k) in enumerate(zip(rates, up_k)):
-        C = C0 >> i
-        put(f"ups.{i}", (C, C // 2, k), C * k / u, 1.4)
-        for j, (r, D) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
-            n = i * J + j
-            for m in range(len(D)):
-                if str(dims["resblock"]) == "1":
-                    put(f"resblocks.{n}.convs1.{m}", (C // 2, C // 2, r), C // 2 * r, 1.4)
-                    put(f"resblocks.{n}.convs2.{m}", (C // 2, C // 2, r), C // 2 * r, 0.5)
-                else:
-                    put(f"resblocks.{n}.convs.{m}", (C // 2, C // 2, r), C // 2 * r, 0.7)
-    put("conv_post", (1, C0 >> len(rates), 7), (C0 >> len(rates)) * 7, 0.1)
-    return sd
+    0.16 - 0.9, inside tanh's curved part.  weight_norm: see _make_generator."""
+    return _make_generator("hfg", dims, seed, weight_norm, 1.0, 1.4, {"1": (1.4, 0.5), "2": (0.7,)}, 0.1)
 
 
-# ----------------------------------------------------------------------------------------------------- BigVGAN generators
 # name -> generator configuration (bigvgan.BigVGan's constructor arguments).  "base": the published 22.05 kHz base model.
 # "odd" / "odd2": HIFIGAN_DIMS["odd"]'s geometry with AMPBlock "1" / "2", plain snake without logscale, no bias in conv_post
 # and a clamp in place of the final tanh.
@@ -417,55 +429,20 @@ def make_bigvgan_state_dict(dims=BIGVGAN_DIMS["base"], seed: int = SEED, weight_
     N(0, 0.05^2): the activations' inputs have an rms around 1.  al is log-uniform in [1, 6] and B in [1, 4] (stored as their
     logarithms with snake_logscale), so al |u| lies around 1 to 10.  conv_post is scaled for output peaks of 0.2 - 0.9 under a
     final tanh, and so that a few per cent of the samples clamp on either side without one.  The filters are bigvgan_filter().
-    weight_norm as in make_hifigan_state_dict."""
-    if weight_norm not in (None, "g_v", "parametrized"):
-        raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
-    C0, rates, up_k = dims["upsample_initial_channel"], dims["upsample_rates"], dims["upsample_kernel_sizes"]
+    weight_norm: see _make_generator."""
     beta, logscale = dims.get("activation", "snakebeta") == "snakebeta", dims.get("snake_logscale", True)
-    sd: dict[str, torch.Tensor] = {}
     filt = bigvgan_filter().float().reshape(1, 1, 12)
 
-    def put(name: str, shape, fan: float, s: float, bias: bool = True):
-        w = _normal(f"bvg/{name}.w", shape, s / math.sqrt(fan), seed=seed)
-        if weight_norm is None:
-            sd[name + ".weight"] = w
-        else:
-            gk, vk = (".weight_g", ".weight_v") if weight_norm == "g_v" else (".parametrizations.weight.original0",
-                                                                             ".parametrizations.weight.original1")
-            ones = [1] * (len(shape) - 1)
-            f = torch.from_numpy(_rng(f"bvg/{name}.f", seed).uniform(0.5, 2.0, size=(shape[0], *ones)).astype(np.float32))
-            sd[name + gk] = w.double().flatten(1).norm(dim=1).reshape(shape[0], *ones).float()
-            sd[name + vk] = w * f
-        if bias:
-            sd[name + ".bias"] = _normal(f"bvg/{name}.b", (shape[0] if not name.startswith("ups.") else shape[1],), 0.05, seed=seed)
-
-    def act(name: str, C: int):
+    def act(sd: dict, name: str, C: int):
         for key, lo, hi in (("alpha", 1.0, 6.0),) + ((("beta", 1.0, 4.0),) if beta else ()):
             v = np.exp(_rng(f"bvg/{name}.{key}", seed).uniform(math.log(lo), math.log(hi), size=(C,)))
             sd[f"{name}.act.{key}"] = torch.from_numpy((np.log(v) if logscale else v).astype(np.float32))
         sd[name + ".upsample.filter"] = filt.clone()
         sd[name + ".downsample.lowpass.filter"] = filt.clone()
 
-    put("conv_pre", (C0, dims["n_mels"], 7), dims["n_mels"] * 7, 0.25)
-    J = len(dims["resblock_kernel_sizes"])
-    for i, (u, k) in enumerate(zip(rates, up_k)):
-        C = C0 >> i
-        put(f"ups.{i}.0", (C, C // 2, k), C * k / u, 1.0)
-        for j, (r, D) in enumerate(zip(dims["resblock_kernel_sizes"], dims["resblock_dilation_sizes"])):
-            n = i * J + j
-            for m in range(len(D)):
-                if str(dims["resblock"]) == "1":
-                    put(f"resblocks.{n}.convs1.{m}", (C // 2, C // 2, r), C // 2 * r, 1.0)
-                    put(f"resblocks.{n}.convs2.{m}", (C // 2, C // 2, r), C // 2 * r, 0.5)
-                    act(f"resblocks.{n}.activations.{2 * m}", C // 2)
-                    act(f"resblocks.{n}.activations.{2 * m + 1}", C // 2)
-                else:
-                    put(f"resblocks.{n}.convs.{m}", (C // 2, C // 2, r), C // 2 * r, 0.7)
-                    act(f"resblocks.{n}.activations.{m}", C // 2)
-    act("activation_post", C0 >> len(rates))
-    tanh = dims.get("use_tanh_at_final", True)
-    put("conv_post", (1, C0 >> len(rates), 7), (C0 >> len(rates)) * 7, 0.1 if tanh else 0.6, bias=dims.get("use_bias_at_final", True))
-    return sd
+    return _make_generator("bvg", dims, seed, weight_norm, 0.25, 1.0, {"1": (1.0, 0.5), "2": (0.7,)},
+                           0.1 if dims.get("use_tanh_at_final", True) else 0.6, up_key="ups.{i}.0", act=act,
+                           post_bias=dims.get("use_bias_at_final", True))
 
 
 # ---------------------------------------------------------------------------------------------------- dataset statistics

@@ -25,12 +25,11 @@ from torch import Tensor, nn
 
 from . import runtime
 from .data.features import twiddles
-from .staging import StagedWeights
+from .generator import MAX_MELS, MelVocoder
 
 N_FFT = 1024
 HOP = runtime.VOCODER_HOP
 EPS = 1e-6
-MAX_MELS = 128         # ispk_vocoder_unfold
 MAX_DIM = 1024         # ispk_dwconv7_ln_f32 and ispk_layernorm_f32: dim % 64 == 0, dim <= 1024
 INTER_MULTIPLE = 32    # pwconv1 rows: the GEMMs' N tiles
 _HEAD_N = N_FFT + 8    # head.out rows padded with zero rows to 1032 (16-byte aligned fp32 rows)
@@ -96,9 +95,10 @@ def _official_keys(num_layers: int, gamma: bool) -> list[str]:
                    "head.istft.window"]
 
 
-class Vocoder(nn.Module):
+class Vocoder(MelVocoder):
     """The Vocos mel vocoder on libispk kernels.  Parameters carry the official state-dict names (backbone.*, head.*), so an
-    official-layout dict loads with load_state_dict(strict=True).
+    official-layout dict loads with load_state_dict(strict=True).  In bf16 compute the residual stream, the head output and
+    the ISTFT stay fp32.
 
     vocoder = Vocoder.from_pretrained(path).to("cuda").eval()
     audio, audio_len = vocoder(mel, mel_len)        # mel fp32 / fp16 [B, n_mels, T] (any strides), mel_len int64 [B] or None
@@ -107,15 +107,11 @@ class Vocoder(nn.Module):
 
     def __init__(self, n_mels: int = 100, dim: int = 512, inter: int = 1536, num_layers: int = 8, gamma: bool = True,
                  hop_length: int = HOP, padding: str = "same"):
-        super().__init__()
         _check_dims(n_mels, dim, inter, N_FFT, N_FFT, hop_length, padding)
-        self.n_mels, self.dim, self.inter, self.num_layers, self.has_gamma = n_mels, dim, inter, num_layers, gamma
-        self.hop_length, self.padding = hop_length, padding
+        super().__init__(n_mels, hop_length)
+        self.dim, self.inter, self.num_layers, self.has_gamma, self.padding = dim, inter, num_layers, gamma, padding
         self.backbone = _Backbone(n_mels, dim, inter, num_layers, gamma)
         self.head = _Head(dim, N_FFT)
-        self.k_pad = (7 * n_mels + 7) // 8 * 8          # embedding GEMM's K: 7 n_mels padded to a multiple of 8
-        self.compute_dtype = torch.float32
-        self._cache = StagedWeights()
 
     # ---- loading
     @classmethod
@@ -171,14 +167,6 @@ class Vocoder(nn.Module):
             raise ValueError(f"{os.fspath(path)}: not a state dict, a {{'state_dict': ...}} dict or a TorchScript archive")
         return cls.from_state_dict(sd, hop_length, padding)
 
-    def set_compute_dtype(self, dtype: torch.dtype) -> "Vocoder":
-        """fp32 (exact-fp32 MFMA GEMMs) or bf16 (bf16 GEMM operands, fp32 accumulation, fp32 residual stream, fp32 head
-        output and ISTFT)."""
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError(f"compute dtype {dtype}: fp32 and bf16 are built")
-        self.compute_dtype = dtype
-        return self
-
     # ---- kernel-ready weight images
     def tables(self) -> Tensor:
         """fp32 [5120]: float64-made twiddles W_2048^m (re, im), then head.istft.window (ispk_istft_head_f32)."""
@@ -212,35 +200,10 @@ class Vocoder(nn.Module):
             return {"emb_w": emb_w.to(cd).contiguous(), "emb_b": bb.embed.bias.detach().float().contiguous(),
                     "blocks": blocks, "head_w": head_w.to(cd).contiguous(), "head_b": head_b, "tables": self.tables()}
 
-    def staged(self, dtype: Optional[torch.dtype] = None) -> dict:
-        """The kernel-ready images for `dtype` (default: the compute dtype), built once per dtype and rebuilt when a
-        parameter changes; build them before a graph capture (a warm-up call does)."""
-        dtype = dtype or self.compute_dtype
-        params = [*self.parameters(), self.head.istft.window]
-        return self._cache.get(dtype, params, lambda: self._build(dtype))
-
     # ---- forward
-    def empty_outputs(self, B: int, T: int, device) -> tuple[Tensor, Tensor]:
-        return (torch.empty((B, T * HOP), dtype=torch.float32, device=device),
-                torch.empty((B,), dtype=torch.int64, device=device))
-
-    def forward(self, mel: Tensor, mel_len: Optional[Tensor] = None,
-                out: Optional[tuple[Tensor, Tensor]] = None) -> tuple[Tensor, Tensor]:
-        """mel fp32 / fp16 [B, n_mels, T] on the GPU -> (audio fp32 [B, S >= 256 T], audio_len int64 [B])."""
-        if not mel.is_cuda or (mel_len is not None and not mel_len.is_cuda):
-            raise runtime.IspkError("Vocoder needs GPU tensors; there is no CPU fallback")
-        if mel.ndim != 3 or mel.dtype not in (torch.float32, torch.float16) or mel.shape[1] != self.n_mels:
-            raise ValueError(f"mel: fp32 / fp16 [B, {self.n_mels}, T], got {mel.dtype} {tuple(mel.shape)}")
-        B, _, T = mel.shape
-        audio, audio_len = out if out is not None else self.empty_outputs(B, T, mel.device)
-        if B == 0:
-            return audio, audio_len
-        if T == 0:
-            runtime.zero_(audio_len)
-            if audio.numel():
-                runtime.zero_(audio)
-            return audio, audio_len
-        cd, dev, R = self.compute_dtype, mel.device, B * T
+    def _vocode(self, mel: Tensor, mel_len: Optional[Tensor], audio: Tensor, audio_len: Tensor) -> None:
+        (B, _, T), cd, dev = mel.shape, self.compute_dtype, mel.device
+        R = B * T
         w = self.staged(cd)
         bb = self.backbone
         rows = torch.empty((R, self.k_pad), dtype=cd, device=dev)
@@ -258,9 +221,3 @@ class Vocoder(nn.Module):
         y = runtime.layernorm(x, bb.final_layer_norm.weight, bb.final_layer_norm.bias, row_mask=mask, eps=EPS, out_dtype=cd)
         h = runtime.gemm(y, w["head_w"], bias=w["head_b"], out_dtype=torch.float32)
         runtime.istft_head(h, T, mel_len, w["tables"], audio, audio_len)
-        return audio, audio_len
-
-    @torch.no_grad()
-    def infer(self, mel: Tensor) -> Tensor:
-        """The notebook's `vocoder.infer(mel)`: every utterance has all T frames; audio fp32 [B, 256 T]."""
-        return self.forward(mel)[0]
