@@ -1101,6 +1101,32 @@ int32_t ispk_hifigan_post_clamp_f32(const float* x, int64_t ldx, const float* w,
                                     int32_t S, int32_t C, float slope, ispk_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * iSTFTNet generator (csrc/istftnet.hip; isp_tts_amd/istftnet.py): the output layer.  conv_pre, the stages and the blocks are
+ * the HiFi-GAN entries above.  Rows, lengths and limits are those of ispk_hifigan_post_f32: x is fp32 rows [B * T][C] with
+ * unit column stride, 16-byte aligned, ldx a multiple of 4; the valid length of utterance b is n_b = len[b] * len_mul rows
+ * (len NULL: T; a value outside [0, T] counts as 0, and so does n_b = 1, which has no reflection); rows at or past it, and
+ * halo rows, read as zeros through a select (NaN in the padding does not propagate); C is a multiple of 32 up to 512.
+ *
+ * ispk_istftnet_tile_frames   frames per workgroup (128): the tests' tile edge.  A workgroup owns 125 hop blocks of one
+ *                             utterance and recomputes the 3 frames it shares with its neighbour.
+ * ispk_istftnet_head_f32      with N = n_fft, H = N / 2, F = n_b + 1 frames, p[0] = x[1], p[i] = x[i - 1] (ReflectionPad1d((1, 0))):
+ *                               y_f[o]  = bias[o] + sum_j sum_c w[j][o][c] leaky_relu(p[f + j - 3][c], slope)   (p = 0 outside [0, F))
+ *                               Z_f[k]  = exp(y_f[k]) exp(i phase_scale sin(y_f[H + 1 + k])),  k = 0 .. H
+ *                               audio[b] = torch.istft(Z, N, hop, N, hann_window(N, periodic), center = True): hop n_b samples
+ *                             (the imaginary parts of Z[0] and Z[H] do not enter; the envelope sum_f w^2 runs over the F frames
+ *                             of the utterance), zeros from hop n_b to S; audio_len[b] = hop n_b (may be NULL).  S >= hop T,
+ *                             ld_audio >= S, T >= 2 (else E_SHAPE).  n_fft a multiple of 4 from 8 to 32 with hop = n_fft / 4
+ *                             (else E_UNSUPPORTED).  w fp32 [7][N + 2][C], bias fp32 [N + 2].  table: 4 N floats made in
+ *                             float64 - cos(2 pi m / N) [N], sin(2 pi m / N) [N], hann[t] / N [N], hann[t]^2 [N].  All
+ *                             arithmetic fp32 with accurate expf / sinf / cosf; no atomics: a sample's bits depend neither on
+ *                             B, nor on the neighbouring utterances, nor on the tile it fell into. */
+int32_t ispk_istftnet_tile_frames(void);
+int32_t ispk_istftnet_head_f32(const float* x, int64_t ldx, const float* w, const float* bias, const float* table,
+                               int32_t table_floats, const int64_t* len, int32_t len_mul, float* audio, int64_t ld_audio,
+                               int64_t* audio_len, int32_t B, int32_t T, int32_t S, int32_t C, int32_t n_fft, int32_t hop,
+                               float slope, float phase_scale, ispk_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * BigVGAN generator (csrc/bigvgan.hip; isp_tts_amd/bigvgan.py): the anti-aliased periodic activation.  The convolutions
  * are the HiFi-GAN entries above with slope 1.  Rows, lengths and limits are exactly those of the HiFi-GAN entries: x and out
  * are fp32 rows [B * T][C] with unit column stride, 16-byte aligned, ldx and ldo multiples of 4; the valid length of

@@ -1,5 +1,5 @@
 """Mel spectrograms to waveforms: the Vocos, HiFi-GAN and BigVGAN vocoders (csrc/vocoder.hip, csrc/hifigan.hip,
-csrc/bigvgan.hip) with their denoiser (csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip)."""
+csrc/bigvgan.hip, csrc/istftnet.hip) with their denoiser (csrc/denoise.hip) and the Griffin-Lim mel inversion (csrc/griffinlim.hip)."""
 from typing import Optional
 
 import torch
@@ -10,7 +10,8 @@ from .audio import _out_like
 
 __all__ = ["VOCODER_HOP", "VOCODER_TABLE_FLOATS", "_lengths_ptr", "vocoder_unfold", "dwconv7_ln", "istft_head",
            "HIFIGAN_TILE_ROWS", "HIFIGAN_MAX_CHANNELS", "HIFIGAN_MAX_KERNEL", "HIFIGAN_MAX_DILATION", "_hifigan_rows",
-           "hifigan_conv", "_hifigan_bn", "hifigan_upsample", "hifigan_post", "SNAKE_AA_TILE_ROWS", "snake_aa",
+           "hifigan_conv", "_hifigan_bn", "hifigan_upsample", "hifigan_post", "ISTFTNET_TILE_FRAMES", "ISTFTNET_N_FFTS",
+           "istftnet_table", "istftnet_head", "SNAKE_AA_TILE_ROWS", "snake_aa",
            "DENOISE_TILE_SAMPLES", "DENOISE_N_FFT", "DENOISE_HOP", "DENOISE_TABLE_FLOATS", "denoise", "GRIFFINLIM_TILE_SAMPLES",
            "GRIFFINLIM_N_FFT", "GRIFFINLIM_HOP", "GRIFFINLIM_PAD", "GRIFFINLIM_STEP", "GRIFFINLIM_INIT", "mel_to_linear",
            "griffinlim_step", "griffinlim_fast_step", "griffinlim_error"]
@@ -187,6 +188,51 @@ def hifigan_post(x: Tensor, T: int, weight: Tensor, bias: Tensor, audio: Tensor,
                 float(B * T * C * 4 + B * S * 4), _rt.lib().ispk_hifigan_post_clamp_f32 if final_clamp else _rt.lib().ispk_hifigan_post_f32,
                 _rt._ptr(x) if x.numel() else None, x.stride(0), weight.data_ptr(), bias.data_ptr(), ln, len_mul, audio.data_ptr(),
                 max(audio.stride(0), S), _rt._ptr(audio_len), B, T, S, C, slope, _rt._stream())
+    return audio
+
+
+# --------------------------------------------------------------------------------------------------- iSTFTNet vocoder
+ISTFTNET_TILE_FRAMES = 128    # ispk_istftnet_tile_frames(): frames of one utterance per workgroup of the output layer
+ISTFTNET_N_FFTS = (8, 12, 16, 20, 24, 28, 32)      # the built geometries; hop = n_fft / 4, window length n_fft
+
+
+def istftnet_table(n_fft: int) -> Tensor:
+    """The output layer's table, made in float64: cos(2 pi m / N) [N], sin(2 pi m / N) [N], hann[t] / N [N], hann[t]^2 [N]
+    (hann periodic) as fp32 [4 N] on the CPU."""
+    m = torch.arange(n_fft, dtype=torch.float64)
+    a = 2.0 * torch.pi * m / n_fft
+    win = torch.hann_window(n_fft, periodic=True, dtype=torch.float64)
+    return torch.cat([torch.cos(a), torch.sin(a), win / n_fft, win * win]).to(torch.float32)
+
+
+def istftnet_head(x: Tensor, T: int, weight: Tensor, bias: Tensor, table: Tensor, n_fft: int, hop: int, audio: Tensor,
+                  audio_len: Optional[Tensor] = None, lengths: Optional[Tensor] = None, len_mul: int = 1, slope: float = 0.01,
+                  phase_scale: float = 1.0) -> Tensor:
+    """ispk_istftnet_head_f32, one launch: x fp32 [B*T, C] rows -> audio fp32 [B, S >= hop T] = istft(exp(y[:H + 1]) exp(i
+    phase_scale sin(y[H + 1:]))) with y = conv7(ReflectionPad1d((1, 0))(leaky_relu(x, slope))), H = n_fft / 2, periodic Hann,
+    center = True: hop n_b samples for the n_b = lengths[b] * len_mul valid rows of utterance b (n_b = 1 counts as 0), zeros from
+    there on; audio_len int64 [B] = hop n_b.  weight fp32 [7, n_fft + 2, C] contiguous, bias fp32 [n_fft + 2], table
+    istftnet_table(n_fft) on the device."""
+    _rt._dev(x, weight, bias, table, audio, audio_len, lengths)
+    _hifigan_rows(x, "x")
+    if n_fft not in ISTFTNET_N_FFTS or hop * 4 != n_fft:
+        raise NotImplementedError(f"n_fft {n_fft} hop {hop}: n_fft in {ISTFTNET_N_FFTS} with hop = n_fft / 4 is built")
+    assert audio.dtype == torch.float32 and audio.ndim == 2 and (audio.stride(1) == 1 or audio.shape[1] <= 1)
+    B, S = audio.shape
+    C = x.shape[1]
+    assert x.shape[0] == B * T and S >= hop * T
+    assert weight.shape == (7, n_fft + 2, C) and weight.is_contiguous() and weight.dtype == torch.float32
+    assert bias.dtype == torch.float32 and bias.shape == (n_fft + 2,) and bias.is_contiguous()
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() >= 4 * n_fft
+    assert audio_len is None or (audio_len.dtype == torch.int64 and audio_len.shape == (B,) and audio_len.is_contiguous())
+    ln = _lengths_ptr(lengths, B)
+    if B == 0:
+        return audio
+    R = B * T
+    _rt._launch(f"istftnet_head_kernel<{n_fft}>", R * (14.0 * C * (n_fft + 2) + 2.0 * n_fft * n_fft),
+                float(R * C * 4 + B * S * 4), _rt.lib().ispk_istftnet_head_f32, x.data_ptr(), x.stride(0), weight.data_ptr(),
+                bias.data_ptr(), table.data_ptr(), table.numel(), ln, len_mul, audio.data_ptr(), max(audio.stride(0), S),
+                _rt._ptr(audio_len), B, T, S, C, n_fft, hop, slope, phase_scale, _rt._stream())
     return audio
 
 

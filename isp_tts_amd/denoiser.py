@@ -82,7 +82,7 @@ class Denoiser(torch.nn.Module):
     @classmethod
     def from_vocoder(cls, vocoder, mode: str = "zeros", frames: Optional[int] = None, seed: int = 0,
                      strength: float = 0.01) -> "Denoiser":
-        """Runs `vocoder` (Vocoder, HifiGan or BigVGan, on the GPU) once on a [1, n_mels, frames] mel of zeros, or of
+        """Runs `vocoder` (Vocoder, HifiGan, BigVGan or IstftNet, on the GPU) once on a [1, n_mels, frames] mel of zeros, or of
         standard-normal values from `seed` (mode "normal"), and keeps |X_0[k]| of frame 0 of that waveform, computed on the
         host in float64 and rounded once.  Construction, outside any forward, as the weight-norm folding is."""
         if mode not in ("zeros", "normal"):

@@ -1,7 +1,8 @@
 """What the mel vocoders share.  `MelVocoder`: the call surface of anything that maps mel spectrograms [B, n_mels, T] (+
-mel_len) to (audio, audio_len) - `vocoder.Vocoder`, `hifigan.HifiGan`, `bigvgan.BigVGan`.  `ConvStackGenerator`: the HiFi-GAN
-skeleton under the two GAN generators - geometry, loader, weight images and the stage / block / unit loop on the kernels of
-csrc/hifigan.hip.  A generator adds its block containers and says, per convolution, what the convolution reads.
+mel_len) to (audio, audio_len) - `vocoder.Vocoder`, `hifigan.HifiGan`, `bigvgan.BigVGan`, `istftnet.IstftNet`.
+`ConvStackGenerator`: the HiFi-GAN skeleton under the three GAN generators - geometry, loader, weight images and the stage /
+block / unit loop on the kernels of csrc/hifigan.hip.  A generator adds its block containers and its output layer, and says,
+per convolution, what the convolution reads.
 """
 from __future__ import annotations
 
@@ -150,7 +151,8 @@ class ConvStackGenerator(MelVocoder):
     (SLOPE), builds its modules with `_stack` (conv_post after it), and has two steps of its own: `_conv_input`, what a
     convolution reads, and `_post`, the output layer.  CONV_READS_STAGE says which of the two `_conv_input` is: true when the
     convolution reads the stage tensor itself, so its halo forbids writing the unit's result over the unit's input; false when
-    it reads a copy in a scratch tensor of the stage's size."""
+    it reads a copy in a scratch tensor of the stage's size.  `head_hop`: the samples the output layer makes of one row of the
+    last stage (1, or the hop of an inverse STFT), so hop_length = prod(upsample_rates) * head_hop."""
 
     UP_KEY = "ups.{i}"                           # the transposed convolution of stage i
     KEY_PREFIXES = ("conv_pre.", "ups.", "resblocks.", "conv_post.")
@@ -160,13 +162,13 @@ class ConvStackGenerator(MelVocoder):
 
     def __init__(self, n_mels: int, upsample_initial_channel: int, upsample_rates: Sequence[int],
                  upsample_kernel_sizes: Sequence[int], resblock: str, resblock_kernel_sizes: Sequence[int],
-                 resblock_dilation_sizes: Sequence[Sequence[int]]):
+                 resblock_dilation_sizes: Sequence[Sequence[int]], head_hop: int = 1):
         rates, up_k = tuple(int(u) for u in upsample_rates), tuple(int(k) for k in upsample_kernel_sizes)
         res_k = tuple(int(k) for k in resblock_kernel_sizes)
         res_d = tuple(tuple(int(d) for d in D) for D in resblock_dilation_sizes)
         resblock = str(resblock)
         _check_geometry(n_mels, upsample_initial_channel, rates, up_k, resblock, res_k, res_d)
-        super().__init__(n_mels, math.prod(rates))
+        super().__init__(n_mels, math.prod(rates) * head_hop)
         self.C0, self.rates, self.up_kernels = upsample_initial_channel, rates, up_k
         self.resblock, self.res_kernels, self.res_dilations = resblock, res_k, res_d
 

@@ -18,6 +18,7 @@ import torch
 
 from .config import AcousticDims
 from .hifigan import CONFIGS as _HIFIGAN_CONFIGS
+from .istftnet import CONFIGS as _ISTFTNET_CONFIGS
 
 SEED = 23  # recipe seed (recipes/acoustic/core.yaml:5)
 
@@ -332,12 +333,13 @@ def make_vocoder_mel(B: int, n_mels: int, T: int, seed: int = SEED) -> torch.Ten
 
 # ------------------------------------------------------------------------------------- HiFi-GAN and BigVGAN generators
 def _make_generator(tag: str, dims: dict, seed: int, weight_norm: Optional[str], s_pre: float, s_up: float, s_unit: dict,
-                    s_post: float, up_key: str = "ups.{i}", act=None, post_bias: bool = True) -> dict[str, torch.Tensor]:
+                    s_post: float, up_key: str = "ups.{i}", act=None, post_bias: bool = True,
+                    post_channels: int = 1) -> dict[str, torch.Tensor]:
     """The walk over conv_pre, stages, blocks, units and conv_post that both generator families share, on the streams
     `<tag>/<name>.w|.f|.b`.  Convolution weights are N(0, s^2 / fan_in): s_pre, s_up (fan_in C_in k / stride), s_unit[type] per
     convolution of a unit, s_post; biases N(0, 0.05^2).  `act(sd, name, C)`, if given, adds the activation that precedes each
-    unit convolution (after the unit's weights) and activation_post.  weight_norm None: plain `weight`; "g_v": `weight_g` +
-    `weight_v`; "parametrized": `parametrizations.weight.original0` + `original1`.  v is the plain weight times a per-slice
+    unit convolution (after the unit's weights) and activation_post.  conv_post has `post_channels` outputs (1: a waveform).
+    weight_norm None: plain `weight`; "g_v": `weight_g` + `weight_v`; "parametrized": `parametrizations.weight.original0` + `original1`.  v is the plain weight times a per-slice
     factor in [0.5, 2] and g the plain weight's norm, so g != ||v|| and g v / ||v|| is the plain weight."""
     if weight_norm not in (None, "g_v", "parametrized"):
         raise ValueError(f"weight_norm {weight_norm!r}: None, 'g_v' or 'parametrized'")
@@ -375,7 +377,7 @@ def _make_generator(tag: str, dims: dict, seed: int, weight_norm: Optional[str],
     C = C0 >> len(rates)
     if act:
         act(sd, "activation_post", C)
-    put("conv_post", (1, C, 7), C * 7, s_post, bias=post_bias)
+    put("conv_post", (post_channels, C, 7), C * 7, s_post, bias=post_bias)
     return sd
 
 
@@ -395,6 +397,41 @@ def make_hifigan_state_dict(dims=HIFIGAN_DIMS["v1"], seed: int = SEED, weight_no
     N(0, 1.4^2 / (C_in k / stride)), conv_post s = 0.1, biases N(0, 0.05^2): on make_vocoder_mel the output peaks at
     0.16 - 0.9, inside tanh's curved part.  weight_norm: see _make_generator."""
     return _make_generator("hfg", dims, seed, weight_norm, 1.0, 1.4, {"1": (1.4, 0.5), "2": (0.7,)}, 0.1)
+
+
+# name -> generator configuration (istftnet.IstftNet's constructor arguments).  "c8c8i": istftnet.CONFIGS' own.  "odd":
+# HIFIGAN_DIMS["odd"]'s stages (lengths that are no powers of two) under an 8 / 2 inverse STFT.  "n20": blocks of type "2", a
+# 20 / 5 inverse STFT (a post layer of 22 channels, twiddles that are no powers of two) and phase_scale = pi.
+ISTFTNET_DIMS = {
+    "c8c8i": _ISTFTNET_CONFIGS["c8c8i"],
+    "odd": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
+                resblock="1", resblock_kernel_sizes=(3, 11), resblock_dilation_sizes=((1, 3, 5),) * 2,
+                gen_istft_n_fft=8, gen_istft_hop_size=2),
+    "n20": dict(n_mels=20, upsample_initial_channel=128, upsample_rates=(3, 2), upsample_kernel_sizes=(7, 4),
+                resblock="2", resblock_kernel_sizes=(3, 5), resblock_dilation_sizes=((1, 2), (2, 6)),
+                gen_istft_n_fft=20, gen_istft_hop_size=5, phase_scale=math.pi),
+}
+ISTFTNET_S_POST = {"1": 0.25, "2": 0.15}       # conv_post's weight scale by block type (type "2" stages end louder)
+ISTFTNET_LOG_MAG = (-2.5, 1.5)                  # conv_post's bias on the log-magnitude channels: a ramp from DC to Nyquist
+ISTFTNET_SIN_ARG = (-2.2, 2.2)                 # and on the phase channels
+
+
+def make_istftnet_state_dict(dims=ISTFTNET_DIMS["c8c8i"], seed: int = SEED, weight_norm: Optional[str] = None) -> dict[str, torch.Tensor]:
+    """Synthetic iSTFTNet generator weights in the official state-dict layout (HiFi-GAN's names, conv_post with n_fft + 2
+    output channels), from keyed streams: make_hifigan_state_dict's scales up to the last stage, conv_post N(0, s^2 / (7 C))
+    with s = ISTFTNET_S_POST[block type].  The last stage's rms grows several-fold from a one-frame mel to a long one, so the
+    spread that exercises exp and sin is put into conv_post's bias, which no input can take away: N(0, 0.05^2) plus a ramp
+    over the n_fft / 2 + 1 log-magnitude channels (ISTFTNET_LOG_MAG) and one over the phase channels (ISTFTNET_SIN_ARG).  On
+    make_vocoder_mel, per utterance (tests/test_istftnet_host.py asserts it for every case the GPU tests use): the
+    log-magnitudes span more than 4 units inside [-7, 4] (exp runs from below 0.1 to above 4), the argument of sin passes
+    -pi / 2 and +pi / 2, and the waveform peaks between 0.1 and 4 with an rms above 0.04.  weight_norm: see
+    _make_generator."""
+    N = dims["gen_istft_n_fft"]
+    sd = _make_generator("isn", dims, seed, weight_norm, 1.0, 1.4, {"1": (1.4, 0.5), "2": (0.7,)},
+                         ISTFTNET_S_POST[str(dims["resblock"])], post_channels=N + 2)
+    ramp = lambda lo_hi: torch.linspace(lo_hi[0], lo_hi[1], N // 2 + 1)
+    sd["conv_post.bias"] += torch.cat([ramp(ISTFTNET_LOG_MAG), ramp(ISTFTNET_SIN_ARG)])
+    return sd
 
 
 # name -> generator configuration (bigvgan.BigVGan's constructor arguments).  "base": the published 22.05 kHz base model.
