@@ -1334,6 +1334,74 @@ int32_t ispk_equalize_f32(const float* audio, int64_t ld_audio, const int64_t* a
                           int64_t table_doubles, int32_t sections, float* out, int64_t ld_out, int64_t* out_len,
                           double* workspace, int64_t workspace_doubles, int32_t B, int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Segmenter (csrc/segment.hip, isp_tts_amd/data/segment.py): long recordings cut into utterances at their pauses and gathered
+ * into a padded batch - the inverse of the document join.  No atomics, no host read.  audio fp32 [B][S], unit stride on S, row
+ * stride ld_audio >= S.  All integers, `/` floors.
+ *   Frames.  The trim frames of ispk_audio_measure_f64.  len = audio_len[b] if 0 <= audio_len[b] <= S, else 0; T = ceil(len /
+ *     256); hop sum h_t = the float64 sum of squares of x[256 t, min(256 t + 256, len)); p_t = (((h_t + h_{t+1}) + h_{t+2}) +
+ *     h_{t+3}) / 1024 with hops at or past T left out; frame t is active when p_t > thr, thr = (max_t p_t) factor (ref_mode 0) or
+ *     ref factor (ref_mode 1), factor = 10^(-top_db / 10) made on the host.  No active frame: no segment.
+ *   Ends.  With f, l the first and last active frames: first = max(0, 256 (f - pad)), last = min(len, 256 (l + pad) + 1024): the
+ *     (start, end) of ispk_audio_measure_f64 with pad_frames = pad.
+ *   Candidates.  Every maximal run of inactive frames u .. v-1 with f < u, v <= l and v - u >= min_silence_frames (>= 4, so
+ *     that 256 (u + 3) <= M <= 256 v: the cut lies where no active frame reaches): M = 256 ((u + 3 + v) / 2),
+ *     e_j = min(256 (u + 3 + pad), M) where the piece before ends, s_j = max(256 (v - pad), M) where the piece after starts;
+ *     j = 0 .. n-1 in frame order, and the virtual boundary e_n = last.
+ *   Choice.  One pass, each j looked at at most twice:
+ *       cur = first; have = false; j = 0
+ *       while j <= n:
+ *           L = e_j - cur
+ *           if L > max_samples and have:        (the previous pause still fitted: cut there and look at j again)
+ *               emit(cur, e_{j-1}); cur = s_{j-1}; have = false; continue
+ *           if j == n or L >= target_samples or L > max_samples:
+ *               emit(cur, e_j); cur = s_j; have = false
+ *           else: have = true
+ *           j += 1
+ *     emit(s, e) appends the segment (s, e) with flags (e - s > max_samples ? 1 : 0) | (e - s < min_samples ? 2 : 0): 1 "over", a
+ *     stretch without a usable pause; 2 "short".  wanted[b] counts every emit, count[b] = min(wanted[b], K) are stored.
+ *   Levels of a stored segment, F = {t < T : s <= 256 t < e}: frames = |F|, speech_frames = |F and active|, speech_power /
+ *     noise_power = the float64 mean of p_t over the active / inactive frames of F, 0 where that set is empty (their ratio is
+ *     the SNR estimate that curation filters on).  Every slot k >= count[b] of the [B][K] outputs is written as zeros.
+ *   Gather.  The stored segments of all items in (b, k) order, those with flags & drop left out; the first R of the rest are the
+ *     rows r = 0, 1, ..: out[r][i] = audio[b][s + i] for i < n_r = min(e - s, S_out), zeros up to S_out, bit for bit; out_len[r]
+ *     = n_r, item[r] = b, index[r] = k, bounds[r] = (s, e), row_flags[r] = flags | (4 when e - s > S_out).  Unused rows:
+ *     out_len 0, item -1, index 0, bounds (0, 0), row_flags 0, zeros in out.  rows[0] = the rows used, rows_wanted[0] = what an
+ *     unbounded R would have used.  A stored pair that is not 0 <= s <= e <= S (device data) copies nothing: bounds (0, 0).
+ * ispk_segment_workspace_bytes  *bytes (HOST memory) = what ispk_segment_plan needs for (B, S): per item the hop sums and frame
+ *                       powers (float64 [max(1, ceil(S / 256))] each) and (e_j, s_j) int64 of up to NH / 5 + 1 candidates.
+ * ispk_segment_plan     two launches.  Grid (ceil(S / 8192), B): the hop sums, 16-byte loads when audio is 16-byte aligned
+ *                       and ld_audio a multiple of four floats - the same values either way; nothing at or past len is read;
+ *                       every hop is summed in an order that is a function of the sample index alone (32 samples in order,
+ *                       eight such sums in order: ispk_audio_measure_f64's, so the frames are its frames bit for bit).  Grid
+ *                       (B), one workgroup per item: frame powers, their max, the candidates compacted in frame order with
+ *                       workgroup scans, the choice by one lane, the level sums by one wave per segment in a fixed order; all
+ *                       passes stride over the workspace, so T is not bounded by LDS.
+ *                       segments int64 [B][K][2]; flags, frames, speech_frames int32 [B][K]; count, wanted int32 [B];
+ *                       speech_power, noise_power float64 [B][K]; all contiguous.
+ * ispk_segment_gather_f32  two launches.  One workgroup writes the row table - which IS out_len / item / index / bounds /
+ *                       row_flags - from count and flags (a thread per item, an exclusive scan over 256 items at a time);
+ *                       then grid (ceil(S_out / 4096), R) copies, every workgroup reading its row's (item, start, out_len);
+ *                       16-byte loads and stores where bases, strides and the start allow.  out fp32 [R][S_out] at ld_out;
+ *                       out_len int64 [R]; item, index, row_flags int32 [R]; bounds int64 [R][2]; rows, rows_wanted int32 [1].
+ * An item's plan depends on that item alone - not on B, its place in the batch, the row stride or the alignment; repeated
+ * calls and graph replays repeat their bits.
+ * Refused before any launch: B > 65535, S (or S_out) outside [0, 2^31), K outside 1 .. 4096, R outside 0 .. 65535,
+ * min_silence_frames < 4, pad outside 0 .. 65536, max_samples < 1, target_samples < 0, min_samples < 0, ref_mode not 0 or 1, a
+ * negative or NaN factor or ref, drop outside 0 .. 3, a row stride below S (S_out), out overlapping audio (E_SHAPE); NULLs
+ * (E_NULL); a workspace below ispk_segment_workspace_bytes or off an 8-byte boundary (E_ALIGN).  B = 0 is a no-op for the plan;
+ * the gather then writes its rows as unused. */
+int32_t ispk_segment_workspace_bytes(int32_t B, int32_t S, int64_t* bytes);
+int32_t ispk_segment_plan(const float* audio, int64_t ld_audio, const int64_t* audio_len, double factor, int32_t ref_mode,
+                          double ref, int32_t pad, int32_t min_silence_frames, int64_t target_samples, int64_t max_samples,
+                          int64_t min_samples, int64_t* segments, int32_t* flags, int32_t* count, int32_t* wanted,
+                          int32_t* frames, int32_t* speech_frames, double* speech_power, double* noise_power, void* workspace,
+                          int64_t workspace_bytes, int32_t B, int32_t S, int32_t K, ispk_stream_t stream);
+int32_t ispk_segment_gather_f32(const float* audio, int64_t ld_audio, const int64_t* segments, const int32_t* flags,
+                                const int32_t* count, int32_t drop, float* out, int64_t ld_out, int64_t* out_len, int32_t* item,
+                                int32_t* index, int64_t* bounds, int32_t* row_flags, int32_t* rows, int32_t* rows_wanted,
+                                int32_t B, int32_t S, int32_t K, int32_t R, int32_t S_out, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

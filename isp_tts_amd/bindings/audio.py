@@ -1,6 +1,6 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip);
 the document join, speech marks, gain envelope and true-peak limiter (csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the
-equalizer (csrc/equalizer.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
+equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
 from typing import Optional
 
 import torch
@@ -14,7 +14,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "JOIN_TILE_SAMPLES", "JOIN_PLAN_BYTES", "JOIN_MAX", "JOIN_MAX_FADE", "join_plan", "join_audio", "MARKS_MAX_TOKENS",
            "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope", "LIMIT_TILE_SAMPLES",
            "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit", "EQ_MAX_SECTIONS", "EQ_SEGMENT_SAMPLES", "EQ_CHUNK_SAMPLES",
-           "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize"]
+           "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize", "SEGMENT_MAX_SEGMENTS", "SEGMENT_MAX_ROWS", "SEGMENT_MAX_PAD",
+           "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -469,3 +470,112 @@ def equalize(audio: Tensor, audio_len: Tensor, table: Tensor, sections: int, out
                 audio_len.data_ptr(), table.data_ptr(), table.numel(), sections, out.data_ptr(), ld(out), out_len.data_ptr(),
                 work.data_ptr(), work.numel(), B, S, _rt._stream())
     return out, out_len
+
+
+# ------------------------------------------------------------------------------------------------------ segmenter
+SEGMENT_MAX_SEGMENTS = 4096   # K: stored segments per item
+SEGMENT_MAX_ROWS = 65535      # R: rows of one gather
+SEGMENT_MAX_PAD = 65536       # frames
+SEGMENT_FLAGS = {"over": 1, "short": 2, "cut": 4}      # longer than max_samples; shorter than min_samples; cut at S_out (rows only)
+_SEGMENT_PLAN = (("segments", torch.int64, 2), ("flags", torch.int32, 0), ("frames", torch.int32, 0), ("speech_frames", torch.int32, 0),
+                 ("speech_power", torch.float64, 0), ("noise_power", torch.float64, 0))
+_SEGMENT_ROWS = (("audio_len", torch.int64, 0), ("item", torch.int32, 0), ("index", torch.int32, 0), ("bounds", torch.int64, 2),
+                 ("row_flags", torch.int32, 0))
+
+
+def segment_workspace_bytes(B: int, S: int) -> int:
+    """ispk_segment_workspace_bytes: per item the 256-sample square sums and the frame powers (float64 each) and (e, s) int64 of
+    up to NH / 5 + 1 candidates."""
+    NH = max(1, -(-S // 256))
+    return 8 * B * (2 * NH + 2 * (NH // 5 + 1))
+
+
+def _segment_audio(audio: Tensor) -> tuple[int, int]:
+    if audio.dtype != torch.float32 or audio.ndim != 2 or (audio.shape[1] > 1 and audio.stride(1) != 1):
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    if B > 65535 or S >= 2 ** 31:
+        raise ValueError(f"audio: at most 65535 items of fewer than 2^31 samples, got {tuple(audio.shape)}")
+    if B > 1 and audio.stride(0) < S:
+        raise ValueError(f"audio: rows overlap (row stride {audio.stride(0)} < {S})")
+    return B, S
+
+
+def _segment_tensors(spec, lead: tuple, given: Optional[dict], device) -> dict:
+    """The tensors of `spec` = (name, dtype, trailing 2 or 0) with the leading shape `lead`: taken from `given`, checked, or made."""
+    out = {}
+    for name, dt, two in spec:
+        shape = lead + ((2,) if two else ())
+        t = None if given is None else given.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=device)
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous {dt} {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+        out[name] = t
+    return out
+
+
+def segment_plan(audio: Tensor, audio_len: Tensor, factor: float, ref_mode: int, ref: float, pad: int, min_silence_frames: int,
+                 target_samples: int, max_samples: int, min_samples: int, max_segments: int, out: Optional[dict] = None) -> dict:
+    """ispk_segment_plan, two launches, no host read: where to cut fp32 audio [B, S] (unit stride on S, any row stride) with int64
+    lengths [B] (include/ispk.h has the arithmetic) -> a dict of segments int64 [B, K, 2]; flags, frames, speech_frames int32
+    [B, K]; speech_power, noise_power float64 [B, K]; count, wanted int32 [B]; work (uint8 scratch of segment_workspace_bytes).
+    `out` may hold any of them; the rest is allocated."""
+    B, S = _segment_audio(audio)
+    K = int(max_segments)
+    if not 1 <= K <= SEGMENT_MAX_SEGMENTS:
+        raise ValueError(f"max_segments is an integer in [1, {SEGMENT_MAX_SEGMENTS}], got {max_segments!r}")
+    dev = audio.device
+    r = _segment_tensors(_SEGMENT_PLAN, (B, K), out, dev)
+    r.update(_segment_tensors((("count", torch.int32, 0), ("wanted", torch.int32, 0)), (B,), out, dev))
+    need = segment_workspace_bytes(B, S)
+    work = None if out is None else out.get("work")
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    r["work"] = work
+    _rt._dev(audio, audio_len, *r.values())
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    # read once for the hop sums; the per-item pass moves 16 B a frame, a few times over
+    _rt._launch("segment_plan_kernels", 2.0 * B * S, 4.0 * B * S + 64.0 * B * (S // 256), _rt.lib().ispk_segment_plan, audio.data_ptr(),
+                audio.stride(0) if B > 1 else max(audio.stride(0), S), audio_len.data_ptr(), float(factor), int(ref_mode), float(ref),
+                int(pad), int(min_silence_frames), int(target_samples), int(max_samples), int(min_samples), r["segments"].data_ptr(),
+                r["flags"].data_ptr(), r["count"].data_ptr(), r["wanted"].data_ptr(), r["frames"].data_ptr(),
+                r["speech_frames"].data_ptr(), r["speech_power"].data_ptr(), r["noise_power"].data_ptr(), work.data_ptr(),
+                work.numel(), B, S, K, _rt._stream())
+    return r
+
+
+def segment_gather(audio: Tensor, segments: Tensor, flags: Tensor, count: Tensor, drop: int, rows: int, samples: int,
+                   out: Optional[dict] = None) -> dict:
+    """ispk_segment_gather_f32, two launches, no host read: the stored segments of a plan without a flag of the mask `drop`, in
+    (item, index) order, into the rows of audio fp32 [R, S_out] -> a dict of audio; audio_len int64 [R]; item, index, row_flags
+    int32 [R]; bounds int64 [R, 2]; rows, rows_wanted int32 [1].  `out` may hold any of them; out["audio"] may have any row
+    stride and may not overlap `audio`."""
+    B, S = _segment_audio(audio)
+    R, S_out = int(rows), int(samples)
+    if not 0 <= R <= SEGMENT_MAX_ROWS or not 0 <= S_out < 2 ** 31:
+        raise ValueError(f"rows in [0, {SEGMENT_MAX_ROWS}] and samples in [0, 2^31), got {rows!r}, {samples!r}")
+    if segments.ndim != 3:
+        raise ValueError(f"segments: int64 [{B}, K, 2], got {tuple(segments.shape)}")
+    K = segments.shape[1]
+    _segment_tensors((("segments", torch.int64, 2), ("flags", torch.int32, 0)), (B, K), dict(segments=segments, flags=flags), None)
+    _segment_tensors((("count", torch.int32, 0),), (B,), dict(count=count), None)
+    dev = audio.device
+    r = _segment_tensors(_SEGMENT_ROWS, (R,), out, dev)
+    r.update(_segment_tensors((("rows", torch.int32, 0), ("rows_wanted", torch.int32, 0)), (1,), out, dev))
+    o = None if out is None else out.get("audio")
+    o = torch.empty((R, S_out), dtype=torch.float32, device=dev) if o is None else o
+    if o.dtype != torch.float32 or tuple(o.shape) != (R, S_out) or (S_out > 1 and o.stride(1) != 1) or (R > 1 and o.stride(0) < S_out):
+        raise ValueError(f"out audio: fp32 [{R}, {S_out}] with unit stride on the samples, got {o.dtype} {tuple(o.shape)} strides "
+                         f"{tuple(o.stride())}")
+    r["audio"] = o
+    _rt._dev(audio, segments, flags, count, *r.values())
+    _rt._launch("segment_gather_kernels", 0.0, 8.0 * R * S_out, _rt.lib().ispk_segment_gather_f32, audio.data_ptr(),
+                audio.stride(0) if B > 1 else max(audio.stride(0), S), segments.data_ptr(), flags.data_ptr(), count.data_ptr(), int(drop),
+                o.data_ptr(), o.stride(0) if R > 1 else max(o.stride(0), S_out), r["audio_len"].data_ptr(), r["item"].data_ptr(),
+                r["index"].data_ptr(), r["bounds"].data_ptr(), r["row_flags"].data_ptr(), r["rows"].data_ptr(),
+                r["rows_wanted"].data_ptr(), B, S, K, R, S_out, _rt._stream())
+    return r
