@@ -34,12 +34,6 @@ struct Taps {
     float fu[12], fd[12];
 };
 
-__device__ __forceinline__ int scaled_len(const int64_t* len, int len_mul, int b, int T) {
-    if (!len) return T;
-    const int64_t l = len[b] * (int64_t)len_mul;
-    return (l >= 0 && l <= T) ? (int)l : 0;
-}
-
 __device__ __forceinline__ float snake(float u, float al, float inv_b) {
     const float s = sinf(al * u);
     return fmaf(inv_b * s, s, u);
@@ -53,7 +47,7 @@ __global__ __launch_bounds__(256) void snake_aa_kernel(const float* __restrict__
     const int c = blockIdx.y * 32 + (tid & 7) * 4;
     const int t0 = blockIdx.x * kWgRows + (tid >> 3) * kRows;
     if (t0 >= T) return;
-    const int n = scaled_len(len, len_mul, b, T);
+    const int n = valid_len(len, b, T, len_mul);
     const int64_t row0 = (int64_t)b * T;
     const float* xc = x + row0 * ldx + c;
     float* oc = out + row0 * ldo + c;

@@ -153,6 +153,14 @@ __device__ __forceinline__ float gelu_grad_fast(float x) {
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 
+// Item b's length from a device array, in units of `mul` per entry (a vocoder's rows per mel frame): T without an array, and 0
+// for a product outside [0, T] - device data is not trusted, such an item reads and writes as empty.
+__device__ __forceinline__ int valid_len(const int64_t* len, int b, int T, int mul = 1) {
+    if (!len) return T;
+    const int64_t l = len[b] * (int64_t)mul;
+    return (l >= 0 && l <= T) ? (int)l : 0;
+}
+
 constexpr int kWave = 64;
 
 __device__ __forceinline__ float wave_sum(float v) {   // every lane ends with the sum over the wave's 64 lanes

@@ -1,4 +1,5 @@
-// Radix-4 Stockham FFT in LDS, shared by features.hip (STFT, YIN autocorrelation) and vocoder.hip (the ISTFT head).
+// Radix-4 Stockham FFT in LDS, shared by features.hip (STFT, YIN autocorrelation) and the 1024 / 256 tile of stft_tile.h (the
+// ISTFT head, the denoiser, Griffin-Lim).
 //
 // Complex values are float2 (re, im).  `tw` is an LDS table of kTw twiddles W_kTw^m = exp(-2 pi i m / kTw), m < kTw, made in
 // float64 and rounded once (data.features.twiddles() holds kTw = 2048; W_1024^m is its entry 2m, the same fp32 value).  An

@@ -3,31 +3,27 @@
 // (csrc/features.hip): n_fft = win = 1024, hop 256, periodic Hann, 384 zeros on both sides, no centring, so an utterance of
 // T frames has n = 256 T samples (include/ispk.h has the definition).
 //
-//   griffinlim_kernel<kInit, kFast>  grid (ceil(256 T / 4096), B), 512 threads = 4 groups of 128: denoise.hip's geometry
-//                    with the extractor's framing.  A workgroup writes 16 hop segments (4096 samples) of ONE utterance.  Sample
-//                    s takes frames floor((s + 384) / 256) - 3 .. floor((s + 384) / 256), so the tile at hop q0 needs the
-//                    up-to-20 frames q0 - 2 .. q0 + 17 within [0, T): the 4 frames it shares with its neighbours are
-//                    transformed by both (no atomics, no second pass, nothing in HBM between analysis and synthesis).  Frames
-//                    run 4 at a time, one per group:
-//                      gather    (step) 1024 samples x[256 f - 384 + j] inside [0, n), zero elsewhere (a select: never an index
-//                                outside the utterance), times the window, as z[m] = x[2m] + i x[2m+1] into the ping buffer;
-//                      forward   (step) 512-point complex Stockham FFT (fft.h) into the frame's 4 KB slot;
+//   griffinlim_kernel<kInit, kFast>  the 1024 / 256 tile of stft_tile.h (geometry, LDS, bank and bit-reproducibility notes are
+//                    there) with the extractor's framing: sample s takes frames floor((s + 384) / 256) - 3 .. floor((s + 384) /
+//                    256), so the tile at hop q0 needs the up-to-20 frames q0 - 2 .. q0 + 17 within [0, T).  Per frame:
+//                      gather    (step) 1024 samples x[256 f - 384 + j] inside [0, n), zero elsewhere (gather_zero_padded: a
+//                                select, never an index outside the utterance), times the window, into the ping buffer;
+//                      forward   (step) 512-point FFT into the frame's slot;
 //                      project   per bin pair (k, 512 - k): step: X by real_split, Y = M X / sqrt(|X|^2) (IEEE sqrt and
 //                                division), Y = M where |X|^2 = 0; init: Y = M (cos, sin)(2 pi u), u = (hash >> 8) 2^-24 from
 //                                drop_hash(seed, 513 f + k) by sincospif.  M = 0 gives exactly 0.  Y / 1024 is packed straight into
-//                                the inverse's half-length spectrum Z_k = (Y_k + conj Y_{512-k}) + i (Y_k - conj Y_{512-k})
-//                                conj(W_1024^k) (imaginary parts of bins 0 and 512 dropped, as irfft);
-//                      inverse   512-point FFT back into the slot: the frame's 1024 real samples in order;
-//                    then per output sample the window-weighted overlap-add of its <= 4 frames and the division by the sum of
-//                    their w^2 (positive for every s < n and every T >= 1), both in ascending frame order.  Samples at or past
-//                    n are written as 0.  LDS: 80 KB of frame slots + 16 KB of ping buffers + 8 KB twiddles + 4 KB window.
+//                                the inverse's half-length spectrum: the loop of stft_tile.h's pack_pairs, written out here
+//                                (keep the two alike);
+//                      inverse   512-point FFT back into the slot;
+//                    then the overlap-add over the utterance's T frames (the w^2 sum is positive for every s < n and every
+//                    T >= 1).  Samples at or past n are written as 0.  A frame's arithmetic depends on (n, f, seed) alone.
 //                    griffinlim_kernel<false, true> is the fast (momentum) step: the step with a second input row `prev` and
 //                    a scalar alpha = momentum / (1 + momentum); its gather takes fma(-alpha, prev[i], x[i]) under the same
 //                    select and nothing else differs.  The textbook iteration takes the phase of STFT(x_n) - alpha STFT(x_{n-1});
 //                    the STFT is linear, so that is STFT(x_n - alpha x_{n-1}): one more waveform read per sample, no spectrum in
 //                    HBM, still one launch per iteration.  A compile-time variant: <false> and <true> keep their code.
 //   griffinlim_error_kernel  grid (ceil(T / 16), B), 512 threads: the spectral convergence's per-frame sums.  The analysis half of
-//                    the step - gather, window, forward FFT, real_split - of 16 frames, 4 at a time, one per group; a frame
+//                    the step - the same gather, forward FFT, real_split - of 16 frames, 4 at a time, one per group; a frame
 //                    belongs to one workgroup (no halo).  Thread t of the group accumulates (sqrt(|X[k]|^2) - M[k])^2 and M[k]^2
 //                    over k = t, t + 128, .. <= 512 with fma, then a fixed tree (shuffles within a wave, the group's two waves
 //                    through LDS) gives work[b][f] = (num_f, den_f), fp32, for f < Tb.  LDS: 32 KB ping + pong, 8 KB twiddles,
@@ -36,49 +32,29 @@
 //                    fixed tree in LDS), err[b] = (float)sqrt(num / den); 0 for Tb = 0, and with den = 0: 0 if num = 0, else +inf.
 //   mel_to_linear_kernel  grid (ceil(T / 8), B), 256 threads.  exp(mel) of 8 frames into LDS, then thread k accumulates
 //                    sum_m P[k][m] exp(mel[m][f]) for the 8 frames in ascending m (P is read transposed: lanes on k), clamps at 0.
-// A frame's arithmetic depends on (n, f, seed) alone and a sample's on (n, s) alone - not on the tile, on B, on T or on the
-// row's neighbours - and there are no atomics: a ragged batch gives each utterance the bits it gets alone, and repeated calls
-// and graph replays repeat theirs.  LDS access patterns are denoise_kernel's (see there).
 //
 // gfx950 resources (csrc/resource_report.py griffinlim.hip; no spills, no scratch):
-//   griffinlim_kernel<false>        72 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
+//   griffinlim_kernel<false>        76 VGPRs, LDS 110,592 B dynamic (one workgroup of 8 waves per CU: the LDS sets the occupancy
+//                                   of 2 waves per SIMD; the report's register-only 6, 7 at the init's count, binds nothing)
 //   griffinlim_kernel<true>         66 VGPRs, LDS 110,592 B dynamic
-//   griffinlim_kernel<false, true>  72 VGPRs, LDS 110,592 B dynamic
-//   griffinlim_error_kernel         58 VGPRs, LDS 45,120 B dynamic
+//   griffinlim_kernel<false, true>  74 VGPRs, LDS 110,592 B dynamic
+//   griffinlim_error_kernel         60 VGPRs, LDS 45,120 B dynamic
 //   griffinlim_error_sum_kernel     14 VGPRs, LDS 4,096 B static
 //   mel_to_linear_kernel      60 VGPRs (fp32 and fp16 mel), LDS 4,096 B static
 #include <math.h>
 
 #include "common.h"
 #include "dropout.h"
-#include "fft.h"
+#include "stft_tile.h"
 
 namespace {
 
-constexpr int kHop = 256;
-constexpr int kNfft = 1024;
-constexpr int kHalf = kNfft / 2;                   // 512: the complex transform's length
-constexpr int kBins = kHalf + 1;                   // 513
 constexpr int kPad = (kNfft - kHop) / 2;           // 384 zeros on each side, the extractor's pad
-constexpr int kSegs = 16;                          // hop segments written per workgroup
-constexpr int kTile = kSegs * kHop;                // 4096 samples
-constexpr int kSlots = kSegs + 4;                  // frame slots: 20 frames touch a tile
-constexpr int kGroups = 4;                         // transforms side by side
-constexpr int kGT = 128;                           // threads per transform
-constexpr int kThreads = kGroups * kGT;
-constexpr int kTw = 1024;                          // W_1024^m: the 512-point FFT's twiddles and the split's
-constexpr size_t kLds = sizeof(cf) * (kTw + kGroups * kHalf) + sizeof(float) * (kNfft + kSlots * kNfft);
 constexpr int kMaxFrames = (INT32_MAX - 2 * kTile) / kHop;
 
 constexpr int kMelFrames = 8;                      // frames per workgroup of mel_to_linear_kernel
 constexpr int kMelThreads = 256;
 constexpr int kMaxMels = 128;
-
-__device__ __forceinline__ int valid_frames(const int64_t* mel_len, int b, int T) {
-    if (!mel_len) return T;
-    const int64_t l = mel_len[b];
-    return (l >= 0 && l <= T) ? (int)l : 0;
-}
 
 // Y / 1024 of the projection: M X / |X|, M where |X|^2 = 0, exactly 0 for M = 0
 __device__ __forceinline__ cf project(cf X, float M) {
@@ -99,13 +75,6 @@ __device__ __forceinline__ cf hashed_phase(float M, uint64_t seed, int f, int k)
     return make_float2(ms * c, ms * s);
 }
 
-// the fast step's sample: x[i] - alpha prev[i] inside [0, n), 0 elsewhere (a select: never an index outside the utterance, in
-// either row)
-__device__ __forceinline__ float fast_sample(const float* __restrict__ xrow, const float* __restrict__ prow, float alpha,
-                                             bool live, int i, int n) {
-    return live && i >= 0 && i < n ? fmaf(-alpha, prow[i], xrow[i]) : 0.f;
-}
-
 template <bool kInit, bool kFast = false>
 __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __restrict__ audio, int64_t lda,
                                                               const float* __restrict__ prev, int64_t ldp, float alpha,
@@ -115,13 +84,10 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
                                                               int64_t ldo, int64_t* __restrict__ audio_len, int T,
                                                               uint64_t seed) {
     extern __shared__ float4 lds_raw[];
-    cf* tw = reinterpret_cast<cf*>(lds_raw);                          // [kTw]
-    cf* ping = tw + kTw;                                              // [kGroups][512]
-    float* win = reinterpret_cast<float*>(ping + kGroups * kHalf);    // [1024]
-    float* frames = win + kNfft;                                      // [kSlots][1024]
+    const TileLds tile = carve_tile(lds_raw);
 
     const int b = blockIdx.y, tid = threadIdx.x, g = tid / kGT, lt = tid % kGT;
-    const int Tb = valid_frames(mel_len, b, T), n = Tb * kHop, S = T * kHop;
+    const int Tb = valid_len(mel_len, b, T), n = Tb * kHop, S = T * kHop;
     const int m0 = blockIdx.x * kTile, m1 = min(S, m0 + kTile);
     const int mv = max(m0, min(n, m1));                               // [m0, mv) are the tile's samples inside the utterance
     static_assert(!(kInit && kFast), "the initial waveform reads no audio");
@@ -134,34 +100,24 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
     if (mv > m0) {
         const int q0 = blockIdx.x * kSegs;
         const int f_lo = max(0, q0 - 2), f_hi = min(Tb, (mv - 1 + kPad) / kHop + 1), nf = f_hi - f_lo;   // nf <= kSlots
-        const cf* tw2048 = reinterpret_cast<const cf*>(tables);
-        for (int i = tid; i < kTw; i += kThreads) tw[i] = tw2048[2 * i];
-        for (int i = tid; i < kNfft; i += kThreads) win[i] = tables[2 * 2048 + i];
+        load_tables(tile.tw, tile.win, tables, tid);
         __syncthreads();
-        cf* A = ping + g * kHalf;
+        cf* A = tile.ping + g * kHalf;
         for (int r = 0; r * kGroups < nf; ++r) {
             const int fs = r * kGroups + g, f = f_lo + fs;            // slot and frame; fs >= nf: transformed, never read
             const bool live = fs < nf;
-            cf* Bf = reinterpret_cast<cf*>(frames + fs * kNfft);
+            cf* Bf = reinterpret_cast<cf*>(tile.frames + fs * kNfft);
             if (!kInit) {
                 const int i0 = f * kHop - kPad;                       // the frame's first sample
-                for (int m = lt; m < kHalf; m += kGT) {
-                    const int ia = i0 + 2 * m, ib = ia + 1;
-                    float xa, xb;
-                    if (kFast) {
-                        xa = fast_sample(xrow, prow, alpha, live, ia, n);
-                        xb = fast_sample(xrow, prow, alpha, live, ib, n);
-                    } else {
-                        xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
-                        xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
-                    }
-                    A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
-                }
+                if (kFast)                                            // x[i] - alpha prev[i]: one select covers both rows
+                    gather_zero_padded(A, tile.win, i0, n, live, lt, [&](int i) { return fmaf(-alpha, prow[i], xrow[i]); });
+                else
+                    gather_zero_padded(A, tile.win, i0, n, live, lt, [&](int i) { return xrow[i]; });
                 __syncthreads();
-                fft<false, kGT, kTw>(A, Bf, kHalf, lt, tw);
+                fft<false, kGT, kTw>(A, Bf, kHalf, lt, tile.tw);
             }
             const float* mf = mrow + (int64_t)f * kBins;
-            for (int k = lt; k <= 256; k += kGT) {
+            for (int k = lt; k <= 256; k += kGT) {                    // pack_pairs of stft_tile.h, written out (see the header)
                 const int m = kHalf - k;
                 const float Mk = live ? mf[k] : 0.f, Mm = live ? mf[m] : 0.f;
                 cf xk, xm;
@@ -169,8 +125,8 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
                     xk = hashed_phase(Mk, seed, f, k);
                     xm = k == 256 ? xk : hashed_phase(Mm, seed, f, m);
                 } else {
-                    xk = project(real_split(Bf, k, kHalf, tw[k]), Mk);
-                    xm = k == 256 ? xk : project(real_split(Bf, m, kHalf, tw[m]), Mm);
+                    xk = project(real_split(Bf, k, kHalf, tile.tw[k]), Mk);
+                    xm = k == 256 ? xk : project(real_split(Bf, m, kHalf, tile.tw[m]), Mm);
                 }
                 if (k == 0) {                                         // irfft drops the imaginary parts of DC and Nyquist
                     xk.y = 0.f;
@@ -178,31 +134,19 @@ __global__ void __launch_bounds__(kThreads) griffinlim_kernel(const float* __res
                 }
                 {   // Z_k
                     const cf e = make_float2(xk.x + xm.x, xk.y - xm.y), d = make_float2(xk.x - xm.x, xk.y + xm.y);
-                    const cf o = ctw<true>(d, tw[k]);
+                    const cf o = ctw<true>(d, tile.tw[k]);
                     A[k] = make_float2(e.x - o.y, e.y + o.x);
                 }
                 if (k > 0 && k < 256) {   // Z_{512-k}
                     const cf e = make_float2(xm.x + xk.x, xm.y - xk.y), d = make_float2(xm.x - xk.x, xm.y + xk.y);
-                    const cf o = ctw<true>(d, tw[m]);
+                    const cf o = ctw<true>(d, tile.tw[m]);
                     A[m] = make_float2(e.x - o.y, e.y + o.x);
                 }
             }
             __syncthreads();
-            fft<true, kGT, kTw>(A, Bf, kHalf, lt, tw);
+            fft<true, kGT, kTw>(A, Bf, kHalf, lt, tile.tw);
         }
-        // ---- window, overlap-add over the utterance's own frames, envelope division (frame order, no atomics)
-        for (int m = m0 + tid; m < mv; m += kThreads) {
-            const int u = m + kPad;                                   // position in the padded signal
-            const int fmin = u >= kNfft ? (u - kNfft) / kHop + 1 : 0, fmax = min(Tb - 1, u / kHop);
-            float acc = 0.f, env = 0.f;
-            for (int f = fmin; f <= fmax; ++f) {
-                const int j = u - f * kHop;
-                const float wj = win[j];
-                acc = fmaf(frames[(f - f_lo) * kNfft + j], wj, acc);
-                env = fmaf(wj, wj, env);
-            }
-            orow[m] = acc / env;
-        }
+        overlap_add(orow, tile.frames, tile.win, m0, mv, kPad, f_lo, Tb, tid);
     }
     for (int m = mv + tid; m < m1; m += kThreads) orow[m] = 0.f;
 }
@@ -225,27 +169,19 @@ __global__ void __launch_bounds__(kThreads) griffinlim_error_kernel(const float*
     float2* part = reinterpret_cast<float2*>(win + kNfft);            // [kGroups][2]: one (num, den) per wave
 
     const int b = blockIdx.y, tid = threadIdx.x, g = tid / kGT, lt = tid % kGT;
-    const int Tb = valid_frames(mel_len, b, T), n = Tb * kHop, f0 = blockIdx.x * kErrFrames;
+    const int Tb = valid_len(mel_len, b, T), n = Tb * kHop, f0 = blockIdx.x * kErrFrames;
     if (f0 >= Tb) return;
     const float* xrow = audio + (int64_t)b * lda;
     const float* mrow = mag + (int64_t)b * ldm;
     float* wrow = work + (int64_t)b * ldw;
-    const cf* tw2048 = reinterpret_cast<const cf*>(tables);
-    for (int i = tid; i < kTw; i += kThreads) tw[i] = tw2048[2 * i];
-    for (int i = tid; i < kNfft; i += kThreads) win[i] = tables[2 * 2048 + i];
+    load_tables(tw, win, tables, tid);
     __syncthreads();
     cf *A = ping + g * kHalf, *Bf = pong + g * kHalf;
     const int nf = min(kErrFrames, Tb - f0);
     for (int r = 0; r * kGroups < nf; ++r) {
         const int f = f0 + r * kGroups + g;
         const bool live = f < Tb;                                     // a group past Tb transforms zeros and writes nothing
-        const int i0 = f * kHop - kPad;
-        for (int m = lt; m < kHalf; m += kGT) {
-            const int ia = i0 + 2 * m, ib = ia + 1;
-            const float xa = live && ia >= 0 && ia < n ? xrow[ia] : 0.f;
-            const float xb = live && ib >= 0 && ib < n ? xrow[ib] : 0.f;
-            A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
-        }
+        gather_zero_padded(A, win, f * kHop - kPad, n, live, lt, [&](int i) { return xrow[i]; });
         __syncthreads();
         fft<false, kGT, kTw>(A, Bf, kHalf, lt, tw);
         // thread-strided partials over the 513 bins in ascending k, then a fixed tree: lanes, then the group's two waves
@@ -276,7 +212,7 @@ __global__ void __launch_bounds__(kSumThreads) griffinlim_error_sum_kernel(const
                                                                            const int64_t* __restrict__ mel_len,
                                                                            float* __restrict__ err, int T) {
     __shared__ double sn[kSumThreads], sd[kSumThreads];
-    const int b = blockIdx.x, tid = threadIdx.x, Tb = valid_frames(mel_len, b, T);
+    const int b = blockIdx.x, tid = threadIdx.x, Tb = valid_len(mel_len, b, T);
     const float* wrow = work + (int64_t)b * ldw;
     double num = 0.0, den = 0.0;
     for (int f = tid; f < Tb; f += kSumThreads) {                     // ascending f per thread, then a fixed tree
@@ -306,7 +242,7 @@ __global__ void __launch_bounds__(kMelThreads) mel_to_linear_kernel(const TM* __
                                                                     int64_t ldm, int n_mels, int T) {
     __shared__ float e[kMaxMels][kMelFrames];
     const int b = blockIdx.y, t0 = blockIdx.x * kMelFrames, tid = threadIdx.x;
-    const int nv = min(kMelFrames, valid_frames(mel_len, b, T) - t0);
+    const int nv = min(kMelFrames, valid_len(mel_len, b, T) - t0);
     if (nv <= 0) return;
     const TM* mb = mel + (int64_t)b * sb;
     for (int i = tid; i < n_mels * kMelFrames; i += kMelThreads) {

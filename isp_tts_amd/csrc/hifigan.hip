@@ -61,12 +61,6 @@ struct ConvParams {
     int accumulate;
 };
 
-__device__ __forceinline__ int scaled_len(const int64_t* len, int len_mul, int b, int T) {
-    if (!len) return T;
-    const int64_t l = len[b] * (int64_t)len_mul;
-    return (l >= 0 && l <= T) ? (int)l : 0;
-}
-
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 template <bool BF, int WN, int TNT>
@@ -85,7 +79,7 @@ __global__ __launch_bounds__(256) void hifigan_conv_kernel(ConvParams p) {
     const int l31 = lane & 31, h = lane >> 5;
     const int b = blockIdx.z, t0 = blockIdx.x * kTM;
     const int nt = blockIdx.y / p.up, ph = blockIdx.y - nt * p.up, n0 = nt * BN;
-    const int len = scaled_len(p.len, p.len_mul, b, p.T);
+    const int len = valid_len(p.len, b, p.T, p.len_mul);
     const int64_t row0 = (int64_t)b * p.T;
 
     if (t0 >= len) {                                  // nothing valid in this tile: its rows are zeros
@@ -310,7 +304,7 @@ __global__ __launch_bounds__(kPostS) void hifigan_post_kernel(const float* __res
                                                               int64_t* __restrict__ audio_len, int T, int S, int C, float slope) {
     __shared__ float win[kPostWin * kPostPitch];
     const int b = blockIdx.y, tid = threadIdx.x, s0 = blockIdx.x * kPostS;
-    const int n = scaled_len(len, len_mul, b, T);
+    const int n = valid_len(len, b, T, len_mul);
     if (blockIdx.x == 0 && tid == 0 && audio_len) audio_len[b] = n;
     float* arow = audio + (int64_t)b * lda;
     const int s = s0 + tid;

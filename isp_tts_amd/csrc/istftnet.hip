@@ -41,12 +41,6 @@ constexpr int kWinRows = kTF + 6;       // the frames' rows and the 3-row halo o
 constexpr int kPitch = kKC + 1;         // odd row pitch: consecutive frames read distinct banks
 constexpr int kOut = kTF - 3;           // hop blocks a workgroup owns: a block sums 4 consecutive frames
 
-__device__ __forceinline__ int scaled_len(const int64_t* len, int len_mul, int b, int T) {
-    if (!len) return T;
-    const int64_t l = len[b] * (int64_t)len_mul;
-    return (l >= 0 && l <= T) ? (int)l : 0;
-}
-
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // table: cos(2 pi m / N) [N], sin(2 pi m / N) [N], w[t] / N [N], w[t]^2 [N]
@@ -61,7 +55,7 @@ __global__ __launch_bounds__(kTF) void istftnet_head_kernel(const float* __restr
     static_assert(kTF * FP <= kWinRows * kPitch, "the frames reuse the row window");
     __shared__ float smem[kWinRows * kPitch];
     const int b = blockIdx.y, tid = threadIdx.x, o0 = blockIdx.x * kOut;
-    int n = scaled_len(len, len_mul, b, T);
+    int n = valid_len(len, b, T, len_mul);
     if (n < 2) n = 0;                                  // one row has no reflection: counts as empty
     if (blockIdx.x == 0 && tid == 0 && audio_len) audio_len[b] = (int64_t)HOP * n;
     float* arow = audio + (int64_t)b * lda;

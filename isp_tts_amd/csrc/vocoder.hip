@@ -17,22 +17,14 @@
 //                          they come from L2: staging in LDS would save only those L2 reads, and would cost a barrier and
 //                          up to 4 KB of LDS per frame at dim 1024.  The bound is HBM: read the fp32 residual once, write
 //                          the normalised rows once.
-//   istft_head_kernel      grid (ceil(S / 4096), B), 512 threads = 4 groups of 128.  A workgroup writes 16 hop segments
-//                          (4096 samples) of one utterance: it transforms the up-to-20 frames s0 - 2 .. s0 + 17 that touch
-//                          them (the 4-frame halo is recomputed by the neighbouring workgroup: no atomics, no second pass),
-//                          4 frames at a time, one per group:
-//                            prologue  exp, clip at 100 (a compare that keeps NaN, as torch.clip), sincos (range-reduced
-//                                      libm sincosf: p is an unbounded Linear output), x 1/1024 (irfft's norm), for the bin
-//                                      pair (k, 512 - k), straight into the half-length spectrum
-//                                      Z_k = (X_k + conj X_{512-k}) + i (X_k - conj X_{512-k}) conj(W_1024^k)
-//                                      (the real inverse as a 512-point complex one; the imaginary parts of bins 0 and 512
-//                                      are dropped, as irfft does);
-//                            inverse   512-point complex Stockham FFT (fft.h) whose last pass lands in the frame's 4 KB
-//                                      LDS slot: z[m] = x[2m] + i x[2m+1] is the frame's 1024 real samples in order;
-//                          then per output sample the window-weighted overlap-add of its <= 4 frames within [0, len_b) and
-//                          the division by the sum of their w^2 (the envelope of the utterance's own frames), in frame
-//                          order.  Samples at or past len_b * 256 are written as 0.  LDS: 80 KB of frames + 16 KB of
-//                          ping buffers + 8 KB twiddles + 4 KB window.
+//   istft_head_kernel      the 1024 / 256 tile of stft_tile.h (geometry, LDS, bank and bit-reproducibility notes are there)
+//                          with the framing of padding="same": 384 samples trimmed in front, so the tile at frame s0
+//                          transforms the up-to-20 frames s0 - 2 .. s0 + 17 of the utterance.  Per frame, the prologue
+//                          exp, clip at 100 (a compare that keeps NaN, as torch.clip), sincos (range-reduced libm sincosf:
+//                          p is an unbounded Linear output), x 1/1024 (irfft's norm) for the bin pair (k, 512 - k), packed
+//                          straight into the inverse's half-length spectrum (pack_pairs); the inverse FFT into the frame's
+//                          slot; then the overlap-add over the frames within [0, len_b).  Samples at or past len_b * 256 are
+//                          written as 0.
 // Every sum runs in a fixed order and there are no atomics: repeated calls and graph replays give the same bits.  A device
 // mel_len outside [0, T] is treated as 0 by all three kernels (zero rows, audio_len 0, nothing read).
 //
@@ -40,24 +32,16 @@
 //   vocoder_unfold_kernel<f32|f16, f32|bf16>   14 VGPRs, LDS 19,968 B static
 //   dwconv7_ln_kernel<NC, f32|bf16>            no LDS; 131 VGPRs at dim 384 (occupancy 3), 176 at dim 512 (2), 256 + 81
 //                                              AGPRs at dim 1024 (1)
-//   istft_head_kernel                           70 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
+//   istft_head_kernel                           72 VGPRs, LDS 110,592 B dynamic (one workgroup per CU)
 #include <hip/hip_fp16.h>
 
 #include "common.h"
-#include "fft.h"
+#include "stft_tile.h"
 
 namespace {
 
-constexpr int kHop = 256;
-constexpr int kNfft = 1024;
 constexpr int kPad = (kNfft - kHop) / 2;          // 384: Vocos ISTFT padding="same"
 constexpr int kMaxMels = 128;
-
-__device__ __forceinline__ int valid_len(const int64_t* mel_len, int b, int T) {
-    if (!mel_len) return T;
-    const int64_t l = mel_len[b];
-    return (l >= 0 && l <= T) ? (int)l : 0;
-}
 
 // ------------------------------------------------------------------------------------------------------------ unfold
 constexpr int kUfFrames = 32;
@@ -188,16 +172,6 @@ int32_t launch_dwconv(bool bf16, const float* x, int64_t ldx, const float* w, co
 }
 
 // -------------------------------------------------------------------------------------------------------- ISTFT head
-constexpr int kSegs = 16;                          // hop segments written per workgroup
-constexpr int kSlots = kSegs + 4;                  // frames transformed per workgroup (2-frame halo on each side)
-constexpr int kGroups = 4;                         // transforms side by side
-constexpr int kGT = 128;                           // threads per transform
-constexpr int kHThreads = kGroups * kGT;
-constexpr int kTw = 1024;                          // W_1024^m: the 512-point FFT's twiddles and the merge's
-constexpr int kBins = kNfft / 2 + 1;               // 513
-constexpr int kTableFloats = 2 * 2048 + kNfft;     // data.features.twiddles() (W_2048), then the window
-constexpr size_t kHeadLds = sizeof(cf) * (kTw + kGroups * 512) + sizeof(float) * (kNfft + kSlots * kNfft);
-
 // X_k / 1024 = clip(exp(lm), max=100) (cos p + i sin p) / 1024
 __device__ __forceinline__ cf head_bin(const float* hrow, int k) {
     float mag = expf(hrow[k]);
@@ -208,15 +182,12 @@ __device__ __forceinline__ cf head_bin(const float* hrow, int k) {
     return make_float2(mag * cs, mag * sn);
 }
 
-__global__ void __launch_bounds__(kHThreads) istft_head_kernel(const float* __restrict__ h, int64_t ldh,
-                                                               const int64_t* __restrict__ mel_len,
-                                                               const float* __restrict__ tables, float* __restrict__ audio,
-                                                               int64_t lda, int64_t* __restrict__ audio_len, int T, int S) {
+__global__ void __launch_bounds__(kThreads) istft_head_kernel(const float* __restrict__ h, int64_t ldh,
+                                                              const int64_t* __restrict__ mel_len,
+                                                              const float* __restrict__ tables, float* __restrict__ audio,
+                                                              int64_t lda, int64_t* __restrict__ audio_len, int T, int S) {
     extern __shared__ float4 lds_raw[];
-    cf* tw = reinterpret_cast<cf*>(lds_raw);                          // [kTw]
-    cf* ping = tw + kTw;                                              // [kGroups][512]
-    float* win = reinterpret_cast<float*>(ping + kGroups * 512);      // [1024]
-    float* frames = win + kNfft;                                      // [kSlots][1024]
+    const TileLds tile = carve_tile(lds_raw);
 
     const int b = blockIdx.y, tid = threadIdx.x, g = tid / kGT, lt = tid % kGT;
     const int s0 = blockIdx.x * kSegs;
@@ -224,59 +195,30 @@ __global__ void __launch_bounds__(kHThreads) istft_head_kernel(const float* __re
     if (blockIdx.x == 0 && tid == 0 && audio_len) audio_len[b] = (int64_t)Tb * kHop;
     const int nseg = max(0, min(kSegs, Tb - s0));
     float* arow = audio + (int64_t)b * lda;
-    const int m0 = s0 * kHop, m1 = min(S, m0 + kSegs * kHop);
+    const int m0 = s0 * kHop, m1 = min(S, m0 + kTile), mv = m0 + nseg * kHop;   // [m0, mv): the tile's samples of the utterance
 
     if (nseg > 0) {
         const int f_lo = max(0, s0 - 2), f_hi = min(Tb, s0 + nseg + 2), nf = f_hi - f_lo;
-        const cf* tw2048 = reinterpret_cast<const cf*>(tables);
-        for (int i = tid; i < kTw; i += kHThreads) tw[i] = tw2048[2 * i];
-        for (int i = tid; i < kNfft; i += kHThreads) win[i] = tables[2 * 2048 + i];
+        load_tables(tile.tw, tile.win, tables, tid);
         __syncthreads();
-        cf* Z = ping + g * 512;
+        cf* Z = tile.ping + g * kHalf;
         for (int r = 0; r * kGroups < nf; ++r) {
-            const int f = r * kGroups + g;                            // slot; f >= nf: transformed, never read
-            if (f < nf) {
-                const float* hrow = h + ((int64_t)b * T + f_lo + f) * ldh;
-                for (int k = lt; k <= 256; k += kGT) {
-                    const int m = 512 - k;
-                    cf xk = head_bin(hrow, k);
-                    cf xm = k == 256 ? xk : head_bin(hrow, m);
-                    if (k == 0) {                                     // irfft drops the imaginary parts of DC and Nyquist
-                        xk.y = 0.f;
-                        xm.y = 0.f;
-                    }
-                    {   // Z_k
-                        const cf e = make_float2(xk.x + xm.x, xk.y - xm.y), d = make_float2(xk.x - xm.x, xk.y + xm.y);
-                        const cf o = ctw<true>(d, tw[k]);
-                        Z[k] = make_float2(e.x - o.y, e.y + o.x);
-                    }
-                    if (k > 0 && k < 256) {   // Z_{512-k}
-                        const cf e = make_float2(xm.x + xk.x, xm.y - xk.y), d = make_float2(xm.x - xk.x, xm.y + xk.y);
-                        const cf o = ctw<true>(d, tw[m]);
-                        Z[m] = make_float2(e.x - o.y, e.y + o.x);
-                    }
-                }
+            const int fs = r * kGroups + g;                           // slot; fs >= nf: transformed, never read
+            if (fs < nf) {
+                const float* hrow = h + ((int64_t)b * T + f_lo + fs) * ldh;
+                pack_pairs(Z, lt, tile.tw, [&](int k, int m, cf& xk, cf& xm) {
+                    xk = head_bin(hrow, k);
+                    xm = k == 256 ? xk : head_bin(hrow, m);
+                });
             } else {
-                for (int k = lt; k < 512; k += kGT) Z[k] = make_float2(0.f, 0.f);
+                clear_frame(Z, lt);
             }
             __syncthreads();
-            fft<true, kGT, kTw>(Z, reinterpret_cast<cf*>(frames + (r * kGroups + g) * kNfft), 512, lt, tw);
+            fft<true, kGT, kTw>(Z, reinterpret_cast<cf*>(tile.frames + fs * kNfft), kHalf, lt, tile.tw);
         }
-        // ---- window, overlap-add over the utterance's own frames, envelope division (frame order, no atomics)
-        for (int m = m0 + tid; m < m0 + nseg * kHop; m += kHThreads) {
-            const int u = m + kPad;                                   // sample index before the "same" trim
-            const int tmin = u >= kNfft ? (u - kNfft) / kHop + 1 : 0, tmax = min(Tb - 1, u / kHop);
-            float acc = 0.f, env = 0.f;
-            for (int t = tmin; t <= tmax; ++t) {
-                const int n = u - t * kHop;
-                const float wn = win[n];
-                acc = fmaf(frames[(t - f_lo) * kNfft + n], wn, acc);
-                env = fmaf(wn, wn, env);
-            }
-            arow[m] = acc / env;
-        }
+        overlap_add(arow, tile.frames, tile.win, m0, mv, kPad, f_lo, Tb, tid);
     }
-    for (int m = m0 + nseg * kHop + tid; m < m1; m += kHThreads) arow[m] = 0.f;
+    for (int m = mv + tid; m < m1; m += kThreads) arow[m] = 0.f;
 }
 
 }  // namespace
@@ -333,9 +275,9 @@ extern "C" int32_t ispk_istft_head_f32(const float* h, int64_t ldh, const int64_
     ISPK_REQUIRE(B >= 1 && B <= 65535 && T >= 0 && ldh >= 2 * kBins && S >= 0 && (int64_t)S >= (int64_t)T * kHop &&
                  ld_audio >= S, -2, "ispk_istft_head_f32: bad shape B=%d T=%d S=%d ldh=%lld ld_audio=%lld (ldh >= 1026, "
                  "S >= 256 T, ld_audio >= S)", B, T, S, (long long)ldh, (long long)ld_audio);
-    ISPK_RESERVE_LDS(istft_head_kernel, kHeadLds, "ispk_istft_head_f32");
-    const int nblk = S > 0 ? (S + kSegs * kHop - 1) / (kSegs * kHop) : 1;
-    hipLaunchKernelGGL(istft_head_kernel, dim3(nblk, B), dim3(kHThreads), kHeadLds, reinterpret_cast<hipStream_t>(stream), h,
+    ISPK_RESERVE_LDS(istft_head_kernel, kLds, "ispk_istft_head_f32");
+    const int nblk = S > 0 ? (S + kTile - 1) / kTile : 1;
+    hipLaunchKernelGGL(istft_head_kernel, dim3(nblk, B), dim3(kThreads), kLds, reinterpret_cast<hipStream_t>(stream), h,
                        ldh, mel_len, tables, audio, ld_audio, audio_len, T, S);
     return ispk_launch_status();
 }
