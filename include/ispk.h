@@ -1402,6 +1402,54 @@ int32_t ispk_segment_gather_f32(const float* audio, int64_t ld_audio, const int6
                                 int32_t* index, int64_t* bounds, int32_t* row_flags, int32_t* rows, int32_t* rows_wanted,
                                 int32_t B, int32_t S, int32_t K, int32_t R, int32_t S_out, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Screen (csrc/screen.hip, isp_tts_amd/data/screen.py): per item of a padded mono batch the measurements that decide whether a
+ * piece is fit to train on, and a word of flags.  Four launches, no atomics, no host read.  audio fp32 [B][S], unit stride on S,
+ * row stride ld_audio >= S; n = audio_len[b] if 0 <= audio_len[b] <= S, else 0.  x is the item with every non-finite sample
+ * read as 0; all integers, `/` floors.
+ *   nonfinite int32      the NaN and Inf samples among the item's n.
+ *   peak fp32            max |x|, exact.
+ *   dc, power float64    (sum x) / n and (sum x^2) / n, summed in float64; 0 at n = 0.
+ *   Runs.  A run is a maximal stretch of consecutive samples of one class.
+ *     Rail: thr = the fp32 product peak * rail_ratio (rail_mode 0) or rail (rail_mode 1); class + where thr > 0 and x >= thr,
+ *       class - where thr > 0 and x <= -thr.  clip_runs int32 = the runs of at least min_run samples, clip_samples int64 = their
+ *       samples, clip_first int64 = the start of the first of them or -1, clip_longest int64 = the longest run of any length.
+ *     Zero: x == 0.  A dropout is a zero run of at least min_dropout samples that neither starts at sample 0 nor ends at
+ *       n - 1 (digital silence in front and behind is padding).  dropout_runs int32, dropout_samples int64, dropout_longest
+ *       int64 = their number, their samples and the longest of them (0: none).
+ *   ltas float64 [B][513]  the long-term average spectrum: F = max(0, (n - 1024) / 256 + 1) frames, frame f = x[256 f, 256 f +
+ *     1024) times the window, no padding; ltas[k] = (1 / F) sum_f |X_f[k]|^2 with the transform and |X|^2 in fp32 and the sum
+ *     over the frames in float64, ascending f within a tile of 16 frames, then the tiles in order.  Zeros at F = 0.  tables fp32
+ *     [5120]: W_2048^m as (re, im), then the window (the head of ispk_audio_features_f32's tables).
+ *   band_bin int32       with top = max ltas[2 .. 512]: the largest k in 0 .. 512 with ltas[k] >= top * band_factor (float64;
+ *     band_factor = 10^(-band_db / 10) made on the host); -1 when F = 0 or top = 0.
+ *   flags int32          1 clipped: clip_runs > 0;  2 narrow: min_band_bin >= 0 and 0 <= band_bin < min_band_bin;  4 dc: |dc| >
+ *     max_dc;  8 dropout: dropout_runs > 0;  16 nonfinite: nonfinite > 0;  32 quiet: peak <= min_peak;  64 short: F = 0.
+ *   parts               1 levels and runs, 2 spectrum, 3 both.  Without 1 no runs are looked for (the six run outputs read as
+ *     none, clip_first -1); without 2 ltas is zeros and band_bin -1.  The flags follow the outputs.
+ * ispk_screen_tile_samples      samples of one item per workgroup (4096; 16 frames start in them): the tests' tile edges.
+ * ispk_screen_workspace_bytes   *bytes (HOST memory) = what ispk_screen_f64 needs for (B, S): per item and tile of 4,096 samples a
+ *                       spectrum partial (float64 [513]), the tile's statistics and two run summaries (88 B), and 8 B per item.
+ * ispk_screen_f64       grid (ceil(S / 4096), B): stages the tile and the 768 samples its last frame reads (16-byte loads where
+ *                       base and stride allow - the same values either way; nothing at or past n is read), statistics, zero-run
+ *                       summary, the tile's frames through the 1024 / 256 FFT of csrc/stft_tile.h.  Grid (B): the item's
+ *                       statistics, ltas, band_bin, dropouts, thr.  Grid (ceil(S / 4096), B): the rail-run summaries.  Grid (B):
+ *                       the clip outputs and the flags.  All outputs contiguous.
+ * An item's results depend on that item alone - not on B, S, the row stride, the alignment or what lies behind n; repeated
+ * calls and graph replays repeat their bits.
+ * Refused before any launch: B > 65535, S outside [0, 2^24], parts outside 1 .. 3, rail_mode not 0 or 1, rail_ratio outside
+ * (0, 1] (mode 0), a rail that is not positive and finite (mode 1), min_run or min_dropout below 1, band_factor outside (0, 1),
+ * min_band_bin outside -1 .. 513, a negative or NaN max_dc or min_peak, a row stride below S (E_SHAPE); NULLs (E_NULL); a
+ * workspace below ispk_screen_workspace_bytes or off an 8-byte boundary (E_ALIGN).  B = 0 is a no-op. */
+int32_t ispk_screen_tile_samples(void);
+int32_t ispk_screen_workspace_bytes(int32_t B, int32_t S, int64_t* bytes);
+int32_t ispk_screen_f64(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables, int32_t parts,
+                        int32_t rail_mode, float rail, float rail_ratio, int32_t min_run, int32_t min_dropout, double band_factor,
+                        int32_t min_band_bin, double max_dc, double min_peak, int32_t* nonfinite, float* peak, double* dc,
+                        double* power, int32_t* clip_runs, int64_t* clip_samples, int64_t* clip_longest, int64_t* clip_first,
+                        int32_t* dropout_runs, int64_t* dropout_samples, int64_t* dropout_longest, double* ltas, int32_t* band_bin,
+                        int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

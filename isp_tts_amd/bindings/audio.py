@@ -1,6 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip);
 the document join, speech marks, gain envelope and true-peak limiter (csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the
-equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
+equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip).  The vocoders' wrappers are in
+bindings/vocoders.py."""
 from typing import Optional
 
 import torch
@@ -15,7 +16,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "MARKS_MAX_WORDS", "speech_marks", "GAIN_TILE_SAMPLES", "GAIN_MAX_RAMP", "gain_envelope", "LIMIT_TILE_SAMPLES",
            "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit", "EQ_MAX_SECTIONS", "EQ_SEGMENT_SAMPLES", "EQ_CHUNK_SAMPLES",
            "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize", "SEGMENT_MAX_SEGMENTS", "SEGMENT_MAX_ROWS", "SEGMENT_MAX_PAD",
-           "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather"]
+           "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather", "SCREEN_TILE_SAMPLES", "SCREEN_TILE_FRAMES",
+           "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -578,4 +580,58 @@ def segment_gather(audio: Tensor, segments: Tensor, flags: Tensor, count: Tensor
                 o.data_ptr(), o.stride(0) if R > 1 else max(o.stride(0), S_out), r["audio_len"].data_ptr(), r["item"].data_ptr(),
                 r["index"].data_ptr(), r["bounds"].data_ptr(), r["row_flags"].data_ptr(), r["rows"].data_ptr(),
                 r["rows_wanted"].data_ptr(), B, S, K, R, S_out, _rt._stream())
+    return r
+
+
+# ------------------------------------------------------------------------------------------------------ screen
+SCREEN_TILE_SAMPLES = 4096    # ispk_screen_tile_samples(): samples of one item per workgroup
+SCREEN_TILE_FRAMES = 16       # the frames (1024 / 256, no padding) that start in a tile
+SCREEN_BINS = 513
+SCREEN_FLAGS = {"clipped": 1, "narrow": 2, "dc": 4, "dropout": 8, "nonfinite": 16, "quiet": 32, "short": 64}
+# name, dtype, trailing dimension (0: none), in the order of ispk_screen_f64's output pointers
+SCREEN_OUTPUTS = (("nonfinite", torch.int32, 0), ("peak", torch.float32, 0), ("dc", torch.float64, 0), ("power", torch.float64, 0),
+                  ("clip_runs", torch.int32, 0), ("clip_samples", torch.int64, 0), ("clip_longest", torch.int64, 0),
+                  ("clip_first", torch.int64, 0), ("dropout_runs", torch.int32, 0), ("dropout_samples", torch.int64, 0),
+                  ("dropout_longest", torch.int64, 0), ("ltas", torch.float64, SCREEN_BINS), ("band_bin", torch.int32, 0),
+                  ("flags", torch.int32, 0))
+
+
+def screen_workspace_bytes(B: int, S: int) -> int:
+    """ispk_screen_workspace_bytes: per item and tile of 4,096 samples a float64 spectrum partial [513], the tile's statistics and
+    two run summaries (11 more 8-byte words), and one word per item."""
+    return 8 * B * ((SCREEN_BINS + 11) * max(1, -(-S // SCREEN_TILE_SAMPLES)) + 1)
+
+
+def screen(audio: Tensor, audio_len: Tensor, tables: Tensor, rail_mode: int, rail: float, rail_ratio: float, min_run: int,
+           min_dropout: int, band_factor: float, min_band_bin: int, max_dc: float, min_peak: float, out: Optional[dict] = None,
+           parts: int = 3) -> dict:
+    """ispk_screen_f64, four launches, no host read: the measurements and flags (include/ispk.h has the definitions) of fp32 audio
+    [B, S] (unit stride on S, any row stride) with int64 lengths [B] -> a dict of the SCREEN_OUTPUTS, [B] each and ltas
+    float64 [B, 513], and work (uint8 scratch of screen_workspace_bytes).  tables: fp32, W_2048 and the window in front (data.
+    AcousticFeatures' or the denoiser's).  min_band_bin -1: no bandwidth floor.  `out` may hold any of them; the rest is allocated."""
+    B, S = _segment_audio(audio)
+    if S > CONDITION_MAX_SAMPLES:
+        raise ValueError(f"audio: at most {CONDITION_MAX_SAMPLES} samples an item, got {tuple(audio.shape)}")
+    dev = audio.device
+    r = {}
+    for name, dt, last in SCREEN_OUTPUTS:
+        r.update(_segment_tensors(((name, dt, 0),), (B, last) if last else (B,), out, dev))
+    need = screen_workspace_bytes(B, S)
+    work = None if out is None else out.get("work")
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() < FEATURE_TABLE_HEAD:
+        raise ValueError(f"tables: contiguous fp32 of at least {FEATURE_TABLE_HEAD} values, got {tables.dtype} {tuple(tables.shape)}")
+    _rt._dev(audio, audio_len, tables, work, *r.values())
+    # per frame five radix passes of 512 complex points and the split; the audio is read twice (the halo apart)
+    frames = B * max(0, (S - 1024) // FEATURE_HOP + 1)
+    _rt._launch("screen_kernels", frames * (5.0 * 512 * 9 + 513 * 12), 8.0 * B * S + 16.0 * frames / SCREEN_TILE_FRAMES * SCREEN_BINS,
+                _rt.lib().ispk_screen_f64, audio.data_ptr(), audio.stride(0) if B > 1 else max(audio.stride(0), S), audio_len.data_ptr(),
+                tables.data_ptr(), int(parts), int(rail_mode), float(rail), float(rail_ratio), int(min_run), int(min_dropout),
+                float(band_factor), int(min_band_bin), float(max_dc), float(min_peak), *(r[name].data_ptr() for name, _, _ in SCREEN_OUTPUTS),
+                work.data_ptr(), work.numel(), B, S, _rt._stream())
+    r["work"] = work
     return r

@@ -4,5 +4,6 @@ from .condition import AudioConditioner, Limiter, k_weighting, meter_table, to_p
 from .equalize import (Band, Equalizer, bandpass, deemphasis, equalizer_table, highpass, highshelf, lowpass, lowshelf,  # noqa: F401
                        notch, peaking, preemphasis)
 from .resample import AudioFrontEnd, Resampler, compact_taps, resampled_length, sinc_hann_taps  # noqa: F401
+from .screen import Screen  # noqa: F401
 from .segment import Segmenter  # noqa: F401
 from .stats import DatasetStats, DatasetStatsResult, FeatureStats  # noqa: F401
