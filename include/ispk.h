@@ -1450,6 +1450,68 @@ int32_t ispk_screen_f64(const float* audio, int64_t ld_audio, const int64_t* aud
                         int32_t* dropout_runs, int64_t* dropout_samples, int64_t* dropout_longest, double* ltas, int32_t* band_bin,
                         int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * NoiseReducer (csrc/noise.hip, isp_tts_amd/data/noise.py): stationary noise reduction.  The noise spectrum of an item is
+ * learnt from its own pauses (the profile), then every frame is attenuated with a Wiener gain smoothed over time and frequency
+ * (the reduce).  audio fp32 [B][S], unit stride on S, row stride ld_audio >= S; n = audio_len[b] if 0 <= audio_len[b] <= S,
+ * else 0.  All integers, `/` floors.
+ *   STFT.  ispk_denoise_f32's: N = 1024, hop 256, K = 513 bins, w the periodic Hann window made in float64 and rounded once,
+ *     xp[p] = x[r(p - 512)] (reflect padding), X_f[k] = sum_j xp[256 f + j] w[j] exp(-2 pi i j k / 1024), f < F = 1 + n / 256.
+ *     Defined for n >= 513; a shorter item has frames = 0, the flag 2 "short", and is copied bit for bit by the reduce.
+ *   Noise frames.  The trim frames of ispk_audio_measure_f64 / ispk_segment_plan: T = ceil(n / 256), the float64 hop sums h_t in
+ *     that fixed order, p_t = (((h_t + h_{t+1}) + h_{t+2}) + h_{t+3}) / 1024 with hops at or past T left out, frame t active
+ *     when p_t > thr, thr = (max_t p_t) factor (ref_mode 0) or ref factor (ref_mode 1), factor = 10^(-top_db / 10) made on the
+ *     host.  STFT frame f and trim frame t = f - 2 cover the same samples [256 t, 256 t + 1024).  Frame f is a noise frame when
+ *     2 <= f <= n / 256 - 2 (no reflection; the frame lies wholly inside the item) and every trim frame u with |u - t| <= guard
+ *     and 0 <= u < T is inactive.
+ *   Profile.  noise[b][k] = the float64 mean over the item's noise frames of |X_f[k]|^2, the transform and |X|^2 in fp32 and
+ *     the sum in float64: ascending f within a tile of the 16 frames [16 w, 16 w + 16), then the tiles in order.  noise_frames
+ *     [b] = their number, frames[b] = F (0 when short).  flags[b] = (noise_frames < min_noise_frames ? 1 : 0) | (n < 513 ? 2 :
+ *     0): 1 "no_profile" - the row is zeros.
+ *   Raw gain.  g_f[k] = max(1 - over noise[k] / |X_f[k]|^2, g_min) where |X_f[k]|^2 > 0, else g_min; g_min = 10^(-reduce_db /
+ *     20) in (0, 1] made on the host.  In fp32 with nb[k] = the fp32 rounding of the float64 product over noise[k], IEEE
+ *     division; a quotient that is infinite or NaN gives g_min.
+ *   Smoothed gain.  Triangular weights w_t[d] = Tt + 1 - |d|, |d| <= Tt, and w_k[e] = Fk + 1 - |e|, |e| <= Fk:
+ *     h_f[k] = (sum_e w_k[e] g_f[k+e]) / (sum_e w_k[e]) over the bins 0 <= k + e <= 512 that exist, then G_f[k] = (sum_d w_t[d]
+ *     h_{f+d}[k]) / (sum_d w_t[d]) over the frames 0 <= f + d < F that exist; e and d ascending, with fma.  The cells that exist
+ *     form a rectangle, so this is sum w_t w_k g / sum w_t w_k over them.
+ *   Output.  Y_f[k] = X_f[k] G_f[k], y_f = irfft_1024(Y_f), out[s] = (sum_f w[j] y_f[j]) / (sum_f w[j]^2), j = s + 512 - 256 f,
+ *     exactly as ispk_denoise_f32; 0 for n <= s < S.
+ * ispk_noise_tile_samples     output samples of one item per workgroup of the reduce (4096): the tests' tile edges.
+ * ispk_noise_workspace_bytes  *bytes (HOST memory) = what ispk_noise_profile_f64 needs for (B, S): per item the hop sums
+ *                       (float64 [NH], NH = max(1, ceil(S / 256))), two int32 [NH + 1] (the active frames before t; the noise
+ *                       frame mask), a float64 [513] partial per tile of 16 frames (S / 4096 + 1 of them) and one word.
+ * ispk_noise_profile_f64  four launches, no atomics.  Grid (ceil(S / 8192), B): the hop sums.  Grid (B): frame powers, thr, the
+ *                       mask, noise_frames, frames, flags.  Grid (S / 4096 + 1, B): each workgroup transforms the noise frames
+ *                       among its 16 (the 1024 / 256 FFT of csrc/stft_tile.h) and writes its float64 partial.  Grid (B): noise.
+ *                       noise float64 [B][513]; noise_frames, frames, flags int32 [B]; all contiguous.  tables fp32 [5120]:
+ *                       ispk_denoise_f32's.  16-byte loads where base and stride allow - the same values either way; nothing
+ *                       at or past n is read.
+ * ispk_noise_reduce_f32   one launch: the tile of ispk_denoise_f32 with the smoothed gain between analysis and synthesis; the
+ *                       raw gains of the Tt frames on either side of a tile's frames come from extra forward transforms,
+ *                       nothing lies in HBM in between.  noise float64 [P][513]; item b takes row index[b] (int32 [B]; NULL: row
+ *                       b).  flags int32 [B] (NULL: none): the profile's.  An item is copied bit for bit (zeros from n on) when
+ *                       n < 513, when its flag has bit 1 or 2 set, or when its row lies outside [0, P).  audio_len may be NULL
+ *                       (every item has S samples).  out fp32 [B][S] at ld_out >= S may not be audio.  Scalar loads and
+ *                       stores: no alignment requirement.
+ * An item's results depend on that item (and its profile row) alone - not on B, S, the row strides, the alignment or what lies
+ * behind n; every sum runs in a fixed order; repeated calls and graph replays repeat their bits.
+ * Refused before any launch.  Profile: B > 65535, S outside [0, 2^24], ref_mode not 0 or 1, a negative or NaN factor or ref,
+ * guard outside 0 .. 65536, min_noise_frames < 1, a row stride below S (E_SHAPE); NULLs (E_NULL); a workspace below
+ * ispk_noise_workspace_bytes or off an 8-byte boundary (E_ALIGN).  Reduce: NULL audio, tables, noise or out (E_NULL); B > 65535,
+ * S > 2^31 - 8193, P < 1, a row stride below S, out == audio, over negative or not finite, g_min outside (0, 1], smooth_frames
+ * outside 0 .. 2, smooth_bins outside 0 .. 8 (E_SHAPE).  B = 0 or S = 0 is a no-op for both. */
+int32_t ispk_noise_tile_samples(void);
+int32_t ispk_noise_workspace_bytes(int32_t B, int32_t S, int64_t* bytes);
+int32_t ispk_noise_profile_f64(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables, double factor,
+                               int32_t ref_mode, double ref, int32_t guard, int32_t min_noise_frames, double* noise,
+                               int32_t* noise_frames, int32_t* frames, int32_t* flags, void* workspace, int64_t workspace_bytes,
+                               int32_t B, int32_t S, ispk_stream_t stream);
+int32_t ispk_noise_reduce_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables,
+                              const double* noise, int32_t P, const int32_t* index, const int32_t* flags, double over,
+                              double g_min, int32_t smooth_frames, int32_t smooth_bins, float* out, int64_t ld_out, int32_t B,
+                              int32_t S, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

@@ -17,7 +17,9 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit", "EQ_MAX_SECTIONS", "EQ_SEGMENT_SAMPLES", "EQ_CHUNK_SAMPLES",
            "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize", "SEGMENT_MAX_SEGMENTS", "SEGMENT_MAX_ROWS", "SEGMENT_MAX_PAD",
            "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather", "SCREEN_TILE_SAMPLES", "SCREEN_TILE_FRAMES",
-           "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen"]
+           "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen", "NOISE_TILE_SAMPLES", "NOISE_BINS",
+           "NOISE_MIN_SAMPLES", "NOISE_MAX_GUARD", "NOISE_MAX_SMOOTH_FRAMES", "NOISE_MAX_SMOOTH_BINS", "NOISE_FLAGS", "NOISE_OUTPUTS",
+           "noise_workspace_bytes", "noise_profile", "noise_reduce"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -635,3 +637,95 @@ def screen(audio: Tensor, audio_len: Tensor, tables: Tensor, rail_mode: int, rai
                 work.data_ptr(), work.numel(), B, S, _rt._stream())
     r["work"] = work
     return r
+
+
+# ------------------------------------------------------------------------------------------------------ noise reducer
+NOISE_TILE_SAMPLES = 4096     # ispk_noise_tile_samples(): output samples of one item per workgroup of the reduce
+NOISE_BINS = 513
+NOISE_MIN_SAMPLES = 513       # below this the reflect padding is undefined: flagged short, copied
+NOISE_MAX_GUARD = 65536       # frames
+NOISE_MAX_SMOOTH_FRAMES, NOISE_MAX_SMOOTH_BINS = 2, 8
+NOISE_FLAGS = {"no_profile": 1, "short": 2}
+# name, dtype, trailing dimension (0: none), in the order of ispk_noise_profile_f64's output pointers
+NOISE_OUTPUTS = (("noise", torch.float64, NOISE_BINS), ("noise_frames", torch.int32, 0), ("frames", torch.int32, 0),
+                 ("flags", torch.int32, 0))
+
+
+def noise_workspace_bytes(B: int, S: int) -> int:
+    """ispk_noise_workspace_bytes: per item the hop sums (float64 [NH]), two int32 [NH + 1], a float64 [513] partial per tile of 16
+    frames (S // 4096 + 1 of them) and one word."""
+    NH = max(1, -(-S // 256))
+    return 8 * B * (NH + 2 * ((NH + 2) // 2) + NOISE_BINS * (S // 4096 + 1) + 1)
+
+
+def noise_profile(audio: Tensor, audio_len: Tensor, tables: Tensor, factor: float, ref_mode: int, ref: float, guard: int,
+                  min_noise_frames: int, out: Optional[dict] = None) -> dict:
+    """ispk_noise_profile_f64, four launches, no host read: the noise spectrum of every item of fp32 audio [B, S] (unit stride on
+    S, any row stride) with int64 lengths [B], from its own pauses (include/ispk.h has the definitions) -> a dict of noise float64
+    [B, 513]; noise_frames, frames, flags int32 [B]; work (uint8 scratch of noise_workspace_bytes).  tables: fp32, W_2048 and the
+    window in front (the denoiser's).  `out` may hold any of them; the rest is allocated."""
+    B, S = _segment_audio(audio)
+    if S > CONDITION_MAX_SAMPLES:
+        raise ValueError(f"audio: at most {CONDITION_MAX_SAMPLES} samples an item, got {tuple(audio.shape)}")
+    dev = audio.device
+    r = {}
+    for name, dt, last in NOISE_OUTPUTS:
+        r.update(_segment_tensors(((name, dt, 0),), (B, last) if last else (B,), out, dev))
+    need = noise_workspace_bytes(B, S)
+    work = None if out is None else out.get("work")
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() < FEATURE_TABLE_HEAD:
+        raise ValueError(f"tables: contiguous fp32 of at least {FEATURE_TABLE_HEAD} values, got {tables.dtype} {tuple(tables.shape)}")
+    _rt._dev(audio, audio_len, tables, work, *r.values())
+    # the audio is read for the hop sums and again by the tiles that hold a noise frame; per such frame one 512-point transform
+    frames = B * (S // FEATURE_HOP + 1)
+    _rt._launch("noise_profile_kernels", frames * (5.0 * 512 * 9 + 513 * 12), 8.0 * B * S + 16.0 * B * (S // 4096 + 1) * NOISE_BINS,
+                _rt.lib().ispk_noise_profile_f64, audio.data_ptr(), audio.stride(0) if B > 1 else max(audio.stride(0), S),
+                audio_len.data_ptr(), tables.data_ptr(), float(factor), int(ref_mode), float(ref), int(guard), int(min_noise_frames),
+                *(r[name].data_ptr() for name, _, _ in NOISE_OUTPUTS), work.data_ptr(), work.numel(), B, S, _rt._stream())
+    r["work"] = work
+    return r
+
+
+def noise_reduce(audio: Tensor, audio_len: Optional[Tensor], tables: Tensor, noise: Tensor, index: Optional[Tensor],
+                 flags: Optional[Tensor], over: float, g_min: float, smooth_frames: int, smooth_bins: int,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """ispk_noise_reduce_f32, one launch, no host read: fp32 audio [B, S] (unit stride on S, any row stride) with int64 lengths
+    [B] (None: all S samples) -> out fp32 [B, S]: STFT (1024 / 256, periodic Hann, reflect-centred), the Wiener gain max(1 - over
+    noise[k] / |X|^2, g_min) smoothed with triangular weights over smooth_frames frames and smooth_bins bins on either side, ISTFT;
+    zeros from audio_len on.  noise float64 [P, 513]; item b takes row index[b] (int32 [B]; None: row b).  Items below 513
+    samples, with bit 1 or 2 in flags (int32 [B], the profile's; None: none) or with a row outside [0, P) are copied.  Out of
+    place only."""
+    _rt._dev(audio, audio_len, tables, noise, index, flags, out)
+    B, S = _segment_audio(audio)
+    if audio_len is not None and (audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous()):
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() < FEATURE_TABLE_HEAD:
+        raise ValueError(f"tables: contiguous fp32 of at least {FEATURE_TABLE_HEAD} values, got {tables.dtype} {tuple(tables.shape)}")
+    if noise.dtype != torch.float64 or noise.ndim != 2 or noise.shape[1] != NOISE_BINS or noise.shape[0] < 1 or not noise.is_contiguous():
+        raise ValueError(f"noise: contiguous float64 [P, {NOISE_BINS}] with P >= 1, got {noise.dtype} {tuple(noise.shape)}")
+    for name, t in (("index", index), ("flags", flags)):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (B,) or not t.is_contiguous()):
+            raise ValueError(f"{name}: contiguous int32 [{B}], got {t.dtype} {tuple(t.shape)}")
+    if not (over >= 0.0 and over < float("inf")) or not 0.0 < g_min <= 1.0:
+        raise ValueError(f"over >= 0 and finite, 0 < g_min <= 1, got {over!r}, {g_min!r}")
+    if int(smooth_frames) != smooth_frames or not 0 <= smooth_frames <= NOISE_MAX_SMOOTH_FRAMES:
+        raise ValueError(f"smooth_frames is an integer in [0, {NOISE_MAX_SMOOTH_FRAMES}], got {smooth_frames!r}")
+    if int(smooth_bins) != smooth_bins or not 0 <= smooth_bins <= NOISE_MAX_SMOOTH_BINS:
+        raise ValueError(f"smooth_bins is an integer in [0, {NOISE_MAX_SMOOTH_BINS}], got {smooth_bins!r}")
+    out = torch.empty((B, S), dtype=torch.float32, device=audio.device) if out is None else out
+    _out_like("out", out, torch.float32, (B, S))
+    if B == 0 or S == 0:
+        return out
+    # per hop: (19 + 2 smooth_frames) / 16 forward and 19 / 16 inverse 512-point transforms, the gains and their smoothing
+    taps = (2 * smooth_frames + 1) * (2 * smooth_bins + 1)
+    _rt._launch("noise_reduce_kernel", B * S / 256.0 * ((38.0 + 2 * smooth_frames) / 16.0 * 5.0 * 512 * 9 + 19.0 / 16.0 * 513 * (40.0 + 2 * taps)),
+                8.0 * B * S, _rt.lib().ispk_noise_reduce_f32, audio.data_ptr(), audio.stride(0) if B > 1 else max(audio.stride(0), S),
+                _rt._ptr(audio_len), tables.data_ptr(), noise.data_ptr(), noise.shape[0], _rt._ptr(index), _rt._ptr(flags), float(over),
+                float(g_min), int(smooth_frames), int(smooth_bins), out.data_ptr(), out.stride(0) if B > 1 else max(out.stride(0), S), B, S,
+                _rt._stream())
+    return out
