@@ -1512,6 +1512,51 @@ int32_t ispk_noise_reduce_f32(const float* audio, int64_t ld_audio, const int64_
                               double g_min, int32_t smooth_frames, int32_t smooth_bins, float* out, int64_t ld_out, int32_t B,
                               int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * TimeStretch (csrc/stretch.hip, isp_tts_amd/data/stretch.py): tempo without pitch, the phase vocoder of torchaudio / librosa.
+ * (data.PitchShift is this followed by ispk_resample_f32.)  audio fp32 [B][S], unit stride on S, row stride ld_audio >= S;
+ * n = audio_len[b] if 0 <= audio_len[b] <= S, else 0; r = rates[b] (float64 [B], device memory) or, with rates NULL, the scalar
+ * `rate`; 0.5 <= r <= 2.  Integers, `/` floors, unless said otherwise.
+ *   Analysis.  ispk_denoise_f32's STFT: N = 1024, hop 256, K = 513 bins, w the periodic Hann window made in float64 and rounded
+ *     once, xp[p] = x[r(p - 512)] (reflect padding), X_i[k] = sum_j xp[256 i + j] w[j] exp(-2 pi i j k / 1024), i < F = 1 + n /
+ *     256, transforms in fp32.  X_F = X_{F+1} = 0.
+ *   Output frames.  t_j = j r (a float64 product, not a running sum); Fo = the smallest j >= 0 with j r >= F; i_j = floor(t_j),
+ *     a_j = t_j - i_j.
+ *   Magnitude.  M_j[k] = (1 - a_j) |X_{i_j}[k]| + a_j |X_{i_j + 1}[k]|.
+ *   Phase.  P_0[k] = arg X_0[k], P_{j+1}[k] = P_j[k] + w_k + wrap(arg X_{i_j + 1}[k] - arg X_{i_j}[k] - w_k), w_k = pi k / 2 the
+ *     expected advance per hop, wrap(d) = d - 2 pi round(d / (2 pi)), arg 0 = 0.  Only exp(i P) is used and w_k + wrap(d - w_k)
+ *     = d modulo 2 pi, so the kernels multiply unit phasors instead, in float64 from the fp32 spectra: e_0 = u(X_0), e_{j+1} =
+ *     e_j u(X_{i_j + 1}) conj(u(X_{i_j})), u(z) = z / |z|, u(0) = 1, ascending j.  Nothing is accumulated in fp32.
+ *   Synthesis.  Y_j[k] = M_j[k] exp(i P_j[k]), y_j = irfft_1024(Y_j), out[s] = (sum_j w[q] y_j[q]) / (sum_j w[q]^2), q = s + 512
+ *     - 256 j, over the frames j < Fo in ascending order, exactly as ispk_denoise_f32; 0 <= s < out_len, zeros behind.
+ *   Length.  wanted = round-half-even(n / r), an int64 from the float64 quotient; out_len = min(wanted, out_samples).  Every
+ *     s < wanted lies under at least one output frame, since 256 F > n.
+ *   flags[b], int32: 1 "short" (n < 513, no reflection), 4 "bad_rate" (a device rate that is NaN or outside [0.5, 2]) - such an
+ *     item is copied bit for bit with wanted = n and out_len = min(n, out_samples); 2 "truncated" (wanted > out_samples).
+ * ispk_stretch_tile_samples     output samples of one item per workgroup of the synthesis (4096): the tests' tile edges.
+ * ispk_stretch_workspace_bytes  *bytes (HOST memory) = what ispk_stretch_f32 needs for (B, S, out_samples): per item and output
+ *                       tile (max(1, ceil(out_samples / 4096)) of them) one phasor row, float64 re [513] then im [513].
+ * ispk_stretch_f32      three launches, no atomics, nothing per (frame, bin) in HBM.  Grid (tiles - 1, B): chunk w = the output
+ *                       frames [max(0, 16 w - 1), 16 w + 15), from the first that touches output tile w to the first that touches
+ *                       tile w + 1; the workgroup transforms the analysis frames they read (forward only, four at a time through a
+ *                       ring of 8 spectra) and writes the product of their steps per bin (chunk 0: times u(X_0)).  Grid (B): the
+ *                       exclusive product over the chunks in order, in place; out_len, wanted (int64 [B]) and flags (int32 [B]).
+ *                       Grid (tiles, B): the tile of ispk_denoise_f32 - the output frames that touch it, started from the chunk's
+ *                       prefix, the analysis frames through the same ring, Y_j / 1024 into the frame's slot, the inverses, the
+ *                       overlap-add.  tables fp32 [5120]: ispk_denoise_f32's.  out fp32 [B][out_samples] at ld_out >=
+ *                       out_samples may not be audio.  Scalar loads and stores: no alignment requirement on audio or out.
+ * An item's results depend on its samples, n and r alone - not on B, S, the row strides, out_samples (where it is at least
+ * wanted), its neighbours or what lies behind n; every product and sum runs in a fixed order; repeated calls and graph replays
+ * repeat their bits.
+ * Refused before any launch: B > 65535, S or out_samples outside [1, 2^24] (workspace_bytes: [0, 2^24]), with rates NULL a scalar
+ * rate that is NaN or outside [0.5, 2], a row stride below the row, out == audio (E_SHAPE); NULLs other than rates (E_NULL); a
+ * workspace below ispk_stretch_workspace_bytes or off an 8-byte boundary (E_ALIGN).  B = 0 is a no-op. */
+int32_t ispk_stretch_tile_samples(void);
+int32_t ispk_stretch_workspace_bytes(int32_t B, int32_t S, int32_t out_samples, int64_t* bytes);
+int32_t ispk_stretch_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables, double rate,
+                         const double* rates, float* out, int64_t ld_out, int32_t out_samples, int64_t* out_len, int64_t* wanted,
+                         int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

@@ -1,7 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip);
 the document join, speech marks, gain envelope and true-peak limiter (csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the
-equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip).  The vocoders' wrappers are in
-bindings/vocoders.py."""
+equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip); the noise reducer (csrc/noise.hip);
+the time stretch (csrc/stretch.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
 from typing import Optional
 
 import torch
@@ -19,7 +19,8 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather", "SCREEN_TILE_SAMPLES", "SCREEN_TILE_FRAMES",
            "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen", "NOISE_TILE_SAMPLES", "NOISE_BINS",
            "NOISE_MIN_SAMPLES", "NOISE_MAX_GUARD", "NOISE_MAX_SMOOTH_FRAMES", "NOISE_MAX_SMOOTH_BINS", "NOISE_FLAGS", "NOISE_OUTPUTS",
-           "noise_workspace_bytes", "noise_profile", "noise_reduce"]
+           "noise_workspace_bytes", "noise_profile", "noise_reduce", "STRETCH_TILE_SAMPLES", "STRETCH_BINS", "STRETCH_MIN_SAMPLES",
+           "STRETCH_RATES", "STRETCH_FLAGS", "stretch_workspace_bytes", "stretch"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -728,4 +729,64 @@ def noise_reduce(audio: Tensor, audio_len: Optional[Tensor], tables: Tensor, noi
                 _rt._ptr(audio_len), tables.data_ptr(), noise.data_ptr(), noise.shape[0], _rt._ptr(index), _rt._ptr(flags), float(over),
                 float(g_min), int(smooth_frames), int(smooth_bins), out.data_ptr(), out.stride(0) if B > 1 else max(out.stride(0), S), B, S,
                 _rt._stream())
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------ time stretch
+STRETCH_TILE_SAMPLES = 4096   # ispk_stretch_tile_samples(): output samples of one item per workgroup of the synthesis
+STRETCH_BINS = 513
+STRETCH_MIN_SAMPLES = 513     # below this the reflect padding is undefined: flagged short, copied
+STRETCH_RATES = (0.5, 2.0)    # the ring of analysis spectra holds two rounds of four frames
+STRETCH_FLAGS = {"short": 1, "truncated": 2, "bad_rate": 4}
+
+
+def stretch_workspace_bytes(B: int, S: int, out_samples: int) -> int:
+    """ispk_stretch_workspace_bytes: per item and output tile of 4,096 samples one float64 phasor row, re [513] then im [513]."""
+    return 8 * B * max(1, -(-out_samples // STRETCH_TILE_SAMPLES)) * 2 * STRETCH_BINS
+
+
+def stretch(audio: Tensor, audio_len: Tensor, tables: Tensor, rate, out: Tensor, out_len: Tensor, wanted: Tensor, flags: Tensor,
+            work: Optional[Tensor] = None) -> Tensor:
+    """ispk_stretch_f32, three launches, no host read: the phase vocoder (include/ispk.h has the definition) of fp32 audio [B, S]
+    (unit stride on S, any row stride) with int64 lengths [B] at `rate` - a float in [0.5, 2], or a float64 [B] device tensor with
+    one rate per item - into out fp32 [B, out_samples] (any row stride, not audio itself): round(n / rate) samples of each item,
+    cut at out_samples, zeros behind.  out_len, wanted int64 [B]; flags int32 [B], bits STRETCH_FLAGS.  tables: fp32, W_2048 and
+    the window in front (the denoiser's); work: uint8 scratch of stretch_workspace_bytes (None: allocated)."""
+    B, S = _mono_batch(audio, audio_len)
+    if out.ndim != 2:
+        raise ValueError(f"out: fp32 [{B}, out_samples], got {tuple(out.shape)}")
+    out_samples = out.shape[1]
+    _out_like("out", out, torch.float32, (B, out_samples))
+    if not 1 <= S or not 1 <= out_samples <= CONDITION_MAX_SAMPLES:
+        raise ValueError(f"audio and out: between 1 and {CONDITION_MAX_SAMPLES} samples a row, got {S} and {out_samples}")
+    if B > 1 and (audio.stride(0) < S or out.stride(0) < out_samples):
+        raise ValueError(f"audio / out: rows overlap (row strides {audio.stride(0)}, {out.stride(0)} < {S}, {out_samples})")
+    _out_like("out_len", out_len, torch.int64, (B,))
+    _out_like("wanted", wanted, torch.int64, (B,))
+    _out_like("flags", flags, torch.int32, (B,))
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() < FEATURE_TABLE_HEAD:
+        raise ValueError(f"tables: contiguous fp32 of at least {FEATURE_TABLE_HEAD} values, got {tables.dtype} {tuple(tables.shape)}")
+    rates = rate if isinstance(rate, Tensor) else None
+    if rates is not None:
+        _out_like("rate", rates, torch.float64, (B,))
+        scalar = 1.0
+    else:
+        scalar = float(rate)
+        if not STRETCH_RATES[0] <= scalar <= STRETCH_RATES[1]:
+            raise ValueError(f"rate in [{STRETCH_RATES[0]}, {STRETCH_RATES[1]}], got {rate!r}")
+    need = stretch_workspace_bytes(B, S, out_samples)
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=audio.device) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    _rt._dev(audio, audio_len, tables, rates, out, out_len, wanted, flags, work)
+    if B == 0:
+        return out
+    # per output hop: up to 2 (19 / 16) max(rate, 1) forward and 19 / 16 inverse 512-point transforms; per (output frame, bin)
+    # about 40 float64 operations in each of the two passes
+    hops = B * (out_samples / 256.0 + 1)
+    _rt._launch("stretch_kernels", hops * ((2.0 * 2.0 + 1.0) * 19.0 / 16.0 * 5.0 * 512 * 9 + 2.0 * STRETCH_BINS * 40.0),
+                4.0 * B * (2.0 * S + out_samples) + 32.0 * B * (out_samples / 4096.0 + 1) * STRETCH_BINS, _rt.lib().ispk_stretch_f32,
+                audio.data_ptr(), audio.stride(0) if B > 1 else max(audio.stride(0), S), audio_len.data_ptr(), tables.data_ptr(), scalar,
+                _rt._ptr(rates), out.data_ptr(), out.stride(0) if B > 1 else max(out.stride(0), out_samples), out_samples,
+                out_len.data_ptr(), wanted.data_ptr(), flags.data_ptr(), work.data_ptr(), work.numel(), B, S, _rt._stream())
     return out

@@ -7,4 +7,5 @@ from .noise import NoiseReducer  # noqa: F401
 from .resample import AudioFrontEnd, Resampler, compact_taps, resampled_length, sinc_hann_taps  # noqa: F401
 from .screen import Screen  # noqa: F401
 from .segment import Segmenter  # noqa: F401
+from .stretch import PitchShift, TimeStretch, nearest_ratio  # noqa: F401
 from .stats import DatasetStats, DatasetStatsResult, FeatureStats  # noqa: F401
