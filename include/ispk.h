@@ -169,8 +169,10 @@ int32_t ispk_ffn_bf16(const uint16_t* x, int64_t ldx, const uint16_t* W1, int64_
  * x fp32 [rows][dim] is both the LayerNorm input and the residual; a wave owns whole rows and computes their statistics
  * itself (two-pass fp32, fixed summation order).  The reference also multiplies LN(x) by the row mask (:102); with the
  * same mask applied to the output (flags: ISPK_EP_MASK_OUT / ISPK_EP_MASK_ACC) that product cannot reach any kept value
- * and is skipped.  W2 packed (ispk_ffn_pack_w2_bf16), no first-Linear bias.  row_stats (optional): float [rows][2] =
- * (mean, rstd with stats_eps) of the OUTPUT rows, for ispk_gemm_bf16_lnin to apply the next LayerNorm while it stages them. */
+ * and is skipped.  ISPK_EP_MASK_ACC masks the block's product (bias2 included) before x is added, out = x + mask * (...), so a
+ * masked row comes out as x; both flags may be set.  W2 packed (ispk_ffn_pack_w2_bf16), no first-Linear bias.
+ * row_stats (optional): float [rows][2] = (mean, rstd with stats_eps) of the OUTPUT rows, for ispk_gemm_bf16_lnin to apply
+ * the next LayerNorm while it stages them. */
 int32_t ispk_ffn_bf16_prenorm(const float* x, int64_t ldx, const float* norm_gamma, const float* norm_beta, float norm_eps,
                               const uint16_t* W1, int64_t ldw1, const uint16_t* W2_packed, const float* bias2,
                               const uint8_t* mask, float* out, int64_t ldo, int32_t rows, int32_t dim, int32_t inner,
@@ -233,7 +235,8 @@ int32_t ispk_attn_out_ffn_bf16(const float* x, int64_t ldx, const uint16_t* attn
 /* ispk_attn_out_ffn_bf16 for the LAST layer of a stack: the stack's final LayerNorm (transformer.py:205-206, row-masked if ln_mask)
  * of the finished rows as a second output from the same registers, ln_out bf16 (ln_bf16) or fp32 [rows][dim] at ld_ln - the separate
  * LayerNorm launch and its re-read of the rows disappear; `out` may be NULL when only the normalised rows are consumed (the decoder:
- * its output goes through `norm` into to_mel, model.py:168-171) and the fp32 rows are then not stored at all. */
+ * its output goes through `norm` into to_mel, model.py:168-171) and the fp32 rows are then not stored at all.  ln_mask needs the mask
+ * pointer only: it masks ln_out whatever the mask flags say about x1 and out. */
 int32_t ispk_attn_out_ffn_norm_bf16(const float* x, int64_t ldx, const uint16_t* attn_out, int64_t ld_attn,
                                     const uint16_t* Wo_chunks, const float* norm_gamma, const float* norm_beta, float norm_eps,
                                     const uint16_t* W1, const uint16_t* W2_chunks, const uint8_t* mask, float* out, int64_t ldo,

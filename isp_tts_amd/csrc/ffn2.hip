@@ -783,7 +783,9 @@ __global__ __launch_bounds__(512, 2) void ffn2_bf16_kernel(Ffn2Params p) {
             const int r = row0 + pass * 64 + rl;
             const bool live = r < p.rows;
             const int rc = live ? r : p.rows - 1;
-            const float mk = (p.mask && (mask_acc || mask_out)) ? (p.mask[rc] ? 1.0f : 0.0f) : 1.0f;   // (projection mode: MASK_ACC belongs to the prologue)
+            // (projection mode: MASK_ACC belongs to the prologue; ln_mask asks for the row mask on its own, with or without a mask flag)
+            const bool want_mk = mask_acc || mask_out || (MODE == kProjMode && p.ln_mask);
+            const float mk = (p.mask && want_mk) ? (p.mask[rc] ? 1.0f : 0.0f) : 1.0f;
             f32x4 y[3];
             float s = 0.f;
 #pragma unroll
