@@ -1560,6 +1560,73 @@ int32_t ispk_stretch_f32(const float* audio, int64_t ld_audio, const int64_t* au
                          const double* rates, float* out, int64_t ld_out, int32_t out_samples, int64_t* out_len, int64_t* wanted,
                          int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, ispk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * PitchTracker (csrc/pyin.hip, isp_tts_amd/data/pitch.py): probabilistic YIN (Mauch & Dixon 2014) as librosa.pyin states it, with
+ * center = True framing on the hop of ispk_audio_features_f32, then a Viterbi decode.  audio fp32 [B][S], unit stride on S, row
+ * stride ld_audio >= S; n = audio_len[b] if 256 <= audio_len[b] <= S, else no frames; Tb = (n - 256) / 256 + 1 frames (the
+ * extractor's mel_len).  Integers, `/` floors, tiny = DBL_MIN.
+ *   Frame t: x[j] = audio[256 t + 128 - 512 + j], j < 2048, 0 outside [0, n): its YIN window x[0, 1024) is centred where mel frame
+ *     t is centred.
+ *   d(tau) = sum_{j<1024} (x[j] - x[j + tau])^2 = (S[1023] + S[tau + 1023] - S[tau - 1]) - 2 c(tau), S the inclusive prefix sums of
+ *     x^2 (float64), c(tau) = sum_{j<1024} x[j] x[j + tau] by 2,048-point transforms in fp32 (nothing wraps: j + tau < 2048).
+ *   y[i] = d(tau) / (sum_{k=1..tau} d(k) / tau + tiny), tau = min_period + i, i < n_lag = max_period - min_period + 1 (float64).
+ *   Troughs: i = 0 if y[0] < y[1]; 0 < i < n_lag - 1 if y[i] < y[i-1] and y[i] <= y[i+1]; never the last lag.
+ *   Shift: 0 at i = 0, else -b / a with a = y[i+1] + y[i-1] - 2 y[i], b = (y[i+1] - y[i-1]) / 2 where |b| < |a|, else 0.
+ *   Probability of trough j (in lag order): sum over the thresholds s (ascending) with y_j < thr[s] of prior[s] (1 - e^-2) e^(-2 k)
+ *     / (1 - e^(-2 N)), N the troughs below thr[s], k the number of them in front of j; the lowest trough (the first of equal
+ *     heights) also gets 0.01 times the prior of the thresholds it does not lie below.
+ *   Bin of trough j: clip(rint(12 bps log2(sample_rate / (tau + shift) / f_min)), 0, NB - 1), rint half to even; the troughs of one
+ *     bin are taken in lag order and the last one's probability stands (also when it is 0).
+ *   `prior` float64 [ISPK_PYIN_TABLE_DOUBLES], device memory: thr [100], prior [100], its exclusive running sum [101], (1 - e^-2)
+ *     e^(-2 k) for k < 512, 1 / (1 - e^(-2 N)) for N <= 512 (entry 0 unused) - data.pitch.observation_table().
+ *   `tables` fp32, at least 4,096 values: W_2048^m as (re, im), made in float64 and rounded once (ispk_audio_features_f32's).
+ * ispk_pyin_frames_per_block  frames of one item per workgroup of the observation (8): the tests' tile edge.
+ * ispk_pyin_observe_f32   one launch, grid (ceil(M / 8), B).  obs fp32 [B][M][NB], contiguous: row t of item b holds the voiced
+ *                       probabilities of frame t, zeros for Tb <= t < M; frames int64 [B] (may be NULL) receives Tb.  M >= the
+ *                       frames of S.  Nothing at or past n is read.
+ * Decode: Viterbi over 2 NB states, voiced bins then unvoiced bins, for item b over its n = obs_len[b] frames (int64 [B]; NULL: M;
+ *   a value outside [0, M] counts as 0).
+ *   Observations.  obs_is_log = 0: obs fp32 [B][M][NB] as above; vp = clip(sum of the row, 0, 1) in float64; logobs[j] = log(max(p_j,
+ *     0) + tiny) for j < NB and log((1 - vp) / NB + tiny) for every j >= NB.  obs_is_log != 0: obs float64 [B][M][2 NB] holds logobs
+ *     itself (voiced_prob is then written as 0).
+ *   `trans` float64 [width + NB + 3], device memory: logtri [width] (the log of the triangular window, centre at (width - 1) / 2),
+ *     lognorm [NB] (the log of each source row's window sum inside [0, NB)), log stay, log switch, log init - data.pitch.
+ *     transition_table().  h = (width - 1) / 2.
+ *   Recursion, float64, plain additions (no fused multiply-add occurs): delta_0[j] = log init + logobs_0[j]; delta'[i] = delta[i] -
+ *     lognorm[bin(i)]; per target bin c and per source block (voiced, unvoiced) m = max over the source bins i = c - h .. c + h
+ *     inside [0, NB), ascending, first maximum, of delta'[i] + logtri[h + c - i]; the voiced target takes max(m_voiced + stay,
+ *     m_unvoiced + switch), the unvoiced one max(m_voiced + switch, m_unvoiced + stay), the voiced source on a tie; new[j] = that +
+ *     logobs[j].  This is max_i(delta'[i] + logtri[..] + (stay | switch)) over the predecessors in ascending state order with the
+ *     first maximum winning, the constant added after the block maximum.  The path ends in the lowest-index maximum of the last
+ *     frame; log_prob is that maximum.
+ *   Outputs, all [B][M] contiguous: state int32 (-1 past n); f0 fp32 = (float)(f_min 2^(bin / (12 bps))) where voiced, 0 where
+ *     unvoiced or past n; voiced int32 (1 / 0); voiced_prob fp32 = vp; pitch fp32 (may be NULL) = (f0 - pitch_mean) / pitch_std in
+ *     fp32 for t < n, 0 past n; frames int64 [B] (may be NULL) = n; log_prob float64 [B] (0 for n = 0).
+ * ispk_pyin_workspace_bytes  *bytes (HOST memory) = what ispk_pyin_decode_f64 needs: two float64 per (item, frame) and one
+ *                       backpointer byte per (item, frame, state), rounded up to 8.
+ * ispk_pyin_decode_f64  one launch, grid (B): one workgroup owns an item, its scores stay in LDS, one lane walks back.
+ * Both entries: no atomics, no host read, every sum and maximum in a fixed order - an item's results depend on that item alone
+ * (not on B, S, M or its neighbours) and repeated calls and graph replays repeat their bits.
+ * Refused before any launch.  Observe: B > 65535, S outside [0, 2^30], ld_audio < S, M below the frames of S, NB outside [1, 1024],
+ * M NB >= 2^31, periods outside 1 <= min_period, min_period + 2 <= max_period <= 1022, sample_rate or f_min not positive,
+ * bins_per_semitone outside [1, 100] (E_SHAPE); NULLs other than frames (E_NULL).  Decode: B > 65535, M > 2^22, NB outside [1,
+ * 1024], width even or outside [1, 127], f_min not positive, bins_per_semitone outside [1, 100], pitch given with pitch_std 0
+ * (E_SHAPE); NULLs other than obs_len, pitch and frames (E_NULL); a workspace below ispk_pyin_workspace_bytes or off an 8-byte
+ * boundary (E_ALIGN).  B = 0 is a no-op for both, M = 0 for the observation. */
+#define ISPK_PYIN_THRESHOLDS 100
+#define ISPK_PYIN_MAX_BINS 1024
+#define ISPK_PYIN_TABLE_DOUBLES 1326
+int32_t ispk_pyin_frames_per_block(void);
+int32_t ispk_pyin_workspace_bytes(int32_t B, int32_t M, int32_t NB, int64_t* bytes);
+int32_t ispk_pyin_observe_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const float* tables,
+                              const double* prior, float* obs, int64_t* frames, int32_t B, int32_t S, int32_t M, int32_t NB,
+                              int32_t min_period, int32_t max_period, double sample_rate, double f_min,
+                              int32_t bins_per_semitone, ispk_stream_t stream);
+int32_t ispk_pyin_decode_f64(const void* obs, int32_t obs_is_log, const int64_t* obs_len, const double* trans, int32_t width,
+                             double f_min, int32_t bins_per_semitone, float pitch_mean, float pitch_std, int32_t* state,
+                             float* f0, int32_t* voiced, float* voiced_prob, float* pitch, int64_t* frames, double* log_prob,
+                             void* workspace, int64_t workspace_bytes, int32_t B, int32_t M, int32_t NB, ispk_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Griffin-Lim mel inversion (csrc/griffinlim.hip; isp_tts_amd/griffinlim.py): waveforms from mel without a vocoder checkpoint,
  * in the framing of ispk_audio_features_f32: N = 1024, hop 256, K = 513 bins, w the periodic Hann window, 384 zeros on both

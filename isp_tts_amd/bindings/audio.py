@@ -1,7 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip);
 the document join, speech marks, gain envelope and true-peak limiter (csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the
 equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip); the noise reducer (csrc/noise.hip);
-the time stretch (csrc/stretch.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
+the time stretch (csrc/stretch.hip); the pitch tracker (csrc/pyin.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
 from typing import Optional
 
 import torch
@@ -20,7 +20,9 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen", "NOISE_TILE_SAMPLES", "NOISE_BINS",
            "NOISE_MIN_SAMPLES", "NOISE_MAX_GUARD", "NOISE_MAX_SMOOTH_FRAMES", "NOISE_MAX_SMOOTH_BINS", "NOISE_FLAGS", "NOISE_OUTPUTS",
            "noise_workspace_bytes", "noise_profile", "noise_reduce", "STRETCH_TILE_SAMPLES", "STRETCH_BINS", "STRETCH_MIN_SAMPLES",
-           "STRETCH_RATES", "STRETCH_FLAGS", "stretch_workspace_bytes", "stretch"]
+           "STRETCH_RATES", "STRETCH_FLAGS", "stretch_workspace_bytes", "stretch", "PYIN_THRESHOLDS", "PYIN_MAX_BINS", "PYIN_MAX_TROUGHS",
+           "PYIN_TABLE_DOUBLES", "PYIN_MAX_PERIOD", "PYIN_MAX_WIDTH", "PYIN_FRAMES_PER_BLOCK", "pyin_workspace_bytes", "pyin_observe",
+           "pyin_decode"]
 
 
 FEATURE_HOP = 256          # STFT / YIN hop of ispk_audio_features_f32 (n_fft = win_length = 1024, pad 384 on each side)
@@ -790,3 +792,108 @@ def stretch(audio: Tensor, audio_len: Tensor, tables: Tensor, rate, out: Tensor,
                 _rt._ptr(rates), out.data_ptr(), out.stride(0) if B > 1 else max(out.stride(0), out_samples), out_samples,
                 out_len.data_ptr(), wanted.data_ptr(), flags.data_ptr(), work.data_ptr(), work.numel(), B, S, _rt._stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------------ pitch tracker
+PYIN_THRESHOLDS = 100         # ISPK_PYIN_THRESHOLDS
+PYIN_MAX_BINS = 1024          # ISPK_PYIN_MAX_BINS: voiced states
+PYIN_MAX_TROUGHS = 512        # the Boltzmann pieces of the observation table
+PYIN_TABLE_DOUBLES = 1326     # ISPK_PYIN_TABLE_DOUBLES: thr [100], prior [100], its running sum [101], e2 [512], inv [513]
+PYIN_MAX_PERIOD = 1022        # lags of a 2,048-sample frame with a 1,024-sample window
+PYIN_MAX_WIDTH = 127          # transition window: two codes per offset fit one backpointer byte
+PYIN_FRAMES_PER_BLOCK = 8     # ispk_pyin_frames_per_block(): frames of one item per workgroup of the observation
+
+
+def pyin_workspace_bytes(B: int, M: int, NB: int) -> int:
+    """ispk_pyin_workspace_bytes: two float64 per (item, frame) and one backpointer byte per (item, frame, state), rounded up to 8."""
+    return 16 * B * M + (2 * B * M * NB + 7) // 8 * 8
+
+
+def pyin_observe(audio: Tensor, audio_len: Tensor, tables: Tensor, prior: Tensor, obs: Tensor, frames: Optional[Tensor],
+                 min_period: int, max_period: int, sample_rate: float, f_min: float, bins_per_semitone: int) -> Tensor:
+    """ispk_pyin_observe_f32, one launch, no host read: the pYIN observation rows (include/ispk.h has the definition) of fp32 audio
+    [B, S] (unit stride on S, any row stride) with int64 lengths [B] into obs fp32 [B, M, NB] (contiguous, M at least
+    feature_frames(S)), zeros past each item's frames; frames int64 [B] or None receives the frame counts.  tables: fp32, W_2048 in
+    front (data.twiddles(), or an AcousticFeatures' tables); prior: float64 [PYIN_TABLE_DOUBLES] (data.pitch.observation_table)."""
+    _rt._dev(audio, audio_len, tables, prior, obs, frames)
+    if audio.dtype != torch.float32 or audio.ndim != 2 or (audio.shape[1] > 1 and audio.stride(1) != 1):
+        raise ValueError(f"audio: fp32 [B, S] with unit stride on S, got {audio.dtype} {tuple(audio.shape)} strides "
+                         f"{tuple(audio.stride())}")
+    B, S = audio.shape
+    _out_like("audio_len", audio_len, torch.int64, (B,))
+    if tables.dtype != torch.float32 or not tables.is_contiguous() or tables.numel() < 4096:
+        raise ValueError(f"tables: contiguous fp32 of at least 4096 values, got {tables.dtype} {tuple(tables.shape)}")
+    if prior.dtype != torch.float64 or tuple(prior.shape) != (PYIN_TABLE_DOUBLES,) or not prior.is_contiguous():
+        raise ValueError(f"prior: contiguous float64 [{PYIN_TABLE_DOUBLES}], got {prior.dtype} {tuple(prior.shape)}")
+    if obs.dtype != torch.float32 or obs.ndim != 3 or obs.shape[0] != B or not obs.is_contiguous():
+        raise ValueError(f"obs: contiguous fp32 [{B}, M, NB], got {obs.dtype} {tuple(obs.shape)}")
+    M, NB = obs.shape[1], obs.shape[2]
+    if M < _rt.feature_frames(S) or not 1 <= NB <= PYIN_MAX_BINS:
+        raise ValueError(f"obs: at least {_rt.feature_frames(S)} frames and 1 .. {PYIN_MAX_BINS} bins, got {tuple(obs.shape)}")
+    if frames is not None:
+        _out_like("frames", frames, torch.int64, (B,))
+    if B == 0 or M == 0:
+        return obs
+    # per frame three 1,024-point transforms (5 radix-4 passes of 256 butterflies, ~34 flops each) and about 100 float64 steps per
+    # trough; the audio is read 2048 / 256 times over through the cache, once from memory
+    _rt._launch("pyin_observe_kernel", B * M * (3.0 * 5 * 256 * 34 + 4.0 * 2048 * 6), 4.0 * B * S + 4.0 * B * M * NB,
+                _rt.lib().ispk_pyin_observe_f32, audio.data_ptr(), audio.stride(0) if B > 1 else max(audio.stride(0), S),
+                audio_len.data_ptr(), tables.data_ptr(), prior.data_ptr(), obs.data_ptr(), _rt._ptr(frames), B, S, M, NB, int(min_period),
+                int(max_period), float(sample_rate), float(f_min), int(bins_per_semitone), _rt._stream())
+    return obs
+
+
+_PYIN_OUTPUTS = (("state", torch.int32), ("f0", torch.float32), ("voiced", torch.int32), ("voiced_prob", torch.float32))
+
+
+def pyin_decode(obs: Tensor, obs_len: Optional[Tensor], trans: Tensor, width: int, f_min: float, bins_per_semitone: int,
+                out: Optional[dict] = None, pitch_mean: float = 0.0, pitch_std: float = 1.0) -> dict:
+    """ispk_pyin_decode_f64, one launch, no host read: the Viterbi path (include/ispk.h has the recursion) through obs - fp32
+    [B, M, NB] voiced probabilities, or float64 [B, M, 2 NB] ready log-observations - over the first obs_len[b] frames (int64 [B];
+    None: M each) -> a dict of state int32, f0 fp32, voiced int32, voiced_prob fp32 [B, M]; frames int64 [B]; log_prob float64 [B];
+    work (uint8 scratch of pyin_workspace_bytes); and pitch fp32 [B, M] = (f0 - pitch_mean) / pitch_std where `out` holds one.
+    trans: float64 [width + NB + 3] (data.pitch.transition_table).  `out` may hold any of them; the rest is allocated."""
+    if obs.ndim != 3 or obs.dtype not in (torch.float32, torch.float64) or not obs.is_contiguous():
+        raise ValueError(f"obs: contiguous fp32 [B, M, NB] or float64 [B, M, 2 NB], got {obs.dtype} {tuple(obs.shape)}")
+    is_log = obs.dtype == torch.float64
+    B, M = obs.shape[:2]
+    if is_log and obs.shape[2] % 2:
+        raise ValueError(f"obs: float64 log-observations hold 2 NB states, got {tuple(obs.shape)}")
+    NB = obs.shape[2] // 2 if is_log else obs.shape[2]
+    if not 1 <= NB <= PYIN_MAX_BINS:
+        raise ValueError(f"obs: 1 .. {PYIN_MAX_BINS} bins, got {NB}")
+    if int(width) != width or not 1 <= width <= PYIN_MAX_WIDTH or width % 2 == 0:
+        raise ValueError(f"width is an odd integer in [1, {PYIN_MAX_WIDTH}], got {width!r}")
+    if trans.dtype != torch.float64 or tuple(trans.shape) != (width + NB + 3,) or not trans.is_contiguous():
+        raise ValueError(f"trans: contiguous float64 [{width + NB + 3}], got {trans.dtype} {tuple(trans.shape)}")
+    if obs_len is not None:
+        _out_like("obs_len", obs_len, torch.int64, (B,))
+    dev = obs.device
+    r = {}
+    for name, dt in _PYIN_OUTPUTS:
+        r.update(_segment_tensors(((name, dt, 0),), (B, M), out, dev))
+    r.update(_segment_tensors((("frames", torch.int64, 0), ("log_prob", torch.float64, 0)), (B,), out, dev))
+    pitch = None if out is None else out.get("pitch")
+    if pitch is not None:
+        _out_like("pitch", pitch, torch.float32, (B, M))
+        if not pitch.is_contiguous():
+            raise ValueError("pitch: contiguous fp32 [B, M]")
+        if float(pitch_std) == 0.0:
+            raise ValueError("pitch std is 0")
+        r["pitch"] = pitch
+    need = pyin_workspace_bytes(B, M, NB)
+    work = None if out is None else out.get("work")
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    r["work"] = work
+    _rt._dev(obs, obs_len, trans, *r.values())
+    if B == 0:
+        return r
+    # per (frame, bin) 2 x width float64 add-compare steps and one log; the rows are read once, a backpointer byte per state
+    _rt._launch("pyin_decode_kernel", B * M * NB * (4.0 * width + 40.0), obs.element_size() * float(obs.numel()) + 2.0 * B * M * NB,
+                _rt.lib().ispk_pyin_decode_f64, obs.data_ptr(), int(is_log), _rt._ptr(obs_len), trans.data_ptr(), int(width), float(f_min),
+                int(bins_per_semitone), float(pitch_mean), float(pitch_std), r["state"].data_ptr(), r["f0"].data_ptr(),
+                r["voiced"].data_ptr(), r["voiced_prob"].data_ptr(), _rt._ptr(pitch), r["frames"].data_ptr(), r["log_prob"].data_ptr(),
+                work.data_ptr(), work.numel(), B, M, NB, _rt._stream())
+    return r

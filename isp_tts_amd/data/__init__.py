@@ -4,6 +4,7 @@ from .condition import AudioConditioner, Limiter, k_weighting, meter_table, to_p
 from .equalize import (Band, Equalizer, bandpass, deemphasis, equalizer_table, highpass, highshelf, lowpass, lowshelf,  # noqa: F401
                        notch, peaking, preemphasis)
 from .noise import NoiseReducer  # noqa: F401
+from .pitch import PitchTracker  # noqa: F401
 from .resample import AudioFrontEnd, Resampler, compact_taps, resampled_length, sinc_hann_taps  # noqa: F401
 from .screen import Screen  # noqa: F401
 from .segment import Segmenter  # noqa: F401

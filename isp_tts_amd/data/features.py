@@ -139,20 +139,34 @@ class AcousticFeatures:
                  M = (S + 768 - 1024) // 256 + 1 (0 below 256 samples), zeros past each mel_len; an utterance below 256
                  samples (where the reference's torch.stft raises) or longer than S gets mel_len 0 and zero rows.
     Pitch is normalised with the dataset stats ((hz - mean) / std, unvoiced frames -mean / std) and 0 past its own frame
-    count, as dataset.py:151-152 leaves it."""
+    count, as dataset.py:151-152 leaves it.
+    pitch_method="pyin": the contour is data.PitchTracker's (pitch_f_min .. pitch_f_max Hz, csrc/pyin.hip) instead, normalised
+    the same way, one value per mel frame; the extractor's launch then computes no pitch and two launches follow it.  The
+    tracker's own tensors (f0 in Hz, voiced flags, ...) are in out["pyin"]."""
+
+    PITCH_METHODS = ("torch-yin", "pyin")
 
     def __init__(self, sample_rate: int = 22050, n_mels: int = 80, f_min: float = 0.0, f_max: Optional[float] = 8000.0,
                  pitch: bool = True, pitch_f_max: float = 800, pitch_threshold: float = 0.15, pitch_mean: float = 0.0,
-                 pitch_std: float = 1.0, energy: bool = True, mel_sample_rate: Optional[int] = None):
+                 pitch_std: float = 1.0, energy: bool = True, mel_sample_rate: Optional[int] = None,
+                 pitch_method: str = "torch-yin", pitch_f_min: float = 55.0):
         self.sample_rate = int(sample_rate)
         mel_sr = int(mel_sample_rate if mel_sample_rate is not None else sample_rate)
         self.n_mels = int(n_mels)
         if not 1 <= self.n_mels <= 128:
             raise NotImplementedError(f"n_mels={n_mels}: 1 .. 128 mel channels are built")
+        if pitch_method not in self.PITCH_METHODS:
+            raise NotImplementedError(f"pitch method {pitch_method!r}: only torch-yin is built")
         self.pitch, self.energy = bool(pitch), bool(energy)
+        self.pitch_method, self.tracker = pitch_method, None
         self.threshold, self.pitch_mean, self.pitch_std = float(pitch_threshold), float(pitch_mean), float(pitch_std)
         self.tau_min, self.tau_max = yin_lags(self.sample_rate, N_FFT, pitch_f_max)
-        if self.pitch:
+        if self.pitch and pitch_method == "pyin":
+            from .pitch import PitchTracker
+            self.tracker = PitchTracker(self.sample_rate, f_min=pitch_f_min, f_max=pitch_f_max)
+            if self.pitch_std == 0.0:
+                raise ValueError("pitch std is 0")
+        elif self.pitch:
             if int(HOP / self.sample_rate * self.sample_rate) != HOP:        # providers.py:298 and pitch.py:47
                 raise NotImplementedError(f"sample rate {sample_rate}: torch-yin's frame stride would not be {HOP}")
             if not (1 <= self.tau_min < self.tau_max - 1 and 2 * self.tau_max >= N_FFT and 3 * self.tau_max <= 2048):
@@ -200,8 +214,10 @@ class AcousticFeatures:
         pitch = _section(d, "pitch", d)
         kw = {}
         if pitch is not None:
-            if pitch.get("method", "torch-yin") != "torch-yin":
+            if pitch.get("method", "torch-yin") not in cls.PITCH_METHODS:
                 raise NotImplementedError(f"pitch method {pitch['method']!r}: only torch-yin is built")
+            if pitch.get("method", "torch-yin") == "pyin":
+                kw.update(pitch_method="pyin", pitch_f_min=float(pitch.get("f_min", 55.0)))
             if int(pitch.get("hop_length", HOP)) != HOP or int(pitch.get("win_length", N_FFT)) != N_FFT:
                 raise NotImplementedError("pitch hop_length / win_length other than 256 / 1024 are not built")
             if pitch.get("pad") is not None and int(pitch["pad"]) != PAD:
@@ -228,14 +244,19 @@ class AcousticFeatures:
         t = self._on.get(device)
         if t is None:
             t = self._on[device] = (self.tables.to(device), self.fb_index.to(device))
+            if self.tracker is not None:
+                self.tracker.device_tables(device)
         return t
 
     def empty_outputs(self, B: int, S: int, device) -> dict:
         M = runtime.feature_frames(S)
         f32 = dict(dtype=torch.float32, device=device)
-        return {"mel": torch.empty((B, self.n_mels, M), **f32), "mel_len": torch.empty((B,), dtype=torch.int64, device=device),
-                "pitch": torch.empty((B, M), **f32) if self.pitch else None,
-                "energy": torch.empty((B, M), **f32) if self.energy else None}
+        out = {"mel": torch.empty((B, self.n_mels, M), **f32), "mel_len": torch.empty((B,), dtype=torch.int64, device=device),
+               "pitch": torch.empty((B, M), **f32) if self.pitch else None,
+               "energy": torch.empty((B, M), **f32) if self.energy else None}
+        if self.tracker is not None:
+            out["pyin"] = self.tracker.empty_outputs(B, S, device, pitch=out["pitch"])
+        return out
 
     def __call__(self, audio: Tensor, audio_len: Tensor, out: Optional[dict] = None) -> dict:
         if audio.ndim != 2 or audio.dtype != torch.float32 or audio.stride(1) != 1:
@@ -248,9 +269,19 @@ class AcousticFeatures:
         if out is None:
             out = self.empty_outputs(B, S, audio.device)
         tables, fb_index = self.device_tables(audio.device)
-        runtime.audio_features(audio, audio_len, tables, fb_index, out["mel"], out["mel_len"], out.get("pitch"),
-                               out.get("energy"), self.tau_min, self.tau_max, float(self.sample_rate), self.threshold,
-                               self.pitch_mean, self.pitch_std)
+        if self.tracker is None:
+            runtime.audio_features(audio, audio_len, tables, fb_index, out["mel"], out["mel_len"], out.get("pitch"),
+                                   out.get("energy"), self.tau_min, self.tau_max, float(self.sample_rate), self.threshold,
+                                   self.pitch_mean, self.pitch_std)
+            return out
+        # pyin: the extractor's launch without its pitch, then the tracker's two, the contour straight into out["pitch"]
+        runtime.audio_features(audio, audio_len, tables, fb_index, out["mel"], out["mel_len"], None, out.get("energy"))
+        pitch = out.get("pitch")
+        if pitch is None or not pitch.is_contiguous():
+            raise ValueError("out['pitch']: a contiguous fp32 [B, M] tensor (take it from empty_outputs)")
+        if out.get("pyin") is None or out["pyin"].get("pitch") is not pitch:
+            out["pyin"] = self.tracker.empty_outputs(B, S, audio.device, pitch=pitch)
+        self.tracker.normalised(self.pitch_mean, self.pitch_std)(audio, audio_len, out=out["pyin"])
         return out
 
 
