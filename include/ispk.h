@@ -1454,6 +1454,49 @@ int32_t ispk_screen_f64(const float* audio, int64_t ld_audio, const int64_t* aud
                         int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S, ispk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Declipper (csrc/declip.hip, isp_tts_amd/data/declip.py): the clipped samples that the screen finds, restored by Janssen's AR
+ * interpolation (Janssen, Veldhuis & Vries 1986) in float64.  Four launches, no atomics, no host read.  audio fp32 [B][S], unit
+ * stride on S, row stride ld_audio >= S; n = audio_len[b] if 0 <= audio_len[b] <= S, else 0.  x is the item with every
+ * non-finite sample read as 0 (such a sample is copied through unchanged); all integers, `/` floors.
+ *   peak, thr, runs      the screen's, value for value: thr = the fp32 product max|x| * rail_ratio (rail_mode 0) or rail
+ *     (rail_mode 1); a sample is at the rail when |x| >= thr > 0; a run is a maximal stretch of at-rail samples of one sign.
+ *     The UNKNOWN samples are those of the runs of at least min_run samples; clip_samples int64 counts them.
+ *   Segments.  Segment j = [512 j, 512 j + 512) within [0, n), solved in its window [512 j - 256, 512 j + 768) within [0, n)
+ *     (N <= 1024 samples): every unknown of the window is solved jointly, the segment's own are kept.  A segment without an
+ *     unknown of its own is a copy and counts nowhere.  A segment whose window holds more than ispk_declip_max_unknowns() = 256
+ *     unknowns, or in which a non-finite intermediate appears (a prediction error or a pivot that is not > 0, a solution that is
+ *     not finite), is left as it is and counted in dense.
+ *   A pass over the window w (float64; the unknowns start at their clipped values), `iterations` times:
+ *     r[k] = sum_i w[i] w[i + k], k = 0 .. order; r[0] *= 1 + 1e-9; r[0] == 0 ends the passes.  Levinson-Durbin gives a[0 ..
+ *     order], a[0] = 1.  b[k] = sum_i a[i] a[i + k].  B[s][t] = b[|s - t|] for |s - t| <= order, else 0; U the window's unknown
+ *     positions, K the rest: solve B_UU x_U = -B_UK x_K (banded Cholesky, two triangular solves).  Then w[u] = s max(s x_u, s
+ *     orig_u), s the sign of the run: a restored sample never lies inside the rail.
+ *   out fp32 [B][S] (row stride ld_out >= S): the restored samples are the float64 values rounded once; every other sample
+ *     below n keeps its bits; zeros from n on.  out_len int64 = n.  peak fp32 = max |out| (it may exceed 1).  restored int64 =
+ *     the samples replaced; windows, dense int32 = the segments solved and left.  flags int32: 1 restored (restored > 0), 2 dense
+ *     (dense > 0), 4 skipped.  in_flags int32 [B] or NULL: the screen's flags; an item without bit 1 there is copied bit for
+ *     bit, gets flag 4 and zeros in clip_samples, restored, windows and dense.
+ * ispk_declip_max_unknowns     256.
+ * ispk_declip_workspace_bytes  *bytes (HOST memory) = what ispk_declip_f64 needs for (B, S): per item 16 B per segment of 512
+ *                       samples and 4 B per tile of 4,096, rounded up to 8 B.
+ * ispk_declip_f64       grid (ceil(S / 4096), B): the tiles' peaks.  Grid (B): thr.  Grid (ceil(S / 512), B): the segments (81,408
+ *                       B of LDS, two workgroups per CU; a segment with nothing at the rail is an 8-byte-wide copy).  Grid (B): the
+ *                       counts, the output's peak, the flags.  All outputs but out contiguous.
+ * An item's results depend on that item alone - not on B, S, the row strides, the alignment or what lies behind n; repeated
+ * calls and graph replays repeat their bits.
+ * Refused before any launch: B > 65535, S outside [0, 2^24], rail_mode not 0 or 1, rail_ratio outside (0, 1] (mode 0), a rail
+ * that is not positive and finite (mode 1), min_run outside 1 .. 64, order outside 1 .. 32, iterations outside 1 .. 8, a row
+ * stride below S, out overlapping audio (E_SHAPE); NULLs other than in_flags (E_NULL); a workspace below
+ * ispk_declip_workspace_bytes or off an 8-byte boundary (E_ALIGN).  B = 0 is a no-op. */
+int32_t ispk_declip_max_unknowns(void);
+int32_t ispk_declip_workspace_bytes(int32_t B, int32_t S, int64_t* bytes);
+int32_t ispk_declip_f64(const float* audio, int64_t ld_audio, const int64_t* audio_len, const int32_t* in_flags, int32_t rail_mode,
+                        float rail, float rail_ratio, int32_t min_run, int32_t order, int32_t iterations, float* out, int64_t ld_out,
+                        int64_t* out_len, float* thr, float* peak, int64_t* clip_samples, int64_t* restored, int32_t* windows,
+                        int32_t* dense, int32_t* flags, void* workspace, int64_t workspace_bytes, int32_t B, int32_t S,
+                        ispk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * NoiseReducer (csrc/noise.hip, isp_tts_amd/data/noise.py): stationary noise reduction.  The noise spectrum of an item is
  * learnt from its own pauses (the profile), then every frame is attenuated with a Wiener gain smoothed over time and frequency
  * (the reduce).  audio fp32 [B][S], unit stride on S, row stride ld_audio >= S; n = audio_len[b] if 0 <= audio_len[b] <= S,

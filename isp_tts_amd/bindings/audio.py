@@ -1,7 +1,7 @@
 """Waveforms in and out: features, resampling, statistics and conditioning (csrc/features.hip, audio.hip, condition.hip);
 the document join, speech marks, gain envelope and true-peak limiter (csrc/join.hip, marks.hip, prosody.hip, limiter.hip); the
-equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip); the noise reducer (csrc/noise.hip);
-the time stretch (csrc/stretch.hip); the pitch tracker (csrc/pyin.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
+equalizer (csrc/equalizer.hip); the segmenter (csrc/segment.hip); the screen (csrc/screen.hip); the declipper (csrc/declip.hip); the
+noise reducer (csrc/noise.hip); the time stretch (csrc/stretch.hip); the pitch tracker (csrc/pyin.hip).  The vocoders' wrappers are in bindings/vocoders.py."""
 from typing import Optional
 
 import torch
@@ -17,7 +17,9 @@ __all__ = ["FEATURE_HOP", "FEATURE_TABLE_HEAD", "feature_frames", "audio_feature
            "LIMIT_MAX_LOOKAHEAD", "LIMIT_TAPS", "limit", "EQ_MAX_SECTIONS", "EQ_SEGMENT_SAMPLES", "EQ_CHUNK_SAMPLES",
            "EQ_TABLE_DOUBLES", "equalize_workspace_doubles", "equalize", "SEGMENT_MAX_SEGMENTS", "SEGMENT_MAX_ROWS", "SEGMENT_MAX_PAD",
            "SEGMENT_FLAGS", "segment_workspace_bytes", "segment_plan", "segment_gather", "SCREEN_TILE_SAMPLES", "SCREEN_TILE_FRAMES",
-           "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen", "NOISE_TILE_SAMPLES", "NOISE_BINS",
+           "SCREEN_BINS", "SCREEN_FLAGS", "SCREEN_OUTPUTS", "screen_workspace_bytes", "screen", "DECLIP_SEGMENT_SAMPLES",
+           "DECLIP_MAX_UNKNOWNS", "DECLIP_MAX_ORDER", "DECLIP_MAX_RUN", "DECLIP_MAX_ITERATIONS", "DECLIP_FLAGS", "DECLIP_OUTPUTS",
+           "declip_workspace_bytes", "declip", "NOISE_TILE_SAMPLES", "NOISE_BINS",
            "NOISE_MIN_SAMPLES", "NOISE_MAX_GUARD", "NOISE_MAX_SMOOTH_FRAMES", "NOISE_MAX_SMOOTH_BINS", "NOISE_FLAGS", "NOISE_OUTPUTS",
            "noise_workspace_bytes", "noise_profile", "noise_reduce", "STRETCH_TILE_SAMPLES", "STRETCH_BINS", "STRETCH_MIN_SAMPLES",
            "STRETCH_RATES", "STRETCH_FLAGS", "stretch_workspace_bytes", "stretch", "PYIN_THRESHOLDS", "PYIN_MAX_BINS", "PYIN_MAX_TROUGHS",
@@ -642,8 +644,70 @@ def screen(audio: Tensor, audio_len: Tensor, tables: Tensor, rail_mode: int, rai
     return r
 
 
+# ------------------------------------------------------------------------------------------------------ declipper
+DECLIP_SEGMENT_SAMPLES = 512  # samples of one item per workgroup of the solve; its window reaches 256 further on either side
+DECLIP_MAX_UNKNOWNS = 256     # ispk_declip_max_unknowns(): a window with more unknown samples is left as it is (dense)
+DECLIP_MAX_ORDER, DECLIP_MAX_RUN, DECLIP_MAX_ITERATIONS = 32, 64, 8
+DECLIP_FLAGS = {"restored": 1, "dense": 2, "skipped": 4}
+# name, dtype, trailing dimension (0: none), in the order of ispk_declip_f64's output pointers behind out
+DECLIP_OUTPUTS = (("audio_len", torch.int64, 0), ("thr", torch.float32, 0), ("peak", torch.float32, 0), ("clip_samples", torch.int64, 0),
+                  ("restored", torch.int64, 0), ("windows", torch.int32, 0), ("dense", torch.int32, 0), ("flags", torch.int32, 0))
+
+
+def declip_workspace_bytes(B: int, S: int) -> int:
+    """ispk_declip_workspace_bytes: per item 16 B per segment of 512 samples and 4 B per tile of 4,096, rounded up to 8 B."""
+    return 8 * B * (2 * max(1, -(-S // DECLIP_SEGMENT_SAMPLES)) + (max(1, -(-S // 4096)) + 1) // 2)
+
+
+def declip(audio: Tensor, audio_len: Tensor, flags: Optional[Tensor], rail_mode: int, rail: float, rail_ratio: float, min_run: int,
+           order: int, iterations: int, out: Optional[dict] = None) -> dict:
+    """ispk_declip_f64, four launches, no host read: the clipped samples (include/ispk.h has the definition) of fp32 audio [B, S]
+    (unit stride on S, any row stride) with int64 lengths [B], restored by AR interpolation in float64 -> a dict of audio fp32
+    [B, S] (any row stride, no memory of the input's), the DECLIP_OUTPUTS [B] each, and work (uint8 scratch of
+    declip_workspace_bytes).  flags: the screen's int32 [B] or None; an item without bit 1 is copied.  `out` may hold any of the
+    tensors; the rest is allocated."""
+    B, S = _segment_audio(audio)
+    if S > CONDITION_MAX_SAMPLES:
+        raise ValueError(f"audio: at most {CONDITION_MAX_SAMPLES} samples an item, got {tuple(audio.shape)}")
+    for name, v, top in (("min_run", min_run, DECLIP_MAX_RUN), ("order", order, DECLIP_MAX_ORDER), ("iterations", iterations, DECLIP_MAX_ITERATIONS)):
+        if int(v) != v or not 1 <= v <= top:
+            raise ValueError(f"{name} is an integer in [1, {top}], got {v!r}")
+    dev = audio.device
+    r = {}
+    o = None if out is None else out.get("audio")
+    o = torch.empty((B, S), dtype=torch.float32, device=dev) if o is None else o
+    if o.dtype != torch.float32 or tuple(o.shape) != (B, S) or (S > 1 and o.stride(1) != 1) or (B > 1 and o.stride(0) < S):
+        raise ValueError(f"out audio: fp32 [{B}, {S}] with unit stride on the samples, got {o.dtype} {tuple(o.shape)} strides {tuple(o.stride())}")
+    ld_in, ld_out = (audio.stride(0) if B > 1 else max(audio.stride(0), S)), (o.stride(0) if B > 1 else max(o.stride(0), S))
+    if B and S:
+        a0, o0 = audio.data_ptr(), o.data_ptr()
+        a1, o1 = a0 + 4 * ((B - 1) * ld_in + S), o0 + 4 * ((B - 1) * ld_out + S)
+        if not (a1 <= o0 or o1 <= a0):
+            raise ValueError("out audio overlaps the input: the declipper works out of place only (neighbouring windows read each "
+                             "other's clipped values)")
+    r["audio"] = o
+    for name, dt, last in DECLIP_OUTPUTS:
+        r.update(_segment_tensors(((name, dt, 0),), (B, last) if last else (B,), out, dev))
+    need = declip_workspace_bytes(B, S)
+    work = None if out is None else out.get("work")
+    work = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if work is None else work
+    if work.dtype != torch.uint8 or work.ndim != 1 or not work.is_contiguous() or work.numel() < need:
+        raise ValueError(f"work: contiguous uint8 of at least {need} bytes, got {work.dtype} {tuple(work.shape)}")
+    if audio_len.dtype != torch.int64 or audio_len.shape != (B,) or not audio_len.is_contiguous():
+        raise ValueError(f"audio_len: contiguous int64 [{B}], got {audio_len.dtype} {tuple(audio_len.shape)}")
+    if flags is not None and (flags.dtype != torch.int32 or flags.shape != (B,) or not flags.is_contiguous()):
+        raise ValueError(f"flags: contiguous int32 [{B}], got {flags.dtype} {tuple(flags.shape)}")
+    _rt._dev(audio, audio_len, flags, work, *r.values())
+    # one read for the peak, one read and one write by the segments; per solved window and pass a banded Cholesky of <= 256 x 33
+    _rt._launch("declip_kernels", 0.0, 12.0 * B * S, _rt.lib().ispk_declip_f64, audio.data_ptr(), ld_in, audio_len.data_ptr(), _rt._ptr(flags),
+                int(rail_mode), float(rail), float(rail_ratio), int(min_run), int(order), int(iterations), o.data_ptr(), ld_out,
+                *(r[name].data_ptr() for name, _, _ in DECLIP_OUTPUTS), work.data_ptr(), work.numel(), B, S, _rt._stream())
+    r["work"] = work
+    return r
+
+
 # ------------------------------------------------------------------------------------------------------ noise reducer
-NOISE_TILE_SAMPLES = 4096     # ispk_noise_tile_samples(): output samples of one item per workgroup of the reduce
+NOISE_TILE_SAMPLES = 4096    # ispk_noise_tile_samples(): output samples of one item per workgroup of the reduce
 NOISE_BINS = 513
 NOISE_MIN_SAMPLES = 513       # below this the reflect padding is undefined: flagged short, copied
 NOISE_MAX_GUARD = 65536       # frames

@@ -1,6 +1,7 @@
 from .features import (AcousticFeatures, collate_audio, melscale_fbanks, pack_filterbank, pitch_frames,  # noqa: F401
                        twiddles, yin_lags)
 from .condition import AudioConditioner, Limiter, k_weighting, meter_table, to_pcm16, true_peak_taps  # noqa: F401
+from .declip import Declipper  # noqa: F401
 from .equalize import (Band, Equalizer, bandpass, deemphasis, equalizer_table, highpass, highshelf, lowpass, lowshelf,  # noqa: F401
                        notch, peaking, preemphasis)
 from .noise import NoiseReducer  # noqa: F401
