@@ -18,7 +18,7 @@
 // Every sum runs in a fixed order and there are no atomics: repeated calls and graph replays give the same bits.
 #include <algorithm>
 
-#include "common.h"
+#include "chunk_grid.h"
 
 namespace {
 
@@ -117,19 +117,6 @@ __device__ __forceinline__ float key_value(uint32_t k) {
     return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-// Sum of one double per thread in a fixed tree order; every thread gets the result.  Ends with a barrier.
-__device__ __forceinline__ double block_sum(double x, int tid, double* red) {
-    red[tid] = x;
-    __syncthreads();
-    for (int s = kStThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(kStThreads) void feature_stats_kernel(const float* __restrict__ pitch, int64_t ld_pitch,
                                                                    const float* __restrict__ energy, int64_t ld_energy,
                                                                    const int64_t* __restrict__ mel_len, double* __restrict__ partial,
@@ -194,8 +181,8 @@ __global__ __launch_bounds__(kStThreads) void feature_stats_kernel(const float* 
                 mx = fmaxf(mx, v);
             }
         }
-    const double count = block_sum(cnt, tid, red);
-    const double total = block_sum(sum, tid, red);
+    const double count = block_sum<kStThreads>(cnt, tid, red);
+    const double total = block_sum<kStThreads>(sum, tid, red);
     const double mean = count > 0.0 ? total / count : 0.0;
     double m2 = 0.0;
     if (live)
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(kStThreads) void feature_stats_kernel(const float* 
             const float v = key_value(keys[i]);
             if ((double)v > lower && (double)v < upper && (f != 0 || v > 0.f)) m2 += ((double)v - mean) * ((double)v - mean);
         }
-    const double M2 = block_sum(m2, tid, red);
+    const double M2 = block_sum<kStThreads>(m2, tid, red);
     fred[tid] = mn;
     fred[kStThreads + tid] = mx;
     __syncthreads();

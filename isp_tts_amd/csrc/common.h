@@ -168,6 +168,19 @@ __device__ __forceinline__ float wave_sum(float v) {   // every lane ends with t
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {   // the same butterfly in float64: every lane gets the same bits
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// NaN and the infinities read as 0 (the audio kernels' rule for samples that are not numbers)
+__device__ __forceinline__ bool is_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }
+__device__ __forceinline__ float finite_or_zero(float x) { return is_finite(x) ? x : 0.f; }
 // lane l <- lane l-1; lane 0 keeps `lane0_value` (bound_ctrl off: invalid source lanes keep `old`)
 __device__ __forceinline__ float dpp_shr1(float src, float lane0_value) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, lane0_value),

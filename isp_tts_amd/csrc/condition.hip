@@ -22,7 +22,8 @@
 // The meter is a serial recurrence s' = A s + B x over the 4 states of the cascade (transposed direct form II), in float64.
 // It runs as a chunked scan on a grid fixed to sample 0: a chunk is 32 samples, a segment 256 chunks = one workgroup.  `start`
 // is a multiple of 256, so it always falls on a chunk boundary and the zero-entry final state of a chunk does not depend on it.
-//   cond_chunk_kernel   grid (W, B).  Stages the segment in LDS (float4 loads when the row base is aligned, zeros past len);
+//   cond_chunk_kernel   grid (W, B).  Stages the segment in LDS (chunk_grid.h: the grid, its staging and the order of the hop
+//                       sums, shared with the segmenter and the noise profile, whose frames are these bit for bit);
 //                       every lane runs its chunk from zero state; writes the 256-sample square sums (hops: a trim frame is four),
 //                       every chunk's final state, and - after a scan across the lanes with the host's A^(32 2^k) - the segment's.
 //   cond_meter_kernel   grid (W, B).  Every workgroup derives (start, end) from the hop sums by itself; a workgroup whose
@@ -38,18 +39,11 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "chunk_grid.h"
 #include "dropout.h"
 
 namespace {
 
-constexpr int kCdThreads = 256;
-constexpr int kCdChunk = 32;                        // samples per lane
-constexpr int kCdSeg = kCdThreads * kCdChunk;       // 8,192 samples per workgroup
-constexpr int kCdPad = kCdChunk + 4;                // LDS floats per chunk: 16 lanes of a ds_read_b128 group hit 16 distinct bank quads
-constexpr int kCdHop = 256, kCdFrame = 1024;
-constexpr int kCdHopChunks = kCdHop / kCdChunk;     // 8 lanes per hop
-constexpr int kCdSegHops = kCdSeg / kCdHop;         // 32
 constexpr int kCdSegSteps = 12;                     // steps a segment can meet: ceil(8192 / 800) + 1 at the lowest rate
 constexpr int kCdGroups = 16;                       // lane groups of the step reduction
 constexpr int kCdPowers = 9;                        // A^(32 2^k), k = 0 .. 8; the last is A^8192
@@ -90,7 +84,7 @@ __device__ __forceinline__ void mat_acc(const double* __restrict__ P, const doub
 
 // Inclusive scan over the workgroup's lanes of S_c = A^32 S_(c-1) + v_c (Hillis-Steele, in registers; st is the exchange
 // buffer).  Ends with every lane's result also in st[.][tid], after a barrier.
-__device__ __forceinline__ void cd_scan(double (*st)[kCdThreads], const double* __restrict__ tab, int tid, double v[4]) {
+__device__ __forceinline__ void cd_scan(double (*st)[kGridThreads], const double* __restrict__ tab, int tid, double v[4]) {
 #pragma unroll 1
     for (int k = 0; k < 8; ++k) {
         st[0][tid] = v[0], st[1][tid] = v[1], st[2][tid] = v[2], st[3][tid] = v[3];
@@ -106,23 +100,6 @@ __device__ __forceinline__ void cd_scan(double (*st)[kCdThreads], const double* 
     __syncthreads();
 }
 
-// xs[chunk c][k] = x(base + 32 c + k), 0 at or past len.  Nothing at or past len is read.
-__device__ __forceinline__ void cd_stage(float* xs, const float* __restrict__ row, int64_t base, int64_t len, int vec, int tid) {
-    for (int g = tid; g < kCdSeg / 4; g += kCdThreads) {
-        const int64_t i = base + 4 * (int64_t)g;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec && i + 4 <= len) {
-            v = *reinterpret_cast<const f32x4*>(row + i);
-        } else {
-            if (i < len) v.x = row[i];
-            if (i + 1 < len) v.y = row[i + 1];
-            if (i + 2 < len) v.z = row[i + 2];
-            if (i + 3 < len) v.w = row[i + 3];
-        }
-        *reinterpret_cast<f32x4*>(xs + (g >> 3) * kCdPad + (g & 7) * 4) = v;
-    }
-}
-
 struct CondArgs {
     int64_t ld;
     int S, W, NH, NS, step, vec;
@@ -131,58 +108,34 @@ struct CondArgs {
     double *hop, *chunk, *seg, *segstep, *segpeak, *steps;
 };
 
-__device__ __forceinline__ int64_t cd_len(const int64_t* __restrict__ audio_len, int b, int S) {
-    const int64_t len = audio_len[b];
-    return (len < 0 || len > S) ? 0 : len;
-}
-
-__global__ __launch_bounds__(kCdThreads) void cond_chunk_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
-                                                                const double* __restrict__ tab, const CondArgs a) {
-    __shared__ __attribute__((aligned(16))) float xs[kCdThreads * kCdPad];
-    __shared__ double st[4][kCdThreads];
+__global__ __launch_bounds__(kGridThreads) void cond_chunk_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
+                                                                  const double* __restrict__ tab, const CondArgs a) {
+    __shared__ __attribute__((aligned(16))) float xs[kGridThreads * kGridPad];
+    __shared__ double st[4][kGridThreads];
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int64_t len = cd_len(audio_len, b, a.S);
-    cd_stage(xs, audio + (int64_t)b * a.ld, (int64_t)w * kCdSeg, len, a.vec, tid);
+    const int64_t len = valid_len(audio_len, b, a.S);
+    stage_chunks(xs, audio + (int64_t)b * a.ld, (int64_t)w * kGridSeg, len, a.vec, tid);
     __syncthreads();
     const Kw c = kw_load(tab);
     double s[4] = {0.0, 0.0, 0.0, 0.0}, e = 0.0;
-    const float* x = xs + tid * kCdPad;
-#pragma unroll
-    for (int k4 = 0; k4 < kCdChunk / 4; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * k4);
-        const double xd[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            e = fma(xd[q], xd[q], e);
-            kw_step(c, xd[q], s);
-        }
-    }
+    each_sample(xs, tid, [&](int, double x) {
+        e = fma(x, x, e);                                               // chunk_square_sum's chain, in the filter's pass
+        kw_step(c, x, s);
+    });
     st[0][tid] = e;
     __syncthreads();
-    if (tid < kCdSegHops) {
-        const int h = w * kCdSegHops + tid;
-        if (h < a.NH) {
-            double t = 0.0;
-            for (int q = 0; q < kCdHopChunks; ++q) t += st[0][tid * kCdHopChunks + q];
-            a.hop[(int64_t)b * a.NH + h] = t;
-        }
+    if (tid < kGridSegHops) {
+        const int h = w * kGridSegHops + tid;
+        if (h < a.NH) a.hop[(int64_t)b * a.NH + h] = hop_fold(st[0], tid);
     }
     __syncthreads();
-    double* f = a.chunk + (((int64_t)b * a.W + w) * kCdThreads + tid) * 4;
+    double* f = a.chunk + (((int64_t)b * a.W + w) * kGridThreads + tid) * 4;
     f[0] = s[0], f[1] = s[1], f[2] = s[2], f[3] = s[3];
     cd_scan(st, tab, tid, s);
-    if (tid == kCdThreads - 1) {
+    if (tid == kGridThreads - 1) {
         double* g = a.seg + ((int64_t)b * a.W + w) * 4;
         g[0] = s[0], g[1] = s[1], g[2] = s[2], g[3] = s[3];
     }
-}
-
-__device__ __forceinline__ double frame_power(const double* __restrict__ hop, int t, int nh) {
-    double p = hop[t];
-    if (t + 1 < nh) p += hop[t + 1];
-    if (t + 2 < nh) p += hop[t + 2];
-    if (t + 3 < nh) p += hop[t + 3];
-    return p / (double)kCdFrame;
 }
 
 // (start, end) of item b from its hop sums; every thread gets them.  Uses red / ired as scratch and ends with a barrier.
@@ -190,69 +143,53 @@ __device__ __forceinline__ void cd_bounds(const double* __restrict__ hop, int64_
                                           int* ired, int64_t& start, int64_t& end) {
     start = 0, end = len;
     if (a.trim_mode == 0) return;
-    const int nh = (int)((len + kCdHop - 1) / kCdHop);
+    const int nh = (int)((len + kGridHop - 1) / kGridHop);
     double thr = a.trim_thr;
     if (a.trim_mode == 1) {
         double mx = 0.0;
-        for (int t = tid; t < nh; t += kCdThreads) mx = fmax(mx, frame_power(hop, t, nh));
-        red[tid] = mx;
-        __syncthreads();
-        for (int s = kCdThreads / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-            __syncthreads();
-        }
-        thr = red[0] * a.trim_thr;
-        __syncthreads();
+        for (int t = tid; t < nh; t += kGridThreads) mx = fmax(mx, frame_power(hop, t, nh));
+        thr = frame_threshold<kGridThreads>(mx, true, 0.0, a.trim_thr, tid, red);
+        __syncthreads();                                                // (red is st[0]: the caller's scans write it next)
     }
     int first = 0x7fffffff, last = -1;
-    for (int t = tid; t < nh; t += kCdThreads)
+    for (int t = tid; t < nh; t += kGridThreads)
         if (frame_power(hop, t, nh) > thr) {
             first = min(first, t);
             last = max(last, t);
         }
-    ired[tid] = first, ired[kCdThreads + tid] = last;
-    __syncthreads();
-    for (int s = kCdThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            ired[tid] = min(ired[tid], ired[tid + s]);
-            ired[kCdThreads + tid] = max(ired[kCdThreads + tid], ired[kCdThreads + tid + s]);
-        }
-        __syncthreads();
-    }
-    first = ired[0], last = ired[kCdThreads];
-    __syncthreads();
+    active_range<kGridThreads>(first, last, tid, ired);
     if (last < 0) {
         start = end = 0;
         return;
     }
-    start = std::max<int64_t>(0, (int64_t)kCdHop * ((int64_t)first - a.pad_frames));
-    end = std::min<int64_t>(len, (int64_t)kCdHop * ((int64_t)last + a.pad_frames) + kCdFrame);
+    start = trim_start(first, a.pad_frames);
+    end = trim_end(last, a.pad_frames, len);
 }
 
-__global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
-                                                                const double* __restrict__ tab, int64_t* __restrict__ bounds,
-                                                                const CondArgs a) {
-    __shared__ __attribute__((aligned(16))) float xs[kCdThreads * kCdPad];
-    __shared__ double st[4][kCdThreads];
-    __shared__ int ired[2 * kCdThreads];
+__global__ __launch_bounds__(kGridThreads) void cond_meter_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
+                                                                  const double* __restrict__ tab, int64_t* __restrict__ bounds,
+                                                                  const CondArgs a) {
+    __shared__ __attribute__((aligned(16))) float xs[kGridThreads * kGridPad];
+    __shared__ double st[4][kGridThreads];
+    __shared__ int ired[2 * kGridThreads];
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int64_t len = cd_len(audio_len, b, a.S);
+    const int64_t len = valid_len(audio_len, b, a.S);
     int64_t start, end;
     cd_bounds(a.hop + (int64_t)b * a.NH, len, a, tid, st[0], ired, start, end);
     if (w == 0 && tid == 0) bounds[2 * b] = start, bounds[2 * b + 1] = end;
-    const int64_t segb = (int64_t)w * kCdSeg;
-    if (end <= start || segb >= end || segb + kCdSeg <= start) return;      // (uniform) nothing of [start, end) here
+    const int64_t segb = (int64_t)w * kGridSeg;
+    if (end <= start || segb >= end || segb + kGridSeg <= start) return;      // (uniform) nothing of [start, end) here
 
     // the state at this segment's first sample
-    const int vs = (int)(start / kCdSeg);
-    const int64_t cs = start / kCdChunk;
+    const int vs = (int)(start / kGridSeg);
+    const int64_t cs = start / kGridChunk;
     double E[4] = {0.0, 0.0, 0.0, 0.0};
     if (w > vs) {
-        const double* f = a.chunk + (((int64_t)b * a.W + vs) * kCdThreads + tid) * 4;
-        const bool live = (int64_t)vs * kCdThreads + tid >= cs;
+        const double* f = a.chunk + (((int64_t)b * a.W + vs) * kGridThreads + tid) * 4;
+        const bool live = (int64_t)vs * kGridThreads + tid >= cs;
         double v[4] = {live ? f[0] : 0.0, live ? f[1] : 0.0, live ? f[2] : 0.0, live ? f[3] : 0.0};
         cd_scan(st, tab, tid, v);
-        E[0] = st[0][kCdThreads - 1], E[1] = st[1][kCdThreads - 1], E[2] = st[2][kCdThreads - 1], E[3] = st[3][kCdThreads - 1];
+        E[0] = st[0][kGridThreads - 1], E[1] = st[1][kGridThreads - 1], E[2] = st[2][kGridThreads - 1], E[3] = st[3][kGridThreads - 1];
         __syncthreads();
         for (int u = vs + 1; u < w; ++u) {
             const double* g = a.seg + ((int64_t)b * a.W + u) * 4;
@@ -261,12 +198,12 @@ __global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __r
             E[0] = n[0], E[1] = n[1], E[2] = n[2], E[3] = n[3];
         }
     }
-    const int64_t cg = (int64_t)w * kCdThreads + tid;                   // this lane's chunk on the item's grid
-    const int64_t cb = cg * kCdChunk;
+    const int64_t cg = (int64_t)w * kGridThreads + tid;                   // this lane's chunk on the item's grid
+    const int64_t cb = cg * kGridChunk;
     const bool live = cg >= cs && cb < end;
     double s[4];
     {
-        const double* f = a.chunk + (((int64_t)b * a.W + w) * kCdThreads + tid) * 4;
+        const double* f = a.chunk + (((int64_t)b * a.W + w) * kGridThreads + tid) * 4;
         const bool in = cg >= cs;
         double v[4] = {in ? f[0] : 0.0, in ? f[1] : 0.0, in ? f[2] : 0.0, in ? f[3] : 0.0};
         if (tid == 0) mat_acc(tab + 8, E, v);
@@ -274,7 +211,7 @@ __global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __r
         const int p = max(tid - 1, 0);
         s[0] = tid ? st[0][p] : E[0], s[1] = tid ? st[1][p] : E[1], s[2] = tid ? st[2][p] : E[2], s[3] = tid ? st[3][p] : E[3];
     }
-    cd_stage(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
+    stage_chunks(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
     __syncthreads();                                                    // (also: every lane has read its entry state from st)
 
     // rerun from the true state: y^2 into the step the sample belongs to (a chunk meets at most two), max |x|
@@ -285,11 +222,11 @@ __global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __r
     if (live) {
         const int64_t rel = cb - start;
         j0 = (int)(rel / a.step);
-        const int kend = (int)std::min<int64_t>(kCdChunk, end - cb);
+        const int kend = (int)std::min<int64_t>(kGridChunk, end - cb);
         const int nb = (int)std::min<int64_t>(kend, (int64_t)(j0 + 1) * a.step - rel);   // samples of step j0 in this chunk
-        const float* x = xs + tid * kCdPad;
+        const float* x = xs + tid * kGridPad;
 #pragma unroll
-        for (int k4 = 0; k4 < kCdChunk / 4; ++k4) {
+        for (int k4 = 0; k4 < kGridChunk / 4; ++k4) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * k4);
             const float xf[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -308,21 +245,21 @@ __global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __r
     double* A0 = st[0];
     double* A1 = st[1];
     double* part = st[2];                                               // [kCdSegSteps][kCdGroups] (192 of st[2..3]'s 512)
-    float* fpk = reinterpret_cast<float*>(ired + kCdThreads);
+    float* fpk = reinterpret_cast<float*>(ired + kGridThreads);
     A0[tid] = a0, A1[tid] = a1, ired[tid] = j0, fpk[tid] = pk;
     __syncthreads();
     const int jlo = (int)((std::max<int64_t>(segb, start) - start) / a.step);
     if (tid < kCdSegSteps * kCdGroups) {
         const int j = jlo + tid / kCdGroups, g = tid % kCdGroups;
         double t = 0.0;
-        for (int l = g * (kCdThreads / kCdGroups); l < (g + 1) * (kCdThreads / kCdGroups); ++l) {
+        for (int l = g * (kGridThreads / kCdGroups); l < (g + 1) * (kGridThreads / kCdGroups); ++l) {
             const int jl = ired[l];
             if (jl + 1 == j) t += A1[l];
             if (jl == j) t += A0[l];
         }
         part[tid] = t;
     }
-    for (int sft = kCdThreads / 2; sft > 0; sft >>= 1) {                // (the peak: a max, any order gives the same bits)
+    for (int sft = kGridThreads / 2; sft > 0; sft >>= 1) {                // (the peak: a max, any order gives the same bits)
         __syncthreads();
         if (tid < sft) fpk[tid] = fmaxf(fpk[tid], fpk[tid + sft]);
     }
@@ -335,35 +272,22 @@ __global__ __launch_bounds__(kCdThreads) void cond_meter_kernel(const float* __r
     if (tid == 0) a.segpeak[(int64_t)b * a.W + w] = (double)fpk[0];
 }
 
-// Sum of one double per thread in a fixed tree order; every thread gets the result.  Ends with a barrier.
-__device__ __forceinline__ double cd_block_sum(double x, int tid, double* red) {
-    red[tid] = x;
-    __syncthreads();
-    for (int s = kCdThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __device__ __forceinline__ double block_z(const double* __restrict__ st, int64_t j, double block_len) {
     return (((st[j] + st[j + 1]) + st[j + 2]) + st[j + 3]) / block_len;
 }
 
-__global__ __launch_bounds__(kCdThreads) void cond_gate_kernel(const int64_t* __restrict__ bounds, double* __restrict__ loudness,
-                                                               float* __restrict__ peak, float* __restrict__ gain, const CondArgs a) {
-    __shared__ double red[kCdThreads];
+__global__ __launch_bounds__(kGridThreads) void cond_gate_kernel(const int64_t* __restrict__ bounds, double* __restrict__ loudness,
+                                                                 float* __restrict__ peak, float* __restrict__ gain, const CondArgs a) {
+    __shared__ double red[kGridThreads];
     const int tid = threadIdx.x, b = blockIdx.x;
     const int64_t start = bounds[2 * b], end = bounds[2 * b + 1];       // (cond_meter_kernel's: 0 <= start <= end <= S)
     const int64_t nsteps = (end - start) / a.step, nblk = nsteps >= 4 ? nsteps - 3 : 0;
     double* steps = a.steps + (int64_t)b * a.NS;
-    for (int64_t j = tid; j < nsteps; j += kCdThreads) {
+    for (int64_t j = tid; j < nsteps; j += kGridThreads) {
         const int64_t lo = start + j * a.step, hi = lo + a.step - 1;
         double t = 0.0;
-        for (int64_t w = lo / kCdSeg; w <= hi / kCdSeg; ++w) {
-            const int64_t jlo = (std::max<int64_t>(w * kCdSeg, start) - start) / a.step;
+        for (int64_t w = lo / kGridSeg; w <= hi / kGridSeg; ++w) {
+            const int64_t jlo = (std::max<int64_t>(w * kGridSeg, start) - start) / a.step;
             t += a.segstep[((int64_t)b * a.W + w) * kCdSegSteps + (j - jlo)];
         }
         steps[j] = t;
@@ -371,34 +295,28 @@ __global__ __launch_bounds__(kCdThreads) void cond_gate_kernel(const int64_t* __
     __syncthreads();
     const double block_len = 4.0 * (double)a.step;
     double sum = 0.0, cnt = 0.0;
-    for (int64_t j = tid; j < nblk; j += kCdThreads) {
+    for (int64_t j = tid; j < nblk; j += kGridThreads) {
         const double z = block_z(steps, j, block_len);
         if (-0.691 + 10.0 * log10(z) > -70.0) sum += z, cnt += 1.0;
     }
-    const double sum1 = cd_block_sum(sum, tid, red), cnt1 = cd_block_sum(cnt, tid, red);
+    const double sum1 = block_sum<kGridThreads>(sum, tid, red), cnt1 = block_sum<kGridThreads>(cnt, tid, red);
     double L = -(double)__builtin_inff();
     if (cnt1 > 0.0) {
         const double gamma = -0.691 + 10.0 * log10(sum1 / cnt1) - 10.0;
         sum = 0.0, cnt = 0.0;
-        for (int64_t j = tid; j < nblk; j += kCdThreads) {
+        for (int64_t j = tid; j < nblk; j += kGridThreads) {
             const double z = block_z(steps, j, block_len);
             const double l = -0.691 + 10.0 * log10(z);
             if (l > -70.0 && l > gamma) sum += z, cnt += 1.0;
         }
-        const double sum2 = cd_block_sum(sum, tid, red), cnt2 = cd_block_sum(cnt, tid, red);
+        const double sum2 = block_sum<kGridThreads>(sum, tid, red), cnt2 = block_sum<kGridThreads>(cnt, tid, red);
         if (cnt2 > 0.0) L = -0.691 + 10.0 * log10(sum2 / cnt2);
     }
     double pk = 0.0;
     if (end > start)
-        for (int64_t w = start / kCdSeg + tid; w <= (end - 1) / kCdSeg; w += kCdThreads) pk = fmax(pk, a.segpeak[(int64_t)b * a.W + w]);
-    red[tid] = pk;
-    __syncthreads();
-    for (int s = kCdThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
+        for (int64_t w = start / kGridSeg + tid; w <= (end - 1) / kGridSeg; w += kGridThreads) pk = fmax(pk, a.segpeak[(int64_t)b * a.W + w]);
+    pk = block_max<kGridThreads>(pk, tid, red);
     if (tid == 0) {
-        pk = red[0];
         double g = 1.0;
         if (a.gain_mode && L > -(double)__builtin_inff()) {
             g = pow(10.0, (a.target - L) / 20.0);
@@ -461,7 +379,7 @@ __global__ __launch_bounds__(kApThreads) void pcm16_kernel(const float* __restri
                                                            int16_t* __restrict__ out, int64_t ld_out, int S, int vec, int dither,
                                                            uint64_t seed) {
     const int b = blockIdx.y;
-    const int64_t len = cd_len(audio_len, b, S);
+    const int64_t len = valid_len(audio_len, b, S);
     uint64_t rs = seed + (uint64_t)b + 0x9e3779b97f4a7c15ull;           // splitmix64 of (mixed seed + b): the row's two seed words
     rs = (rs ^ (rs >> 30)) * 0xbf58476d1ce4e5b9ull;
     rs = (rs ^ (rs >> 27)) * 0x94d049bb133111ebull;
@@ -496,12 +414,12 @@ struct CondLayout {
 
 CondLayout cond_layout(int B, int S, int step) {
     CondLayout l;
-    l.W = std::max(1, (S + kCdSeg - 1) / kCdSeg);
-    l.NH = std::max(1, (S + kCdHop - 1) / kCdHop);
+    l.W = std::max(1, (S + kGridSeg - 1) / kGridSeg);
+    l.NH = std::max(1, (S + kGridHop - 1) / kGridHop);
     l.NS = S / step + 1;
     int64_t at = 0;
     l.hop = at, at += (int64_t)B * l.NH;
-    l.chunk = at, at += (int64_t)B * l.W * kCdThreads * 4;
+    l.chunk = at, at += (int64_t)B * l.W * kGridThreads * 4;
     l.seg = at, at += (int64_t)B * l.W * 4;
     l.segstep = at, at += (int64_t)B * l.W * kCdSegSteps;
     l.segpeak = at, at += (int64_t)B * l.W;
@@ -552,9 +470,9 @@ extern "C" int32_t ispk_audio_measure_f64(const float* audio, int64_t ld_audio, 
     a.hop = ws + l.hop, a.chunk = ws + l.chunk, a.seg = ws + l.seg, a.segstep = ws + l.segstep, a.segpeak = ws + l.segpeak;
     a.steps = ws + l.steps;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(cond_chunk_kernel, dim3(l.W, B), dim3(kCdThreads), 0, st, audio, audio_len, table, a);
-    hipLaunchKernelGGL(cond_meter_kernel, dim3(l.W, B), dim3(kCdThreads), 0, st, audio, audio_len, table, bounds, a);
-    hipLaunchKernelGGL(cond_gate_kernel, dim3(B), dim3(kCdThreads), 0, st, bounds, loudness, peak, gain, a);
+    hipLaunchKernelGGL(cond_chunk_kernel, dim3(l.W, B), dim3(kGridThreads), 0, st, audio, audio_len, table, a);
+    hipLaunchKernelGGL(cond_meter_kernel, dim3(l.W, B), dim3(kGridThreads), 0, st, audio, audio_len, table, bounds, a);
+    hipLaunchKernelGGL(cond_gate_kernel, dim3(B), dim3(kGridThreads), 0, st, bounds, loudness, peak, gain, a);
     return ispk_launch_status();
 }
 

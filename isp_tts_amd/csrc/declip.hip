@@ -95,19 +95,7 @@ struct DeclipArgs {
 __device__ __forceinline__ SegRec* ws_rec(const DeclipArgs& a, int b) { return reinterpret_cast<SegRec*>(a.ws + (int64_t)b * a.per_item); }
 __device__ __forceinline__ float* ws_part(const DeclipArgs& a, int b) { return reinterpret_cast<float*>(ws_rec(a, b) + a.J); }
 
-__device__ __forceinline__ float dc_finite(float x) { return fabsf(x) <= 3.402823466e+38f ? x : 0.f; }   // NaN and Inf read as 0
 __device__ __forceinline__ bool dc_skipped(const DeclipArgs& a, int b) { return a.in_flags && !(a.in_flags[b] & 1); }
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-    return v;
-}
 
 __global__ __launch_bounds__(kDcThreads) void declip_peak_kernel(const float* __restrict__ audio, int64_t ld, const int64_t* __restrict__ audio_len,
                                                                  int vec, const DeclipArgs a) {
@@ -122,13 +110,13 @@ __global__ __launch_bounds__(kDcThreads) void declip_peak_kernel(const float* __
         const int i = base + 4 * (tid + q * kDcThreads);
         if (vec && i + 4 <= n) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(row + i);
-            pk = fmaxf(pk, fmaxf(fmaxf(fabsf(dc_finite(v.x)), fabsf(dc_finite(v.y))), fmaxf(fabsf(dc_finite(v.z)), fabsf(dc_finite(v.w)))));
+            pk = fmaxf(pk, fmaxf(fmaxf(fabsf(finite_or_zero(v.x)), fabsf(finite_or_zero(v.y))), fmaxf(fabsf(finite_or_zero(v.z)), fabsf(finite_or_zero(v.w)))));
         } else {
             for (int e = 0; e < 4; ++e)
-                if (i + e < n) pk = fmaxf(pk, fabsf(dc_finite(row[i + e])));
+                if (i + e < n) pk = fmaxf(pk, fabsf(finite_or_zero(row[i + e])));
         }
     }
-    pk = wave_max_f(pk);
+    pk = wave_max(pk);
     if (tid % kWave == 0) red[tid / kWave] = pk;
     __syncthreads();
     if (tid == 0) {
@@ -144,7 +132,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_thr_kernel(const int64_t* _
     const float* part = ws_part(a, b);
     float pk = 0.f;
     for (int w = tid; w < Wn; w += kDcThreads) pk = fmaxf(pk, part[w]);
-    pk = wave_max_f(pk);
+    pk = wave_max(pk);
     if (tid % kWave == 0) red[tid / kWave] = pk;
     __syncthreads();
     if (tid == 0) {
@@ -198,7 +186,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_solve_kernel(const float* _
             if (p < s1) orow[p] = v0;
             if (p + 1 < s1) orow[p + 1] = v1;
         }
-        const float pk = wave_max_f(fmaxf(fabsf(dc_finite(v0)), fabsf(dc_finite(v1))));
+        const float pk = wave_max(fmaxf(fabsf(finite_or_zero(v0)), fabsf(finite_or_zero(v1))));
         if (lane == 0) mf[wv] = pk;
         __syncthreads();
         if (tid == 0 && s0 < n) {
@@ -209,7 +197,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_solve_kernel(const float* _
         }
     };
 
-    const float f0 = dc_finite(v0), f1 = dc_finite(v1);
+    const float f0 = finite_or_zero(v0), f1 = finite_or_zero(v1);
     const int at = thr > 0.f && (fabsf(f0) >= thr || fabsf(f1) >= thr) && !dc_skipped(a, b);
     if (tid == 0) mi[8] = 0;
     const int wave_at = __any(at);
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_solve_kernel(const float* _
     for (int k = tid; k < kDcCls; k += kDcThreads) {
         const int g = hb + k;
         float x = 0.f;
-        if (g >= 0 && g < n) x = dc_finite(row[g]);
+        if (g >= 0 && g < n) x = finite_or_zero(row[g]);
         cls[k] = x >= thr ? 1 : x <= -thr ? 2 : 0;          // (thr > 0 here; 0 outside the item)
         if (k >= kDcSide && k < kDcSide + N) win[k - kDcSide] = (double)x;
     }
@@ -283,7 +271,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_solve_kernel(const float* _
         for (int k = wv; k <= order; k += kDcWaves) {
             double s = 0.0;
             for (int i = lane; i < N - k; i += kWave) s = fma(win[i], win[i + k], s);
-            s = wave_sum_d(s);
+            s = wave_sum(s);
             if (lane == 0) rr[k] = k == 0 ? s * (1.0 + 1e-9) : s;
         }
         __syncthreads();
@@ -297,7 +285,7 @@ __global__ __launch_bounds__(kDcThreads) void declip_solve_kernel(const float* _
                 const int src = (i - lane) & (kWave - 1);
                 const bool in = lane >= 1 && lane < i;
                 const double rv = __shfl(rl, src, kWave), av = __shfl(al, src, kWave);
-                const double acc = wave_sum_d(in ? al * rv : 0.0) + __shfl(rl, i, kWave);
+                const double acc = wave_sum(in ? al * rv : 0.0) + __shfl(rl, i, kWave);
                 const double k = -acc / e;
                 if (in) al = fma(k, av, al);
                 if (lane == i) al = k;

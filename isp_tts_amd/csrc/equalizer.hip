@@ -30,22 +30,17 @@
 // only its own segment of audio and stages it in LDS before it stores, and the first launch has read everything it needs
 // before the second stores anything: out may be audio itself (same base, same row stride).
 //
-// LDS: the segment as 256 chunks of 36 floats - the meter's stride: the 16 lanes of a ds_read_b128 group then hit 16 distinct
-// bank quads (36 l mod 64 takes 16 values a multiple of 4 apart), where a stride of 32 would put them all on two.  With the
-// scan's exchange buffer that is 40 KiB a workgroup, four workgroups to a CU; the four spare floats behind chunk k hold the
+// LDS: the segment as 256 chunks of 36 floats, staged and read back by chunk_grid.h (the meter's grid; the bank reasoning is
+// there).  With the scan's exchange buffer that is 40 KiB a workgroup, four workgroups to a CU; the four spare floats behind chunk k hold the
 // entry state of section k, and the kernels are held to 128 registers so that four waves fit a SIMD as well.
 #include <math.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "chunk_grid.h"
 
 namespace {
 
-constexpr int kEqThreads = 256;
-constexpr int kEqChunk = 32;                        // samples per lane
-constexpr int kEqSeg = kEqThreads * kEqChunk;       // 8,192 samples per workgroup
-constexpr int kEqPad = kEqChunk + 4;                // LDS floats per chunk
 constexpr int kEqMaxSections = 8;
 constexpr int kEqPowers = 8;                        // A_k^(32 2^j), j = 0 .. 7
 constexpr int kEqCoef = 8;                          // doubles per section at the head of the table: b0, b1, b2, a1, a2, three unused
@@ -76,7 +71,7 @@ __device__ __forceinline__ double sos_step(const Sos& c, double x, double& s0, d
 // Inclusive scan over the workgroup's lanes of S_c = A^32 S_(c-1) + v_c (Hillis-Steele, in registers; st is the exchange
 // buffer, pw the section's eight 2 x 2 powers: uniform addresses, scalar loads).  Ends with every lane's result also in
 // st[.][tid], after a barrier.
-__device__ __forceinline__ void eq_scan(double (*st)[kEqThreads], const double* __restrict__ pw, int tid, double& v0, double& v1) {
+__device__ __forceinline__ void eq_scan(double (*st)[kGridThreads], const double* __restrict__ pw, int tid, double& v0, double& v1) {
 #pragma unroll 1
     for (int j = 0; j < kEqPowers; ++j) {
         st[0][tid] = v0, st[1][tid] = v1;
@@ -94,42 +89,16 @@ __device__ __forceinline__ void eq_scan(double (*st)[kEqThreads], const double* 
     __syncthreads();
 }
 
-// xs[chunk c][k] = x(base + 32 c + k), 0 at or past len.  Nothing at or past len is read.
-__device__ __forceinline__ void eq_stage(float* xs, const float* __restrict__ row, int64_t base, int64_t len, int vec, int tid) {
-    for (int g = tid; g < kEqSeg / 4; g += kEqThreads) {
-        const int64_t i = base + 4 * (int64_t)g;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec && i + 4 <= len) {
-            v = *reinterpret_cast<const f32x4*>(row + i);
-        } else {
-            if (i < len) v.x = row[i];
-            if (i + 1 < len) v.y = row[i + 1];
-            if (i + 2 < len) v.z = row[i + 2];
-            if (i + 3 < len) v.w = row[i + 3];
-        }
-        *reinterpret_cast<f32x4*>(xs + (g >> 3) * kEqPad + (g & 7) * 4) = v;
-    }
-}
-
-__device__ __forceinline__ void eq_load_chunk(const float* xs, int tid, double x[kEqChunk]) {
-    const float* p = xs + tid * kEqPad;
-#pragma unroll
-    for (int k4 = 0; k4 < kEqChunk / 4; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(p + 4 * k4);
-        x[4 * k4] = (double)v.x, x[4 * k4 + 1] = (double)v.y, x[4 * k4 + 2] = (double)v.z, x[4 * k4 + 3] = (double)v.w;
-    }
-}
-
 // One section over the segment: x holds the lane's 32 inputs and, with `rerun`, its 32 outputs afterwards.  (e0, e1) is the
 // section's state at the segment's first sample.  Returns the state behind the segment's last sample in (f0, f1) of the last
 // lane.  Ends with a barrier behind the last read of st.
-__device__ __forceinline__ void eq_section(const double* __restrict__ tab, int n, int k, double (*st)[kEqThreads], int tid,
-                                           double e0, double e1, bool rerun, double x[kEqChunk], double& f0, double& f1) {
+__device__ __forceinline__ void eq_section(const double* __restrict__ tab, int n, int k, double (*st)[kGridThreads], int tid,
+                                           double e0, double e1, bool rerun, double x[kGridChunk], double& f0, double& f1) {
     const Sos c = sos_load(tab, k);
     const double* pw = tab + kEqCoef * n + 4 * kEqPowers * k;
     double v0 = 0.0, v1 = 0.0;
 #pragma unroll
-    for (int i = 0; i < kEqChunk; ++i) sos_step(c, x[i], v0, v1);
+    for (int i = 0; i < kGridChunk; ++i) sos_step(c, x[i], v0, v1);
     if (tid == 0) {                                                     // the segment's entry state, carried through chunk 0
         v0 = fma(pw[1], e1, fma(pw[0], e0, v0));
         v1 = fma(pw[3], e1, fma(pw[2], e0, v1));
@@ -141,13 +110,8 @@ __device__ __forceinline__ void eq_section(const double* __restrict__ tab, int n
     __syncthreads();                                                    // (the next section's scan writes st)
     if (rerun) {
 #pragma unroll
-        for (int i = 0; i < kEqChunk; ++i) x[i] = sos_step(c, x[i], s0, s1);
+        for (int i = 0; i < kGridChunk; ++i) x[i] = sos_step(c, x[i], s0, s1);
     }
-}
-
-__device__ __forceinline__ int64_t eq_len(const int64_t* __restrict__ audio_len, int b, int S) {
-    const int64_t len = audio_len[b];
-    return (len < 0 || len > S) ? 0 : len;
 }
 
 struct EqArgs {
@@ -156,37 +120,37 @@ struct EqArgs {
     double* seg;                                    // [B][W][2 n]: every segment's final joint state from zero entry
 };
 
-__global__ __launch_bounds__(kEqThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void eq_state_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
-                                                              const double* __restrict__ tab, const EqArgs a) {
-    __shared__ __attribute__((aligned(16))) float xs[kEqThreads * kEqPad];
-    __shared__ double st[2][kEqThreads];
+__global__ __launch_bounds__(kGridThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void eq_state_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
+                                                                const double* __restrict__ tab, const EqArgs a) {
+    __shared__ __attribute__((aligned(16))) float xs[kGridThreads * kGridPad];
+    __shared__ double st[2][kGridThreads];
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int64_t len = eq_len(audio_len, b, a.S);
-    const int64_t segb = (int64_t)w * kEqSeg;
+    const int64_t len = valid_len(audio_len, b, a.S);
+    const int64_t segb = (int64_t)w * kGridSeg;
     if (segb >= len) return;                                            // (uniform) no later segment holds a sample
-    eq_stage(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
+    stage_chunks(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
     __syncthreads();
-    double x[kEqChunk];
-    eq_load_chunk(xs, tid, x);
+    double x[kGridChunk];
+    load_chunk(xs, tid, x);
     double* g = a.seg + ((int64_t)b * a.W + w) * 2 * a.n;
 #pragma unroll 1
     for (int k = 0; k < a.n; ++k) {
         double f0, f1;
         eq_section(tab, a.n, k, st, tid, 0.0, 0.0, k + 1 < a.n, x, f0, f1);
-        if (tid == kEqThreads - 1) g[2 * k] = f0, g[2 * k + 1] = f1;
+        if (tid == kGridThreads - 1) g[2 * k] = f0, g[2 * k + 1] = f1;
     }
 }
 
-__global__ __launch_bounds__(kEqThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void eq_apply_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
-                                                              const double* __restrict__ tab, float* __restrict__ out,
-                                                              int64_t* __restrict__ out_len, const EqArgs a) {
-    __shared__ __attribute__((aligned(16))) float xs[kEqThreads * kEqPad];
-    __shared__ double st[2][kEqThreads];
+__global__ __launch_bounds__(kGridThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void eq_apply_kernel(const float* __restrict__ audio, const int64_t* __restrict__ audio_len,
+                                                                const double* __restrict__ tab, float* __restrict__ out,
+                                                                int64_t* __restrict__ out_len, const EqArgs a) {
+    __shared__ __attribute__((aligned(16))) float xs[kGridThreads * kGridPad];
+    __shared__ double st[2][kGridThreads];
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int64_t len = eq_len(audio_len, b, a.S);
-    const int64_t segb = (int64_t)w * kEqSeg;
+    const int64_t len = valid_len(audio_len, b, a.S);
+    const int64_t segb = (int64_t)w * kGridSeg;
     if (w == 0 && tid == 0 && out_len) out_len[b] = len;
-    float* xo = xs + tid * kEqPad;
+    float* xo = xs + tid * kGridPad;
     if (segb < len) {                                                   // (uniform)
         // the joint state at this segment's first sample: E <- A^8192 E + (segment u from zero), u = 0 .. w - 1, row i by lane i,
         // back and forth between the two rows of st; then section k's pair into the four spare floats behind chunk k of xs
@@ -205,20 +169,20 @@ __global__ __launch_bounds__(kEqThreads) __attribute__((amdgpu_waves_per_eu(4, 4
             cur ^= 1;
             __syncthreads();
         }
-        if (tid < n2) reinterpret_cast<double*>(xs + (tid >> 1) * kEqPad + kEqChunk)[tid & 1] = st[cur][tid];
-        eq_stage(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
+        if (tid < n2) reinterpret_cast<double*>(xs + (tid >> 1) * kGridPad + kGridChunk)[tid & 1] = st[cur][tid];
+        stage_chunks(xs, audio + (int64_t)b * a.ld, segb, len, a.vec, tid);
         __syncthreads();
-        double x[kEqChunk];
-        eq_load_chunk(xs, tid, x);
+        double x[kGridChunk];
+        load_chunk(xs, tid, x);
 #pragma unroll 1
         for (int k = 0; k < a.n; ++k) {
-            const double* e = reinterpret_cast<const double*>(xs + k * kEqPad + kEqChunk);
+            const double* e = reinterpret_cast<const double*>(xs + k * kGridPad + kGridChunk);
             double f0, f1;
             eq_section(tab, a.n, k, st, tid, e[0], e[1], true, x, f0, f1);
         }
-        const int64_t cb = segb + (int64_t)tid * kEqChunk;
+        const int64_t cb = segb + (int64_t)tid * kGridChunk;
 #pragma unroll
-        for (int k4 = 0; k4 < kEqChunk / 4; ++k4) {
+        for (int k4 = 0; k4 < kGridChunk / 4; ++k4) {
             f32x4 v;
             v.x = cb + 4 * k4 < len ? (float)x[4 * k4] : 0.f;
             v.y = cb + 4 * k4 + 1 < len ? (float)x[4 * k4 + 1] : 0.f;
@@ -229,14 +193,14 @@ __global__ __launch_bounds__(kEqThreads) __attribute__((amdgpu_waves_per_eu(4, 4
     } else {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int k4 = 0; k4 < kEqChunk / 4; ++k4) *reinterpret_cast<f32x4*>(xo + 4 * k4) = z;
+        for (int k4 = 0; k4 < kGridChunk / 4; ++k4) *reinterpret_cast<f32x4*>(xo + 4 * k4) = z;
     }
     __syncthreads();
     float* o = out + (int64_t)b * a.ld_out;
-    for (int g = tid; g < kEqSeg / 4; g += kEqThreads) {
+    for (int g = tid; g < kGridSeg / 4; g += kGridThreads) {
         const int64_t i = segb + 4 * (int64_t)g;
         if (i >= a.S) break;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(xs + (g >> 3) * kEqPad + (g & 7) * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xs + (g >> 3) * kGridPad + (g & 7) * 4);
         if (a.vec_out && i + 4 <= a.S) {
             *reinterpret_cast<f32x4*>(o + i) = v;
         } else {
@@ -250,7 +214,7 @@ __global__ __launch_bounds__(kEqThreads) __attribute__((amdgpu_waves_per_eu(4, 4
 
 }  // namespace
 
-extern "C" int32_t ispk_equalize_segment_samples(void) { return kEqSeg; }
+extern "C" int32_t ispk_equalize_segment_samples(void) { return kGridSeg; }
 
 extern "C" int32_t ispk_equalize_f32(const float* audio, int64_t ld_audio, const int64_t* audio_len, const double* table,
                                      int64_t table_doubles, int32_t sections, float* out, int64_t ld_out, int64_t* out_len,
@@ -272,7 +236,7 @@ extern "C" int32_t ispk_equalize_f32(const float* audio, int64_t ld_audio, const
         ISPK_REQUIRE(a1 <= o0 || o1 <= a0, ISPK_E_SHAPE,
                      "ispk_equalize_f32: out overlaps audio without being audio (same base and row stride)");
     }
-    const int W = std::max(1, (S + kEqSeg - 1) / kEqSeg);
+    const int W = std::max(1, (S + kGridSeg - 1) / kGridSeg);
     const int64_t need = (int64_t)B * W * 2 * sections;
     ISPK_REQUIRE(workspace_doubles >= need && ispk_aligned(workspace, 8) && ispk_aligned(table, 8), ISPK_E_ALIGN,
                  "ispk_equalize_f32: the workspace needs %lld doubles at an 8-byte boundary, got %lld", (long long)need,
@@ -282,7 +246,7 @@ extern "C" int32_t ispk_equalize_f32(const float* audio, int64_t ld_audio, const
     a.vec = ld_audio % 4 == 0 && ispk_aligned(audio, 16);
     a.vec_out = ld_out % 4 == 0 && ispk_aligned(out, 16);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (W > 1) hipLaunchKernelGGL(eq_state_kernel, dim3(W - 1, B), dim3(kEqThreads), 0, st, audio, audio_len, table, a);
-    hipLaunchKernelGGL(eq_apply_kernel, dim3(W, B), dim3(kEqThreads), 0, st, audio, audio_len, table, out, out_len, a);
+    if (W > 1) hipLaunchKernelGGL(eq_state_kernel, dim3(W - 1, B), dim3(kGridThreads), 0, st, audio, audio_len, table, a);
+    hipLaunchKernelGGL(eq_apply_kernel, dim3(W, B), dim3(kGridThreads), 0, st, audio, audio_len, table, out, out_len, a);
     return ispk_launch_status();
 }

@@ -61,12 +61,6 @@ struct LimArgs {
 
 __host__ __device__ constexpr int lim_halo(int L) { return (2 * L + 3) & ~3; }
 
-__device__ __forceinline__ float lim_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(kLimThreads) void limit_kernel(const LimArgs a) {
 #pragma clang fp contract(off)   // g x is the rounded product (cond_apply_kernel's); every FMA below is written as one
     extern __shared__ __attribute__((aligned(16))) unsigned char lim_lds[];
@@ -188,7 +182,7 @@ __global__ __launch_bounds__(kLimThreads) void limit_kernel(const LimArgs a) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(bufA + Hx + 4 * (u * kLimThreads + tid));
         y[u][0] = t.x, y[u][1] = t.y, y[u][2] = t.z, y[u][3] = t.w;
     }
-    pk = lim_wave_max(pk);
+    pk = wave_max(pk);
     if ((tid & 63) == 0) red[tid >> 6] = pk;
     const int any = __syncthreads_or(limited);                             // (also: bufB is written, bufA and red are read)
     if (tid == 0) {
@@ -289,7 +283,7 @@ __global__ __launch_bounds__(kLimThreads) void limit_kernel(const LimArgs a) {
         }
     }
     if (!any || !a.reduction) return;                                      // (uniform) untouched: the 1.0f of the memset stands
-    lowest = -lim_wave_max(-lowest);
+    lowest = -wave_max(-lowest);
     if ((tid & 63) == 0) red[4 + (tid >> 6)] = lowest;
     __syncthreads();
     if (tid == 0) {

@@ -5,8 +5,8 @@
 // periodic Hann, center = true with reflect padding, F = 1 + n / 256 frames.
 //
 // The profile, four launches, no atomics:
-//   nz_hop_kernel      grid (ceil(S / 8192), B): the float64 hop sums in seg_hop_kernel's order (segment.hip, which has it from
-//                      condition.hip), so the trim frames are the conditioner's and the segmenter's bit for bit.
+//   hop_sums_kernel    chunk_grid.h's: grid (ceil(S / 8192), B), the float64 hop sums into the item's workspace.  The trim
+//                      frames are the header's one definition, so they are the conditioner's and the segmenter's bit for bit.
 //   nz_plan_kernel     grid (B), 1,024 lanes.  p_t and their max, thr; every lane counts the active frames of its strip of
 //                      consecutive frames, an exclusive scan turns that into cum[t] = the active frames before t; STFT frame f
 //                      (trim frame t = f - 2) is a noise frame when 2 <= f <= n / 256 - 2 and cum[min(T, t + guard + 1)] ==
@@ -15,7 +15,7 @@
 //                      its noise frames in order, stages samples [4096 w - 512, 4096 w + 4352) in LDS (a noise frame lies wholly
 //                      inside the item: no reflection) and runs them four at a time through fft.h as screen_tile_kernel does;
 //                      lane k adds |X_f[k]|^2 (fp32) in frame order into its float64 sum, the tile's partial [513].  LDS is
-//                      screen.hip's reduced layout (no synthesis side): 64,512 B, two workgroups per CU.
+//                      stft_tile.h's analysis-only layout (no synthesis side): 64,512 B, two workgroups per CU.
 //   nz_item_kernel     grid (B): noise[k] = (the partials in tile order) / noise_frames, zeros below min_noise_frames.
 //
 // The reduce, one launch:
@@ -46,13 +46,13 @@
 // gfx950 resources (csrc/resource_report.py noise.hip; no spills, no scratch):
 //   nz_reduce_kernel   58 VGPRs, LDS 141,552 B dynamic (one workgroup per CU)
 //   nz_tile_kernel     48 VGPRs, LDS 64,512 B dynamic + 80 B static (two workgroups per CU)
-//   nz_hop_kernel      22 VGPRs, LDS 38,912 B        nz_plan_kernel     18 VGPRs, LDS 12,288 B
+//   hop_sums_kernel    22 VGPRs, LDS 38,912 B        nz_plan_kernel     18 VGPRs, LDS 12,288 B
 //   nz_item_kernel     14 VGPRs, no LDS
 #include <math.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "chunk_grid.h"
 #include "stft_tile.h"
 
 namespace {
@@ -71,17 +71,9 @@ static_assert(kNzRow % 4 == 0 && kNzRow >= kBins, "the frame slots behind the ro
 static_assert(kNzReduceLds == 141552 && kNzReduceLds <= 160 * 1024, "the header above and DESIGN.md 4.32 quote this");
 
 // ------------------------------------------------------------------------------------------------------------ profile
-constexpr int kNzHopThreads = 256;
-constexpr int kNzChunk = 32;                        // samples per lane of the hop pass
-constexpr int kNzSeg = kNzHopThreads * kNzChunk;    // 8,192 samples per workgroup
-constexpr int kNzPad = kNzChunk + 4;                // LDS floats per chunk (condition.hip: 16 lanes hit 16 distinct bank quads)
-constexpr int kNzHopChunks = kHop / kNzChunk;       // 8 lanes per hop
-constexpr int kNzSegHops = kNzSeg / kHop;           // 32
 constexpr int kNzPlanThreads = 1024;
-constexpr int kNzStage = kTile + kNfft - kHop;      // 4,864 staged samples: 16 frames of 1024 every 256
-constexpr size_t kNzTileLds = sizeof(cf) * (kTw + kGroups * kHalf) + sizeof(float) * (kNfft + kNzStage + kGroups * kNfft);
-static_assert(kNzStage % 4 == 0, "float4 staging; the pong slots behind the staged samples are float2");
-static_assert(kNzTileLds == 64512, "screen.hip's reduced layout");
+static_assert(kGridHop == kHop && kGridFrame == kNfft, "a trim frame t is the STFT frame t + 2: one hop, one frame length");
+static_assert(kAnalysisLds == 64512, "the header above quotes this");
 
 struct NzLayout {
     int NH, W;                                      // hops an item can have; tiles of 16 STFT frames
@@ -113,75 +105,6 @@ __device__ __forceinline__ int* nz_mask(const NzArgs& a, int b) { return reinter
 __device__ __forceinline__ double* nz_part(const NzArgs& a, int b) { return nz_hop(a, b) + a.part; }
 __device__ __forceinline__ int* nz_count(const NzArgs& a, int b) { return reinterpret_cast<int*>(nz_hop(a, b) + a.count); }
 
-__global__ __launch_bounds__(kNzHopThreads) void nz_hop_kernel(const float* __restrict__ audio, int64_t ld, const int64_t* __restrict__ audio_len,
-                                                               int vec, const NzArgs a) {
-    __shared__ __attribute__((aligned(16))) float xs[kNzHopThreads * kNzPad];
-    __shared__ double part[kNzHopThreads];
-    const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int len = valid_len(audio_len, b, a.S), base = w * kNzSeg;
-    if (base >= len) return;                                            // (uniform) no frame of the item reads a hop from here
-    const float* row = audio + (int64_t)b * ld;
-    for (int g = tid; g < kNzSeg / 4; g += kNzHopThreads) {             // xs[chunk c][k] = x(base + 32 c + k), 0 at or past len
-        const int i = base + 4 * g;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec && i + 4 <= len) {
-            v = *reinterpret_cast<const f32x4*>(row + i);
-        } else {
-            if (i < len) v.x = row[i];
-            if (i + 1 < len) v.y = row[i + 1];
-            if (i + 2 < len) v.z = row[i + 2];
-            if (i + 3 < len) v.w = row[i + 3];
-        }
-        *reinterpret_cast<f32x4*>(xs + (g >> 3) * kNzPad + (g & 7) * 4) = v;
-    }
-    __syncthreads();
-    double e = 0.0;
-    const float* x = xs + tid * kNzPad;
-#pragma unroll
-    for (int k4 = 0; k4 < kNzChunk / 4; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * k4);
-        const double xd[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e = fma(xd[q], xd[q], e);
-    }
-    part[tid] = e;
-    __syncthreads();
-    if (tid < kNzSegHops) {
-        const int h = w * kNzSegHops + tid;
-        if (h * kHop < len) {                                           // h < T <= NH
-            double t = 0.0;
-            for (int q = 0; q < kNzHopChunks; ++q) t += part[tid * kNzHopChunks + q];
-            nz_hop(a, b)[h] = t;
-        }
-    }
-}
-
-__device__ __forceinline__ double nz_frame_power(const double* hop, int t, int nh) {
-    double p = hop[t];
-    if (t + 1 < nh) p += hop[t + 1];
-    if (t + 2 < nh) p += hop[t + 2];
-    if (t + 3 < nh) p += hop[t + 3];
-    return p / (double)kNfft;
-}
-
-// Exclusive sum-scan over the workgroup's lanes (Hillis-Steele in LDS); `total` is the sum over all lanes.  Ends with a barrier.
-__device__ __forceinline__ int nz_scan(int v, int tid, int* buf, int& total) {
-#pragma unroll 1
-    for (int k = 0; (1 << k) < kNzPlanThreads; ++k) {
-        buf[tid] = v;
-        __syncthreads();
-        const int src = tid - (1 << k);
-        if (src >= 0) v += buf[src];
-        __syncthreads();
-    }
-    buf[tid] = v;
-    __syncthreads();
-    const int excl = tid ? buf[tid - 1] : 0;
-    total = buf[kNzPlanThreads - 1];
-    __syncthreads();
-    return excl;
-}
-
 __global__ __launch_bounds__(kNzPlanThreads) void nz_plan_kernel(const int64_t* __restrict__ audio_len, const NzArgs a) {
     constexpr int kNT = kNzPlanThreads;
     __shared__ double red[kNT];
@@ -194,24 +117,18 @@ __global__ __launch_bounds__(kNzPlanThreads) void nz_plan_kernel(const int64_t* 
     int* mask = nz_mask(a, b);
 
     double mx = 0.0;
-    for (int t = tid; t < T; t += kNT) mx = fmax(mx, nz_frame_power(hop, t, T));
-    red[tid] = mx;
-    __syncthreads();
-    for (int s = kNT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double thr = a.ref_mode == 0 ? red[0] * a.factor : a.ref * a.factor;
+    for (int t = tid; t < T; t += kNT) mx = fmax(mx, frame_power(hop, t, T));
+    const double thr = frame_threshold<kNT>(mx, a.ref_mode == 0, a.ref, a.factor, tid, red);
 
     // cum[t] = the active frames before t, t <= T: a strip of consecutive frames per lane
     const int L = (T + kNT - 1) / kNT, t0 = min(T, tid * L), t1 = min(T, t0 + L);
     int act = 0;
-    for (int t = t0; t < t1; ++t) act += nz_frame_power(hop, t, T) > thr;
+    for (int t = t0; t < t1; ++t) act += frame_power(hop, t, T) > thr;
     int total;
-    int before = nz_scan(act, tid, ired, total);
+    int before = block_scan_excl<false, kNT>(act, 0, tid, ired, total);
     for (int t = t0; t < t1; ++t) {
         cum[t] = before;
-        before += nz_frame_power(hop, t, T) > thr;
+        before += frame_power(hop, t, T) > thr;
     }
     if (tid == 0) cum[T] = total;
     __syncthreads();                                                    // cum is written (this workgroup's own stores)
@@ -245,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void nz_tile_kernel(const float* __restri
                                                            const float* __restrict__ tables, int vec, const NzArgs a) {
     extern __shared__ float4 lds_raw[];
     __shared__ int list[kSegs], listed;
-    const TileLds tile = carve_tile(lds_raw, kNzStage);     // four slots behind the staged samples: the groups' pong buffers
+    const TileLds tile = carve_tile(lds_raw, kAnalysisStage);     // four slots behind the staged samples: the groups' pong buffers
     float* xs = tile.win + kNfft;
 
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y, g = tid / kGT, lt = tid % kGT;
@@ -269,20 +186,7 @@ __global__ __launch_bounds__(kThreads) void nz_tile_kernel(const float* __restri
     }
 
     const int base = w * kTile - kHalf;                     // frame f reads [256 f - 512, 256 f + 512); a multiple of 4
-    const float* row = audio + (int64_t)b * ld;
-    for (int q = tid; q < kNzStage / 4; q += kThreads) {    // xs[j] = x(base + j), 0 outside [0, n)
-        const int i = base + 4 * q;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec && i >= 0 && i + 4 <= n) {
-            v = *reinterpret_cast<const f32x4*>(row + i);
-        } else {
-            if (i >= 0 && i < n) v.x = row[i];
-            if (i + 1 >= 0 && i + 1 < n) v.y = row[i + 1];
-            if (i + 2 >= 0 && i + 2 < n) v.z = row[i + 2];
-            if (i + 3 >= 0 && i + 3 < n) v.w = row[i + 3];
-        }
-        *reinterpret_cast<f32x4*>(xs + 4 * q) = v;
-    }
+    stage_flat(xs, audio + (int64_t)b * ld, base, n, kAnalysisStage, vec, tid);
     load_tables(tile.tw, tile.win, tables, tid);
     __syncthreads();
 
@@ -325,18 +229,6 @@ __global__ __launch_bounds__(kThreads) void nz_item_kernel(const int64_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------ reduce
-// A[m] = the frame's samples 2 m, 2 m + 1 times the window: x[r(256 f - 512 + j)], r the reflection at 0 and n - 1 (n >= 513 and
-// 0 <= f < F keep every index inside [0, n))
-__device__ __forceinline__ void nz_gather(cf* A, const float* win, const float* __restrict__ xrow, int f, int n, int lt) {
-    const int i0 = f * kHop - kHalf;
-    for (int m = lt; m < kHalf; m += kGT) {
-        int ia = i0 + 2 * m, ib = ia + 1;
-        ia = ia < 0 ? -ia : ia >= n ? 2 * (n - 1) - ia : ia;
-        ib = ib < 0 ? -ib : ib >= n ? 2 * (n - 1) - ib : ib;
-        A[m] = make_float2(xrow[ia] * win[2 * m], xrow[ib] * win[2 * m + 1]);
-    }
-}
-
 __device__ __forceinline__ float nz_power(cf X) { return fmaf(X.x, X.x, X.y * X.y); }
 
 // row[k] = max(1 - nb[k] / |X[k]|^2, g_min), g_min where |X[k]|^2 = 0 (IEEE division; -inf and NaN fall to the floor), k <= 512,
@@ -400,7 +292,7 @@ __global__ void __launch_bounds__(kThreads) nz_reduce_kernel(const float* __rest
             const int s = g < 2 ? g - 2 : nf + g - 2;
             const int f = f_lo + s;
             const bool live = (g < 2 ? -s <= Tt : s - nf < Tt) && f >= 0 && f < F;
-            if (live) nz_gather(A, tile.win, xrow, f, n, lt);
+            if (live) gather_reflected(A, tile.win, xrow, f, n, lt);
             else clear_frame(A, lt);
             __syncthreads();
             fft<false, kGT, kTw>(A, slot(g), kHalf, lt, tile.tw);
@@ -410,7 +302,7 @@ __global__ void __launch_bounds__(kThreads) nz_reduce_kernel(const float* __rest
         }
         for (int r = 0; r * kGroups < nf; ++r) {                         // analysis: Z of every frame into its slot
             const int fs = r * kGroups + g;                              // fs >= nf: transformed, never read
-            if (fs < nf) nz_gather(A, tile.win, xrow, f_lo + fs, n, lt);
+            if (fs < nf) gather_reflected(A, tile.win, xrow, f_lo + fs, n, lt);
             else clear_frame(A, lt);
             __syncthreads();                                             // (also: the halo's rows are written, its slots free)
             fft<false, kGT, kTw>(A, slot(fs), kHalf, lt, tile.tw);
@@ -500,9 +392,10 @@ extern "C" int32_t ispk_noise_profile_f64(const float* audio, int64_t ld_audio, 
     a.noise = noise, a.noise_frames = noise_frames, a.frames = frames, a.flags = flags;
     const int vec = ld_audio % 4 == 0 && ispk_aligned(audio, 16);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(nz_hop_kernel, dim3((S + kNzSeg - 1) / kNzSeg, B), dim3(kNzHopThreads), 0, st, audio, ld_audio, audio_len, vec, a);
+    hipLaunchKernelGGL(hop_sums_kernel<>, dim3((S + kGridSeg - 1) / kGridSeg, B), dim3(kGridThreads), 0, st, audio, ld_audio, audio_len, S,
+                       vec, a.ws, a.per_item);
     hipLaunchKernelGGL(nz_plan_kernel, dim3(B), dim3(kNzPlanThreads), 0, st, audio_len, a);
-    hipLaunchKernelGGL(nz_tile_kernel, dim3(l.W, B), dim3(kThreads), kNzTileLds, st, audio, ld_audio, audio_len, tables, vec, a);
+    hipLaunchKernelGGL(nz_tile_kernel, dim3(l.W, B), dim3(kThreads), kAnalysisLds, st, audio, ld_audio, audio_len, tables, vec, a);
     hipLaunchKernelGGL(nz_item_kernel, dim3(B), dim3(kThreads), 0, st, audio_len, a);
     return ispk_launch_status();
 }

@@ -26,8 +26,9 @@
 // tiles in order (staged 256 at a time in LDS, lane 0 walks), joining a tail to the next head of its class; with kZero a run
 // that starts at sample 0 or ends at n - 1 is padding and is left out.
 //
-// LDS of screen_tile_kernel: 8 KB twiddles, 16 KB ping, 4 KB window, 19 KB of staged samples, 16 KB pong (one 4 KB slot per
-// group: no synthesis side, so none of stft_tile.h's 80 KB of frame slots) = 64,512 B dynamic, two workgroups (16 waves) per CU.
+// LDS of screen_tile_kernel (stft_tile.h's analysis-only layout, kAnalysisLds): 8 KB twiddles, 16 KB ping, 4 KB window, 19 KB
+// of staged samples, 16 KB pong (one 4 KB slot per group: no synthesis side, so none of the 80 KB of frame slots) = 64,512 B
+// dynamic, two workgroups (16 waves) per CU.
 // Bits.  Every sum runs in an order fixed by the item's length; integers and maxima do not depend on the order; no atomics.  An
 // item's results depend on that item alone - not on B, S, the row stride, the alignment or what lies behind its length.
 //
@@ -44,17 +45,14 @@
 
 namespace {
 
-constexpr int kScHalo = kNfft - kHop;                      // 768: what the tile's last frame reads past the tile
-constexpr int kScStage = kTile + kScHalo;                  // 4,864 staged samples
 constexpr int kScStrip = kTile / kThreads;                 // 8 consecutive samples per lane
 constexpr int kScWaves = kThreads / kWave;                 // 8
 constexpr int kScChunk = 256;                              // tile summaries staged in LDS for the walk
 constexpr int kScFlagThreads = 256;
 constexpr int kScMaxSamples = 1 << 24;                     // CONDITION_MAX_SAMPLES
 constexpr int kScTileWords = kBins + 3 + 4 + 4;            // per tile, in 8-byte words: partial [513], TileStat, two RunRec
-constexpr size_t kScLds = sizeof(cf) * (kTw + kGroups * kHalf) + sizeof(float) * (kNfft + kScStage + kGroups * kNfft);
-static_assert(kScStrip == 8 && kScStage % 4 == 0, "two float4 per lane; the pong slots behind the staged samples are float2");
-static_assert(kScLds == 64512, "the resource line above and DESIGN.md 4.31 quote this");
+static_assert(kScStrip == 8, "two float4 per lane");
+static_assert(kAnalysisLds == 64512, "the resource line above and DESIGN.md 4.31 quote this");
 
 struct TileStat {
     double sum, sumsq;
@@ -98,13 +96,13 @@ __device__ __forceinline__ float* ws_thr(const ScreenArgs& a, int b) { return re
 
 __device__ __forceinline__ int sc_frames(int n) { return n >= kNfft ? (n - kNfft) / kHop + 1 : 0; }
 __device__ __forceinline__ float sc_finite(float x, int& bad) {
-    const bool ok = fabsf(x) <= 3.402823466e+38f;           // false for NaN and the infinities
-    bad += !ok;
-    return ok ? x : 0.f;
+    bad += !is_finite(x);
+    return finite_or_zero(x);
 }
 
 // xs[j] = x(base + j) for j < count (a multiple of 4), 0 at or past n, a non-finite sample as 0; returns the lane's number of
-// non-finite samples among j < kTile.  base is a multiple of 4, so a row that allows float4 loads allows them here.
+// non-finite samples among j < kTile.  base is a multiple of 4, so a row that allows float4 loads allows them here.  (Not
+// stft_tile.h's stage_flat: base is never negative here, and the tests of i >= 0 that a negative base needs do not fold away.)
 __device__ __forceinline__ int sc_stage(float* xs, const float* __restrict__ row, int base, int n, int count, int vec, int tid) {
     int bad = 0;
     for (int g = tid; g < count / 4; g += kThreads) {
@@ -271,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void screen_tile_kernel(const float* __re
     __shared__ double red_d[2 * kScWaves];
     __shared__ float red_f[kScWaves];
     __shared__ int red_i[kScWaves], sh[48];
-    const TileLds tile = carve_tile(lds_raw, kScStage);     // four slots behind the staged samples: the groups' pong buffers
+    const TileLds tile = carve_tile(lds_raw, kAnalysisStage);     // four slots behind the staged samples: the groups' pong buffers
     float* xs = tile.win + kNfft;
 
     const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y, g = tid / kGT, lt = tid % kGT;
@@ -280,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void screen_tile_kernel(const float* __re
     const int m = min(kTile, n - base);
     const int F = sc_frames(n), f_lo = w * kSegs, nf = (a.parts & 2) ? min(F - f_lo, kSegs) : 0;
 
-    int bad = sc_stage(xs, audio + (int64_t)b * ld, base, n, nf > 0 ? kScStage : kTile, vec, tid);
+    int bad = sc_stage(xs, audio + (int64_t)b * ld, base, n, nf > 0 ? kAnalysisStage : kTile, vec, tid);
     if (nf > 0) load_tables(tile.tw, tile.win, tables, tid);
     __syncthreads();
 
@@ -509,7 +507,7 @@ extern "C" int32_t ispk_screen_f64(const float* audio, int64_t ld_audio, const i
     const int vec = ld_audio % 4 == 0 && ispk_aligned(audio, 16);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const unsigned W = (unsigned)((S + kTile - 1) / kTile);
-    if (W) hipLaunchKernelGGL(screen_tile_kernel, dim3(W, B), dim3(kThreads), kScLds, st, audio, ld_audio, audio_len, tables, vec, a);
+    if (W) hipLaunchKernelGGL(screen_tile_kernel, dim3(W, B), dim3(kThreads), kAnalysisLds, st, audio, ld_audio, audio_len, tables, vec, a);
     hipLaunchKernelGGL(screen_item_kernel, dim3(B), dim3(kThreads), 0, st, audio_len, a);
     if (W && (parts & 1)) hipLaunchKernelGGL(screen_rail_kernel, dim3(W, B), dim3(kThreads), 0, st, audio, ld_audio, audio_len, vec, a);
     hipLaunchKernelGGL(screen_flag_kernel, dim3(B), dim3(kScFlagThreads), 0, st, audio_len, a);

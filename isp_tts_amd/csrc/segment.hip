@@ -1,8 +1,8 @@
 // Segmenter (no counterpart in the reference, whose recordings arrive as utterances): long recordings cut into utterances at
 // their pauses and gathered into a padded batch, on a padded mono batch fp32 [B][S] with int64 audio_len [B] (a length below 0
 // or above S counts as 0).  include/ispk.h has the definitions; in short, all integers, `/` floors:
-//   Frames      the conditioner's trim frames (condition.hip): hop sums h_t of 256 samples in float64, p_t = (((h_t + h_t+1) +
-//               h_t+2) + h_t+3) / 1024 over T = ceil(len / 256) frames, active when p_t > thr.
+//   Frames      the trim frames of chunk_grid.h, which the conditioner and the noise profile share: hop sums h_t of 256 samples
+//               in float64, p_t = (((h_t + h_t+1) + h_t+2) + h_t+3) / 1024 over T = ceil(len / 256) frames, active when p_t > thr.
 //   Ends        first / last from the first and last active frames f, l as the conditioner's start / end with pad_frames = pad.
 //   Candidates  every maximal inactive run u .. v-1 strictly between f and l of at least min_silence_frames frames:
 //               M = 256 ((u + 3 + v) / 2), e = min(256 (u + 3 + pad), M), s = max(256 (v - pad), M).
@@ -10,9 +10,8 @@
 //   Levels      per stored segment the counts and float64 means of p_t over its active / inactive frames.
 //   Gather      the stored segments without a dropped flag, in (item, index) order, copied bit for bit into rows.
 //
-//   seg_hop_kernel     grid (ceil(S / 8192), B).  Stages 8,192 samples in LDS (float4 loads when the row base is aligned, zeros
-//                      past len); every lane sums the squares of its 32 samples in sample order, a hop is eight lanes in lane
-//                      order - cond_chunk_kernel's order, so the hop sums have its bits.  A workgroup at or past len returns.
+//   hop_sums_kernel    chunk_grid.h's: grid (ceil(S / 8192), B), the hop sums into the item's workspace.  Its staging and the
+//                      order of its sums are the header's, so the conditioner's hop sums have the same bits.
 //   seg_plan_kernel    grid (B), one workgroup of 1,024 lanes per item (its passes are bound by the latency of one CU's loads:
 //                      the more of them in flight, the better).  p_t into the workspace and their max; f and l; then over
 //                      [f, l] in chunks of 8,192 frames (8 consecutive frames a lane): an exclusive max-scan hands every lane
@@ -28,17 +27,11 @@
 // Every sum runs in an order that depends only on the item (never on B or on another item); no atomics, no host read.
 #include <algorithm>
 
-#include "common.h"
+#include "chunk_grid.h"
 
 namespace {
 
-constexpr int kSgThreads = 256;
-constexpr int kSgChunk = 32;                        // samples per lane of the hop pass
-constexpr int kSgSeg = kSgThreads * kSgChunk;       // 8,192 samples per workgroup
-constexpr int kSgPad = kSgChunk + 4;                // LDS floats per chunk (condition.hip: 16 lanes hit 16 distinct bank quads)
-constexpr int kSgHop = 256, kSgFrame = 1024;
-constexpr int kSgHopChunks = kSgHop / kSgChunk;     // 8 lanes per hop
-constexpr int kSgSegHops = kSgSeg / kSgHop;         // 32
+constexpr int kSgThreads = 256;                     // seg_rows_kernel: items per round of its scan
 constexpr int kSgPlanThreads = 1024;                // the per-item workgroup: one CU's worth of loads in flight
 constexpr int kSgStrip = 8;                         // consecutive frames per lane of the candidate pass: chunks of 8,192 frames
 constexpr int kSgCandTile = 128;                    // candidates staged in LDS for the choice
@@ -52,7 +45,7 @@ struct SegLayout {
 
 SegLayout seg_layout(int S) {
     SegLayout l;
-    l.NH = std::max(1, (int)(((int64_t)S + kSgHop - 1) / kSgHop));
+    l.NH = std::max(1, (int)(((int64_t)S + kGridHop - 1) / kGridHop));
     l.NC = l.NH / 5 + 1;                            // a candidate is >= 4 inactive frames behind an active one
     l.per_item = 2 * (int64_t)l.NH + 2 * (int64_t)l.NC;
     return l;
@@ -67,82 +60,6 @@ struct SegArgs {
     int32_t *flags, *count, *wanted, *frames, *speech_frames;
     double *speech_power, *noise_power;
 };
-
-__device__ __forceinline__ int64_t sg_len(const int64_t* __restrict__ audio_len, int b, int S) {
-    const int64_t len = audio_len[b];
-    return (len < 0 || len > S) ? 0 : len;
-}
-
-__global__ __launch_bounds__(kSgThreads) void seg_hop_kernel(const float* __restrict__ audio, int64_t ld, const int64_t* __restrict__ audio_len,
-                                                             int S, int vec, double* __restrict__ ws, int64_t per_item) {
-    __shared__ __attribute__((aligned(16))) float xs[kSgThreads * kSgPad];
-    __shared__ double part[kSgThreads];
-    const int tid = threadIdx.x, w = blockIdx.x, b = blockIdx.y;
-    const int64_t len = sg_len(audio_len, b, S), base = (int64_t)w * kSgSeg;
-    if (base >= len) return;                                            // (uniform) no frame of the item reads a hop from here
-    const float* row = audio + (int64_t)b * ld;
-    for (int g = tid; g < kSgSeg / 4; g += kSgThreads) {                // xs[chunk c][k] = x(base + 32 c + k), 0 at or past len
-        const int64_t i = base + 4 * (int64_t)g;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (vec && i + 4 <= len) {
-            v = *reinterpret_cast<const f32x4*>(row + i);
-        } else {
-            if (i < len) v.x = row[i];
-            if (i + 1 < len) v.y = row[i + 1];
-            if (i + 2 < len) v.z = row[i + 2];
-            if (i + 3 < len) v.w = row[i + 3];
-        }
-        *reinterpret_cast<f32x4*>(xs + (g >> 3) * kSgPad + (g & 7) * 4) = v;
-    }
-    __syncthreads();
-    double e = 0.0;
-    const float* x = xs + tid * kSgPad;
-#pragma unroll
-    for (int k4 = 0; k4 < kSgChunk / 4; ++k4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + 4 * k4);
-        const double xd[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e = fma(xd[q], xd[q], e);
-    }
-    part[tid] = e;
-    __syncthreads();
-    if (tid < kSgSegHops) {
-        const int64_t h = (int64_t)w * kSgSegHops + tid;
-        if (h * kSgHop < len) {                                         // h < T <= NH
-            double t = 0.0;
-            for (int q = 0; q < kSgHopChunks; ++q) t += part[tid * kSgHopChunks + q];
-            ws[(int64_t)b * per_item + h] = t;
-        }
-    }
-}
-
-__device__ __forceinline__ double sg_frame_power(const double* hop, int t, int nh) {
-    double p = hop[t];
-    if (t + 1 < nh) p += hop[t + 1];
-    if (t + 2 < nh) p += hop[t + 2];
-    if (t + 3 < nh) p += hop[t + 3];
-    return p / (double)kSgFrame;
-}
-
-// Exclusive scan over the workgroup's lanes (Hillis-Steele in LDS), a sum or a max; `total` is the reduction over all lanes.
-// `identity` is what lane 0 gets.  Ends with a barrier, after which buf is free again.
-template <bool kMax, int kThreads>
-__device__ __forceinline__ int sg_scan(int v, int identity, int tid, int* buf, int& total) {
-#pragma unroll 1
-    for (int k = 0; (1 << k) < kThreads; ++k) {
-        buf[tid] = v;
-        __syncthreads();
-        const int src = tid - (1 << k);
-        if (src >= 0) v = kMax ? max(v, buf[src]) : v + buf[src];
-        __syncthreads();
-    }
-    buf[tid] = v;
-    __syncthreads();
-    const int excl = tid ? buf[tid - 1] : identity;
-    total = buf[kThreads - 1];
-    __syncthreads();
-    return excl;
-}
 
 // The choice's state, held by lane 0.
 struct SegChoice {
@@ -186,8 +103,8 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
     __shared__ int64_t ce_s[kSgCandTile], cs_s[kSgCandTile];
     __shared__ int sh_count;
     const int tid = threadIdx.x, b = blockIdx.x;
-    const int64_t len = sg_len(audio_len, b, a.S);
-    const int T = (int)((len + kSgHop - 1) / kSgHop);
+    const int64_t len = valid_len(audio_len, b, a.S);
+    const int T = (int)((len + kGridHop - 1) / kGridHop);
     double* hop = a.ws + (int64_t)b * a.per_item;
     double* pw = hop + a.NH;
     int64_t* ce = reinterpret_cast<int64_t*>(pw + a.NH);
@@ -198,7 +115,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
     for (int t = tid; t < T; t += 4 * kNT) {                            // four frames a round: their loads go out together
         double p[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) p[u] = t + u * kNT < T ? sg_frame_power(hop, t + u * kNT, T) : 0.0;
+        for (int u = 0; u < 4; ++u) p[u] = t + u * kNT < T ? frame_power(hop, t + u * kNT, T) : 0.0;
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             if (t + u * kNT < T) {
@@ -206,13 +123,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
                 mx = fmax(mx, p[u]);
             }
     }
-    red[tid] = mx;
-    __syncthreads();
-    for (int s = kNT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double thr = a.ref_mode == 0 ? red[0] * a.factor : a.ref * a.factor;
+    const double thr = frame_threshold<kNT>(mx, a.ref_mode == 0, a.ref, a.factor, tid, red);
 
     // the first and last active frames
     int f = 0x7fffffff, l = -1;
@@ -222,17 +133,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
             f = min(f, t);
             l = max(l, t);
         }
-    ired[tid] = f, ired[kNT + tid] = l;
-    __syncthreads();
-    for (int s = kNT / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            ired[tid] = min(ired[tid], ired[tid + s]);
-            ired[kNT + tid] = max(ired[kNT + tid], ired[kNT + tid + s]);
-        }
-        __syncthreads();
-    }
-    f = ired[0], l = ired[kNT];
-    __syncthreads();
+    active_range<kNT>(f, l, tid, ired);
 
     int count = 0;
     if (l >= 0) {                                                       // (uniform)
@@ -245,7 +146,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
                 if (t0 + q <= l && pw[t0 + q] > thr) bits |= 1u << q;
             int total;
             const int mine = bits ? (int)t0 + 31 - __clz(bits) : -1;
-            const int prev = max(carry, sg_scan<true, kNT>(mine, -1, tid, ired, total));
+            const int prev = max(carry, block_scan_excl<true, kNT>(mine, -1, tid, ired, total));
             carry = max(carry, total);
             int cnt = 0, pa = prev;
             for (int q = 0; q < kSgStrip; ++q)
@@ -254,7 +155,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
                     cnt += t > f && t - (pa + 1) >= a.msf;
                     pa = t;
                 }
-            int k = n + sg_scan<false, kNT>(cnt, 0, tid, ired, total);
+            int k = n + block_scan_excl<false, kNT>(cnt, 0, tid, ired, total);
             n += total;
             pa = prev;
             for (int q = 0; q < kSgStrip; ++q)
@@ -262,10 +163,10 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
                     const int t = (int)t0 + q;
                     if (t > f && t - (pa + 1) >= a.msf) {
                         const int64_t u = pa + 1, v = t;
-                        const int64_t M = kSgHop * ((u + 3 + v) / 2);
+                        const int64_t M = kGridHop * ((u + 3 + v) / 2);
                         if (k < a.NC) {
-                            ce[k] = std::min<int64_t>(kSgHop * (u + 3 + a.pad), M);
-                            cs[k] = std::max<int64_t>(kSgHop * (v - a.pad), M);
+                            ce[k] = std::min<int64_t>(kGridHop * (u + 3 + a.pad), M);
+                            cs[k] = std::max<int64_t>(kGridHop * (v - a.pad), M);
                         }
                         ++k;
                     }
@@ -276,9 +177,9 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
 
         // the choice, by lane 0
         SegChoice c;
-        c.cur = std::max<int64_t>(0, (int64_t)kSgHop * ((int64_t)f - a.pad));
+        c.cur = trim_start(f, a.pad);
         c.pe = c.ps = 0, c.have = false, c.wanted = 0;
-        const int64_t last = std::min<int64_t>(len, (int64_t)kSgHop * ((int64_t)l + a.pad) + kSgFrame);
+        const int64_t last = trim_end(l, a.pad, len);
         for (int j0 = 0; j0 < n; j0 += kSgCandTile) {
             __syncthreads();                                            // the candidates are written; the tile is free
             const int m = min(kSgCandTile, n - j0);
@@ -300,7 +201,7 @@ __global__ __launch_bounds__(kSgPlanThreads) void seg_plan_kernel(const int64_t*
         for (int k = wave; k < count; k += kNT / kWave) {
             const int64_t o = (int64_t)b * a.K + k;
             const int64_t s = a.segments[2 * o], e = a.segments[2 * o + 1];
-            const int t0 = (int)((s + kSgHop - 1) / kSgHop), t1 = (int)std::min<int64_t>(T, (e + kSgHop - 1) / kSgHop);
+            const int t0 = (int)((s + kGridHop - 1) / kGridHop), t1 = (int)std::min<int64_t>(T, (e + kGridHop - 1) / kGridHop);
             double sp = 0.0, np = 0.0;
             int ns = 0, ni = 0;
             for (int t = t0 + lane; t < t1; t += kWave) {
@@ -354,7 +255,7 @@ __global__ __launch_bounds__(kSgThreads) void seg_rows_kernel(const RowArgs a) {
             for (int k = 0; k < n; ++k) kept += !(a.flags[(int64_t)b * a.K + k] & a.drop);
         }
         int total;
-        int r = done + sg_scan<false, kSgThreads>(kept, 0, tid, buf, total);
+        int r = done + block_scan_excl<false, kSgThreads>(kept, 0, tid, buf, total);
         done += total;
         for (int k = 0; k < n && r < a.R; ++k) {
             const int64_t o = (int64_t)b * a.K + k;
@@ -460,9 +361,9 @@ extern "C" int32_t ispk_segment_plan(const float* audio, int64_t ld_audio, const
     a.speech_power = speech_power, a.noise_power = noise_power;
     const int vec = ld_audio % 4 == 0 && ispk_aligned(audio, 16);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const unsigned W = (unsigned)(((int64_t)S + kSgSeg - 1) / kSgSeg);
+    const unsigned W = (unsigned)(((int64_t)S + kGridSeg - 1) / kGridSeg);
     if (W)
-        hipLaunchKernelGGL(seg_hop_kernel, dim3(W, B), dim3(kSgThreads), 0, st, audio, ld_audio, audio_len, S, vec, a.ws, a.per_item);
+        hipLaunchKernelGGL(hop_sums_kernel<>, dim3(W, B), dim3(kGridThreads), 0, st, audio, ld_audio, audio_len, S, vec, a.ws, a.per_item);
     hipLaunchKernelGGL(seg_plan_kernel, dim3(B), dim3(kSgPlanThreads), 0, st, audio_len, a);
     return ispk_launch_status();
 }

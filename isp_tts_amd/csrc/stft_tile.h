@@ -1,6 +1,7 @@
 // The 1024 / 256 STFT tile: the frame machinery under the Vocos ISTFT head (vocoder.hip), the denoiser (denoise.hip) and
-// Griffin-Lim (griffinlim.hip).  n_fft = win = 1024, hop 256, 513 bins; this header is the only place that knows the tile, and
-// what a kernel does with a frame (its prologue, shrink, projection, error sums, reflection) stays in its own file.
+// Griffin-Lim (griffinlim.hip); the noise reducer and the phase vocoder (noise.hip, stretch.hip) run on it too, and the screen
+// and the noise profile on its analysis-only half.  n_fft = win = 1024, hop 256, 513 bins; this header is the only place that
+// knows the tile, and what a kernel does with a frame (its prologue, shrink, projection, error sums) stays in its own file.
 //
 // Tile.  Grid (ceil(samples / 4096), B), 512 threads = kGroups = 4 groups of kGT = 128.  A workgroup writes kSegs = 16 hop
 // segments (kTile = 4096 samples) of ONE utterance.  With `pad` samples in front of the signal (384 or 512, the caller's framing),
@@ -85,6 +86,43 @@ __device__ __forceinline__ void gather_zero_padded(cf* A, const float* win, int 
         const float xa = live && (unsigned)ia < (unsigned)n ? sample(ia) : 0.f;
         const float xb = live && (unsigned)ib < (unsigned)n ? sample(ib) : 0.f;
         A[m] = make_float2(xa * win[2 * m], xb * win[2 * m + 1]);
+    }
+}
+
+// The same A for frame f of a center = true framing with reflect padding: x[r(256 f - 512 + j)], r the reflection at 0 and
+// n - 1 (n >= 513 and 0 <= f < 1 + n / 256 keep every index inside [0, n)).  Reads HBM: the reflected ends are no tile's own.
+__device__ __forceinline__ void gather_reflected(cf* A, const float* win, const float* __restrict__ xrow, int f, int n, int lt) {
+    const int i0 = f * kHop - kHalf;
+    for (int m = lt; m < kHalf; m += kGT) {
+        int ia = i0 + 2 * m, ib = ia + 1;
+        ia = ia < 0 ? -ia : ia >= n ? 2 * (n - 1) - ia : ia;
+        ib = ib < 0 ? -ib : ib >= n ? 2 * (n - 1) - ib : ib;
+        A[m] = make_float2(xrow[ia] * win[2 * m], xrow[ib] * win[2 * m + 1]);
+    }
+}
+
+// The analysis-only tile (the screen, the noise profile): no synthesis side, so instead of the kSlots frame slots the tile's
+// kAnalysisStage = 4,864 samples - 16 frames of 1024 every 256 - staged once behind the window (carve_tile's `extra`), and one
+// 4 KB pong slot per group behind them: 64,512 B, two workgroups per CU.
+constexpr int kAnalysisStage = kTile + kNfft - kHop;
+constexpr size_t kAnalysisLds = sizeof(cf) * (kTw + kGroups * kHalf) + sizeof(float) * (kNfft + kAnalysisStage + kGroups * kNfft);
+static_assert(kAnalysisStage % 4 == 0, "float4 staging; the pong slots behind the staged samples are float2");
+
+// xs[j] = x(base + j) for j < count (a multiple of 4, as base is: a row that allows float4 loads allows them here), 0 outside
+// [0, n); nothing outside [0, n) is read.  base may be negative (a centred framing's first tile).
+__device__ __forceinline__ void stage_flat(float* xs, const float* __restrict__ row, int base, int n, int count, int vec, int tid) {
+    for (int q = tid; q < count / 4; q += kThreads) {
+        const int i = base + 4 * q;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (vec && i >= 0 && i + 4 <= n) {
+            v = *reinterpret_cast<const f32x4*>(row + i);
+        } else {
+            if (i >= 0 && i < n) v.x = row[i];
+            if (i + 1 >= 0 && i + 1 < n) v.y = row[i + 1];
+            if (i + 2 >= 0 && i + 2 < n) v.z = row[i + 2];
+            if (i + 3 >= 0 && i + 3 < n) v.w = row[i + 3];
+        }
+        *reinterpret_cast<f32x4*>(xs + 4 * q) = v;
     }
 }
 

@@ -94,18 +94,6 @@ __device__ __forceinline__ StPlan st_plan(const int64_t* __restrict__ audio_len,
 
 __device__ __forceinline__ int st_first_frame(int w) { return w > 0 ? w * kSegs - 1 : 0; }   // of output tile / chunk w
 
-// A[m] = the frame's samples 2 m, 2 m + 1 times the window: x[r(256 f - 512 + j)], r the reflection at 0 and n - 1 (n >= 513 and
-// 0 <= f < F keep every index inside [0, n))
-__device__ __forceinline__ void st_gather(cf* A, const float* win, const float* __restrict__ xrow, int f, int n, int lt) {
-    const int i0 = f * kHop - kHalf;
-    for (int m = lt; m < kHalf; m += kGT) {
-        int ia = i0 + 2 * m, ib = ia + 1;
-        ia = ia < 0 ? -ia : ia >= n ? 2 * (n - 1) - ia : ia;
-        ib = ib < 0 ? -ib : ib >= n ? 2 * (n - 1) - ib : ib;
-        A[m] = make_float2(xrow[ia] * win[2 * m], xrow[ib] * win[2 * m + 1]);
-    }
-}
-
 // One bin of one output frame, from the half-length spectra of the analysis frames i_j (Za) and i_j + 1 (Zb): their magnitudes
 // and the unit step u(Xb) conj(u(Xa)), in float64 from the fp32 spectra.
 struct StBin {
@@ -146,7 +134,7 @@ __device__ __forceinline__ void st_stream(const TileLds& tile, cf* ring, const f
     int j = j0;
     while (j < j1) {
         const int f = a + g;
-        if (f < frames) st_gather(A, tile.win, xrow, f, n, lt);
+        if (f < frames) gather_reflected(A, tile.win, xrow, f, n, lt);
         else clear_frame(A, lt);
         __syncthreads();                                                 // (also: per_j's reads of the ring are done)
         fft<false, kGT, kTw>(A, ring + (f & (kStRing - 1)) * kHalf, kHalf, lt, tile.tw);
